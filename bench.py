@@ -8,9 +8,12 @@ error counters (RCCL, only when N > 1).  Weak scaling: every rank owns `--frames
 therefore payload bits and noise) do not depend on the GPU count.
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HBM, algorithmic
-bytes of SURVEY.md section 8d / kernel time from HIP events on the launch stream) and `cpu_baseline`
-(the oracle = CPU restatement of the .m reference, timed on this box's host cores on a bounded
-sample of the same frames; NOT MATLAB).
+bytes of SURVEY.md section 8d / kernel time from HIP events on the launch stream).  A plain run does only what
+that line needs: set up, warm up, time the K steps, print.  `--full` adds the measurements that take runs of their
+own: per-kernel times (`kernels_ms`, `roofline_dominant`), `cpu_baseline` (the oracle = CPU restatement of the .m
+reference, timed on this box's host cores on a bounded sample of the same frames; NOT MATLAB) with its
+`ber_match`, the float64 leg (`f64`) and the C2..C5 configurations (`secondary`).
+`--dump-outputs DIR` writes what the last timed step returned to its caller (see dump_outputs).
 """
 from __future__ import annotations
 
@@ -167,6 +170,22 @@ def f64_leg(ofdm, fr, cfg, dev, dev_index, F, steps, bps, check_frames):
     return r
 
 
+DUMP_BITS_FRAMES = 2048      # frames of decided bits in a --dump-outputs sample: 2048 x 4032 B as float32 = 33 MB
+
+
+def dump_outputs(d, out, ferr, F):
+    """--dump-outputs DIR: the arrays the last timed step returned to its caller, as float32 .npy files (< 64 MB in all).
+    errors.npy = per-frame bit error counts [frames] of the whole job in global frame order; bits.npy = the packed decided
+    bits [n, frame_bytes] (byte values) of a fixed, seeded sample of n = min(F, DUMP_BITS_FRAMES) of rank 0's frames in
+    ascending order (global frames 0 .. F-1, so the sample does not depend on the GPU count)."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    rows = np.sort(np.random.default_rng(0).choice(F, min(F, DUMP_BITS_FRAMES), replace=False))
+    bits = out["bits"][torch.from_numpy(rows).to(out["bits"].device)].cpu().numpy()
+    np.save(os.path.join(d, "errors.npy"), ferr.astype(np.float32))
+    np.save(os.path.join(d, "bits.npy"), bits.astype(np.float32))
+
+
 # Work-skipping ablation switches of rounds 1-2: gone from the shipped library (only the -DOFDM_DIAG build of tools/ has
 # OFDM_WAVE_ABL); a benchmark must not be able to skip work by environment, so their mere presence is refused.
 RESULT_CHANGING_ENV = ("OFDM_WAVE_ABL", "OFDM_CHAIN_SKIP")
@@ -207,7 +226,13 @@ def main():
     ap.add_argument("--no-f64", action="store_true", help="skip the reference-precision (float64) leg of config M")
     ap.add_argument("--f64-steps", type=int, default=150)
     ap.add_argument("--no-secondary", action="store_true", help="skip the C2..C5 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also per-kernel times, the CPU baseline, the float64 leg and C2..C5 (the --no-* switches select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -300,14 +325,15 @@ def main():
     elapsed = time.perf_counter() - t0
     kernel_ms = ev[0].elapsed_time(ev[1]) / args.steps if args.steps else float("nan")
 
-    # per-kernel durations (HIP events inside the library, on the launch stream), outside the timed region
-    plan.set_timing(True)
-    kms = []
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-        kms.append(plan.last_kernel_ms())
-    plan.set_timing(False)
-    kms = np.mean(np.array(kms), axis=0)
+    if args.full:
+        # per-kernel durations (HIP events inside the library, on the launch stream), outside the timed region
+        plan.set_timing(True)
+        kms = []
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+            kms.append(plan.last_kernel_ms())
+        plan.set_timing(False)
+        kms = np.mean(np.array(kms), axis=0)
 
     tmax = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     if world > 1:
@@ -324,6 +350,8 @@ def main():
     ferr = ferr.cpu().numpy()
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out, ferr, F)
         sym_per_step = F * cfg.N_symb * world
         value = sym_per_step * args.steps / elapsed
         csize = 16 if args.precision == "fp64" else 8
@@ -333,11 +361,14 @@ def main():
         # the symbol stage of this geometry (Nfft 2048, fp32) is the one-wavefront-per-frame kernel unless switched off
         sym_kernel = ("rx_symbols_wave_kernel" if args.precision == "fp32" and not os.environ.get("OFDM_FAST_NO_WAVE")
                       else "rx_symbols_kernel")
-        if float(kms[1]) == 0.0:
-            knames, kvals = ["rx_pilot_omp_kernel", sym_kernel], [float(kms[0]), float(kms[2])]
-        else:
-            knames = ["rx_pilot_kernel", "omp_batch_kernel", sym_kernel]
-            kvals = [float(k) for k in kms]
+        chain = "ofdm_rx_chain_task5"
+        if args.full:
+            if float(kms[1]) == 0.0:
+                knames, kvals = ["rx_pilot_omp_kernel", sym_kernel], [float(kms[0]), float(kms[2])]
+            else:
+                knames = ["rx_pilot_kernel", "omp_batch_kernel", sym_kernel]
+                kvals = [float(k) for k in kms]
+            chain += " = " + " + ".join(knames)
         res = {
             "metric": "OFDM sym/s full Task-5 RX (Nfft=2048, 64-QAM, OMP)",
             "value": value, "unit": "OFDM symbols/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -352,10 +383,8 @@ def main():
                              "sha1": __import__("hashlib").sha1(ferr.astype("<i4").tobytes()).hexdigest()},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": None,
-                         "kernel": "ofdm_rx_chain_task5 = " + " + ".join(knames) +
-                                   f" (all launches of one step; dominant: {sym_kernel})",
+                         "kernel": chain + f" (all launches of one step; dominant: {sym_kernel})",
                          "kernel_ms": kernel_ms, "bytes_per_symbol": b_sym},
-            "kernels_ms": dict(zip(knames, kvals)),
             "env": env_in_force(),
         }
         # HBM bytes per step from the committed PMC passes (cannot be collected from inside this process): only
@@ -372,14 +401,16 @@ def main():
             res["roofline"]["algorithmic_bytes"] = b_sym * F * cfg.N_symb
             res["roofline"]["traffic_source"] = (os.path.relpath(tpath, os.path.dirname(pdir)) + ": rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
                                                  "passes of this command (tools/pmc.sh), FETCH_SIZE doubled for gfx950")
-        # dominant kernel alone: symbols 2..S of every frame + stash + bits out + reference bits in
-        nd_, np_ = len(cfg.dataCarriers), len(cfg.pilotCarriers)
-        b_dom = ((cfg.N_symb - 1) * (cfg.Nfft + cfg.T_guard) * csize + cfg.N_carrier * csize
-                 + 2 * cfg.N_symb * nd_ * bps / 8.0) * F
-        res["roofline_dominant"] = {"kernel": sym_kernel, "bound": "hbm", "bytes_per_launch": b_dom,
-                                    "achieved": b_dom / (float(kms[2]) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                                    "unit": "GB/s", "frac": b_dom / (float(kms[2]) * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        if world == 1 and not args.no_cpu:
+        if args.full:
+            res["kernels_ms"] = dict(zip(knames, kvals))
+            # dominant kernel alone: symbols 2..S of every frame + stash + bits out + reference bits in
+            nd_, np_ = len(cfg.dataCarriers), len(cfg.pilotCarriers)
+            b_dom = ((cfg.N_symb - 1) * (cfg.Nfft + cfg.T_guard) * csize + cfg.N_carrier * csize
+                     + 2 * cfg.N_symb * nd_ * bps / 8.0) * F
+            res["roofline_dominant"] = {"kernel": sym_kernel, "bound": "hbm", "bytes_per_launch": b_dom,
+                                        "achieved": b_dom / (float(kms[2]) * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                                        "unit": "GB/s", "frac": b_dom / (float(kms[2]) * 1e-3) / 1e9 / HBM_PEAK_GBS}
+        if args.full and world == 1 and not args.no_cpu:
             ncpu = min(args.cpu_frames, F)
             nall = max(1, min(host_threads(), ncpu // 4))
             nthr = max(1, min(args.cpu_threads, nall))
@@ -401,11 +432,11 @@ def main():
             res["ber_match"] = {"frames": int(ncpu), "gpu_errors": int(gpu_errs.sum()),
                                 "oracle_errors": int(cb["errors"].sum()),
                                 "max_abs_diff_per_frame": int(np.max(np.abs(gpu_errs - cb["errors"])))}
-        if world == 1 and not args.no_f64 and args.precision == "fp32":
+        if args.full and world == 1 and not args.no_f64 and args.precision == "fp32":
             del data, rx, ref, out, plan
             torch.cuda.empty_cache()
             res["f64"] = f64_leg(ofdm, fr, cfg, dev, dev_index, F, args.f64_steps, bps, 0 if args.no_cpu else 256)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             torch.cuda.empty_cache()
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import bench_configs

@@ -9,17 +9,17 @@ root=$PWD
 cd /tmp && export TMPDIR=/tmp && cd $root
 step() { echo "== $1" >> $out/progress.txt; date >> $out/progress.txt; }
 step bench
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $out/bench_20steps.json 2> $out/bench.err
-t0=$SECONDS; timeout -k 10 600 python bench.py > $out/final_bench.json 2>> $out/bench.err || { echo "bench failed"; exit 1; }
-echo "python bench.py (defaults: M fp32 2000 steps + cpu_baseline + f64 leg + C2..C5): $((SECONDS - t0)) s wall" > $out/bench_wall.txt
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $out/bench_20steps.json 2> $out/bench.err
+t0=$SECONDS; timeout -k 10 600 python bench.py --full > $out/final_bench.json 2>> $out/bench.err || { echo "bench failed"; exit 1; }
+echo "python bench.py --full (defaults: M fp32 2000 steps + cpu_baseline + f64 leg + C2..C5): $((SECONDS - t0)) s wall" > $out/bench_wall.txt
 step smoke
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.txt 2>&1 || echo "smoke failed"
 step stats
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --no-cpu --no-f64 --no-secondary --steps 600 --warmup 40 > $out/stats_bench.json 2> $out/stats.err || { echo "stats pass failed"; exit 1; }
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python bench.py --full --no-cpu --no-f64 --no-secondary --steps 600 --warmup 40 > $out/stats_bench.json 2> $out/stats.err || { echo "stats pass failed"; exit 1; }
 cp $out/stats/*/*kernel_stats.csv $out/final_kernel_stats.csv
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats64 -- python bench.py --no-cpu --no-secondary --precision fp64 --steps 200 --warmup 20 > $out/stats_bench_f64.json 2> $out/stats64.err && cp $out/stats64/*/*kernel_stats.csv $out/f64_kernel_stats.csv
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats64 -- python bench.py --full --no-cpu --no-secondary --precision fp64 --steps 200 --warmup 20 > $out/stats_bench_f64.json 2> $out/stats64.err && cp $out/stats64/*/*kernel_stats.csv $out/f64_kernel_stats.csv
 step bench2
-timeout -k 10 600 python bench.py --gpus 2 --backend gloo --force-device 0 --steps 200 --warmup 20 --frames 8192 > $out/bench_gpus2_gloo_rehearsal.json 2> $out/bench2.err || echo "2-rank rehearsal failed"
+timeout -k 10 600 python bench.py --full --gpus 2 --backend gloo --force-device 0 --steps 200 --warmup 20 --frames 8192 > $out/bench_gpus2_gloo_rehearsal.json 2> $out/bench2.err || echo "2-rank rehearsal failed"
 export C5_WARM_S=0.5
 for c in c3 c4 c5; do
   step $c
