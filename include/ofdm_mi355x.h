@@ -254,6 +254,30 @@ int ofdm_tx_frames_ex(ofdm_rx_plan* plan, const void* h, int h_len, double snr_d
  * reference's drivers, which add the noise before the channel -- use ofdm_tx_frames_ex(noise_first = 1) for that). */
 int ofdm_tx_frames(ofdm_rx_plan* plan, const void* h, int h_len, double snr_db, int noise_on, uint64_t seed,
                    int64_t frame0, int64_t n_frames, void* rx_out, uint8_t* ref_bits_out, uint8_t* bits_out, int flags);
+/* Reference-order frame generator in three sample passes (T5/Main_model_Task_5.m:50-127, T5/Noise.m:3-10,
+ * T5/Task5_part2.m:134,:152): payload -> [Scrambler per frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator
+ * -> Noise(snr_db) -> conv(h) truncated per frame.  The same draws as ofdm_tx_frames_ex(noise_first = 1, sto_mode =
+ * cfo_mode = 0, noise_on = 1): payload Philox (seed, frame0 + f), noise Philox counter (i, 0, frame0 + f, 0) with the
+ * Box-Muller of ofdm_Noise, the noise power from the frame's own mean |x|^2 (Noise.m:3).  No STO / CFO (the Task-5
+ * receiver has no synchroniser; Task-4 sweeps keep ofdm_tx_frames_ex).  h: HOST array of h_len complex taps in the precision
+ * of `flags`, at most 64 nonzero taps at delays <= 4096 (NULL = no channel); scr_reg15: HOST uint8[15] or NULL.
+ * rx_out [frame_samples x n_frames], ref_bits_out (packed payload bits, optional), sc_ref_bits_out (packed scrambled bits,
+ * optional, Scrambler on) live where `flags` says.  Results depend on (seed, frame0 + f) only, not on the batching. */
+int ofdm_tx_frames_fused(ofdm_rx_plan* plan, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
+                         int64_t n_frames, const uint8_t* scr_reg15, void* rx_out, uint8_t* ref_bits_out,
+                         uint8_t* sc_ref_bits_out, int flags);
+/* One tile of a BER(SNR) sweep (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152): for each point p the frames
+ * frame0 .. frame0 + frames_per_point - 1 are generated as ofdm_tx_frames_fused(h, snr_db[p], seeds[p], ...) and decoded by
+ * ofdm_rx_chain_task5 on this plan, each frame once.  snr_db[n_points] / seeds[n_points]: HOST arrays.
+ * errors_out[n_points] (uint64): bit errors per point; frame_errors_out (optional): [n_points][frames_per_point] uint32;
+ * both live where `flags` says.  With scr_reg15 (HOST uint8[15]) the plan must carry a DeScrambler with the same register
+ * and the errors count against the payload bits (T3/Main_model_Task_3.m:237-265); without it the plan must not descramble.
+ * An MMSE-mode plan is accepted only with n_points == 1 (its operator is built for one SNR).
+ * max_frames_per_chunk: 0 = the library's choice (a workspace of about 2 GB); results do not depend on it.
+ * With OFDM_DEVICE nothing synchronises the host (apart from a first-call workspace growth) and nothing is reduced on it. */
+int ofdm_ber_sweep_task5(ofdm_rx_plan* plan, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                         int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                         int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags);
 /* Per-frame DeScrambler inside ofdm_rx_chain_task5 / ofdm_rx_chain_task4 (T5/DeScrambler.m:1-16 with
  * the register reset for every frame, T5/Main_model_Task_5.m:257-274, T4/Main_model_Task_4.m:354-364): the demapped bits
  * of a frame go through d[i] = s[i] ^ s[i-13] ^ s[i-14], s[-m] = reg15[m-1], before they are written to bits_out and

@@ -750,6 +750,92 @@ class RxPlan:
             out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
+    def _fused_args(self, h, Register, what):
+        cdt_np = np.complex128 if self.f64 else np.complex64
+        hh = None
+        if h is not None:
+            hh = np.ascontiguousarray(np.asarray(h.cpu().numpy() if _is_torch(h) else h).ravel().astype(cdt_np))
+        reg = None
+        if Register is not None:
+            reg = np.ascontiguousarray(np.asarray(Register).ravel().astype(np.uint8))
+            if reg.size != 15:
+                raise OfdmError(f"{what}: Register must have 15 entries")
+        ph = hh.ctypes.data_as(C.c_void_p) if hh is not None else None
+        pr = reg.ctypes.data_as(C.c_void_p) if reg is not None else None
+        return (hh, reg), ph, 0 if hh is None else hh.size, pr
+
+    def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None):
+        """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
+        frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(SNR) -> conv(h) truncated
+        (T5/Main_model_Task_5.m:50-127, T5/Task5_part2.m:134,:152).  The draws of tx_frames(noise_first=True): the same
+        frames up to rounding.  No STO / CFO.  h=None: no channel.
+        Returns dict(rx=[frame_samples, n_frames], packed=[n_frames, frame_bytes] (the payload bits)
+        (+ sc_packed = the scrambled bits when Register is given)); torch CUDA tensors when `device` is given."""
+        n_frames = int(n_frames)
+        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
+        scr = Register is not None
+        if device is not None:
+            dev = torch.device(device)
+            rx = torch.empty((n_frames, self.frame_samples), dtype=torch.complex128 if self.f64 else torch.complex64,
+                             device=dev)
+            packed = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev)
+            scp = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev) if scr else None
+            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            flags |= L.OFDM_DEVICE
+        else:
+            L.check(self.lib.ofdm_set_stream(None), "set_stream")
+            rx = np.empty((n_frames, self.frame_samples), dtype=np.complex128 if self.f64 else np.complex64)
+            packed = np.empty((n_frames, self.frame_bytes), dtype=np.uint8)
+            scp = np.empty((n_frames, self.frame_bytes), dtype=np.uint8) if scr else None
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        keep, ph, nh, pr = self._fused_args(h, Register, "tx_frames_fused")
+        L.check(self.lib.ofdm_tx_frames_fused(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr, ptr(rx),
+                                              ptr(packed), ptr(scp), flags), "tx_frames_fused")
+        out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
+        if scr:
+            out["sc_packed"] = scp
+        return out
+
+    def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
+                  want_frame_errors=False, max_frames_per_chunk=0):
+        """One device-resident tile of a BER(SNR) sweep (ofdm_ber_sweep_task5): for every SNR of `SNRs` the frames
+        frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p]) decoded by rx_chain_task5 on this plan
+        (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152).  seeds: one Philox key per point (default: `seed`
+        for every point).  With Register the plan must descramble with the same register (set_descrambler) and the
+        errors count against the payload bits.
+        Returns dict(errors=[n_points] int64 bit errors, bits=bits counted per point, frame_errors=[n_points,
+        frames_per_point] (with want_frame_errors)); torch tensors on `device` (no host synchronisation) when it is given,
+        numpy arrays otherwise."""
+        snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
+        n = snr.size
+        fpp = int(frames_per_point)
+        sd = np.full(n, int(seed), dtype=np.uint64) if seeds is None else \
+            np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
+        if sd.size != n:
+            raise OfdmError("ber_sweep: seeds must have one entry per SNR point")
+        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
+        if device is not None:
+            dev = torch.device(device)
+            err = torch.empty((n,), dtype=torch.int64, device=dev)
+            fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
+            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            flags |= L.OFDM_DEVICE
+        else:
+            L.check(self.lib.ofdm_set_stream(None), "set_stream")
+            err = np.empty((n,), dtype=np.uint64)
+            fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
+        L.check(self.lib.ofdm_ber_sweep_task5(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
+                                              sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                              int(max_frames_per_chunk), ptr(err), ptr(fe), flags), "ber_sweep_task5")
+        out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
+        if want_frame_errors:
+            out["frame_errors"] = fe
+        return out
+
     def set_timing(self, enable=True):
         L.check(self.lib.ofdm_rx_plan_set_timing(self.handle, int(bool(enable))), "rx_plan_set_timing")
 

@@ -1,0 +1,431 @@
+// ofdm_tx_frames_fused / ofdm_ber_sweep_task5: the reference-order frame generator in three sample passes, and one
+// device-resident tile of a BER(SNR) sweep on top of it (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152).
+//
+// Per frame (T5/Main_model_Task_5.m:50-127, Noise.m:3-10):
+//   payload -> [Scrambler per frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(snr_db) -> conv(h) truncated
+// with the draws of ofdm_tx_frames_ex(noise_first = 1): payload Philox (seed, frame0 + f), noise Philox counter
+// (i, 0, frame0 + f, 0) through awgn_kernel's Box-Muller, per-frame noise power from the frame's own mean |x|^2.
+//
+//   tx_symbols_fused_kernel<T, N>   one transform per symbol (the wg_fft of mod_kernel): the carriers are built in registers
+//                                   from the plan's role tables and the payload draw (no X buffer), 1/N, symbol + CP written
+//                                   once, and the symbol's sum |x|^2 (CP included, double) into partial[frame][symbol].
+//   tx_channel_fused_kernel<T>      one workgroup per (segment of TXF_SEG samples, frame): sigma from the frame's partials
+//                                   (fixed order, no atomics), segment + halo of max_delay samples loaded into LDS with the
+//                                   noise added (the halo's noise is regenerated: it is a pure function of the counter),
+//                                   the sparse FIR from LDS with the taps in kernel arguments, rx written once (nontemporal).
+//   ber_point_reduce_kernel         per-frame uint32 errors -> per-point uint64 (integers: exact in any order).
+// TX samples: one write, one read (+ halo), RX: one write -- 3 sample passes against ~9 for ofdm_tx_frames_ex's stages.
+#include <algorithm>
+#include <type_traits>
+
+#include "fft_core.hpp"
+#include "rx_plan.hpp"
+#include "tx_philox.hpp"
+
+namespace ofdm {
+int tx_dict_device(ofdm_rx_plan* pl);                                                       // ofdm_txgen.hip
+int tx_bits_device(const ofdm_rx_plan* pl, uint32_t* packed, uint8_t* bits, uint32_t k0, uint32_t k1, uint32_t stream0,
+                   int64_t nf);
+int tx_pack_bits_device(const ofdm_rx_plan* pl, const uint8_t* bits, uint32_t* packed, int64_t nf);
+
+constexpr int TXF_MAX_TAPS = 64;
+constexpr int TXF_MAX_DELAY = 4096;
+constexpr int TXF_SEG = 4096;                       // output samples per channel workgroup
+constexpr size_t TXF_WS_BUDGET = size_t(2) << 30;   // chunk cap of the plan-owned workspace
+
+template <typename T>
+struct TxfTaps {
+  int32_t delay[TXF_MAX_TAPS];
+  cx<T> amp[TXF_MAX_TAPS];
+  int n;
+  int halo;                                          // largest delay: samples before a segment the FIR reaches back to
+};
+
+// ---------------------------------------------------------------------------------------------
+// map_carriers + OFDM_modulator of one symbol per transform, carriers from the role tables
+// ---------------------------------------------------------------------------------------------
+template <typename T, int N>
+__global__ __launch_bounds__(fft_wg_threads(N)) void tx_symbols_fused_kernel(
+    cx<T>* __restrict__ tx, double* __restrict__ partial, const cx<T>* __restrict__ tw, const int16_t* __restrict__ prole,
+    const int16_t* __restrict__ drole, const cx<T>* __restrict__ pilots, const cx<T>* __restrict__ dict,
+    const uint8_t* __restrict__ sc_bits, int n_symb, int t_guard, int nd, int bps, uint32_t k0, uint32_t k1,
+    uint32_t stream0, int64_t n_sym_total) {
+  constexpr int TPX = N / 8;
+  constexpr int XPW = fft_xforms_per_wg(N);
+  __shared__ cx<T> lds[XPW * fft_lds_elems(N)];
+  const int g = threadIdx.x / TPX;
+  const int j = threadIdx.x % TPX;
+  const int64_t q = (int64_t)blockIdx.x * XPW + g;              // symbol of the chunk, frame-major
+  const bool live = q < n_sym_total;
+  const int64_t f = live ? q / n_symb : 0;
+  const int s = live ? (int)(q - f * n_symb) : 0;
+  const int64_t frame_bits = (int64_t)nd * n_symb * bps;
+  cx<T> v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = j + e * TPX;
+    const int p = prole[k], d = drole[k];
+    cx<T> val = mk<T>(0, 0);
+    if (live) {
+      if (p >= 0) val = pilots[p];                               // pilot rows written last in OFDM_map_carriers.m:8
+      else if (d >= 0) {
+        uint32_t code;
+        if (sc_bits) {                                           // the frame's scrambled bits, bps per symbol, MSB first
+          const uint8_t* b = sc_bits + f * frame_bits + ((int64_t)s * nd + d) * bps;
+          code = 0;
+          for (int r = 0; r < bps; ++r) code = (code << 1) | (uint32_t)(b[r] & 1u);
+        } else {
+          code = payload_code((uint64_t)s * nd + d, stream0 + (uint32_t)f, k0, k1, bps);
+        }
+        val = dict[code];
+      }
+    }
+    v[e] = val;
+  }
+  wg_fft<T, N, true>(v, j, tw, lds + g * fft_lds_elems(N));
+  double ps = 0;
+  if (live) {
+    const T scale = T(1) / T(N);
+    cx<T>* dst = tx + q * (int64_t)(N + t_guard);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int idx = j + e * TPX;
+      const cx<T> val = v[e] * scale;
+      const double e2 = (double)val.x * (double)val.x + (double)val.y * (double)val.y;
+      dst[t_guard + idx] = val;
+      ps += e2;
+      if (idx >= N - t_guard) {                                  // OFDM_modulator.m:8-9
+        dst[idx - (N - t_guard)] = val;
+        ps += e2;
+      }
+    }
+  }
+  // the symbol's sum: butterfly inside the transform's lanes (a fixed order), then the waves of a multi-wave transform
+  constexpr int W = TPX < 64 ? TPX : 64;
+#pragma unroll
+  for (int off = W / 2; off > 0; off >>= 1) ps += __shfl_xor(ps, off, 64);
+  if constexpr (TPX <= 64) {
+    if (j == 0 && live) partial[q] = ps;
+  } else {
+    constexpr int NWV = TPX / 64;                                // waves per transform (N = 1024: two transforms of two)
+    __shared__ double wsum[XPW * NWV];
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = ps;
+    __syncthreads();
+    if (j == 0 && live) {
+      double t = 0;
+      for (int w = 0; w < NWV; ++w) t += wsum[g * NWV + w];
+      partial[q] = t;
+    }
+  }
+}
+
+// x + sigma * (n_re + i n_im): awgn_kernel's Box-Muller on the same Philox words, in the same arithmetic per precision
+template <typename T>
+__device__ __forceinline__ cx<T> txf_noisy(cx<T> v, int64_t i, double sg, uint32_t stream, uint32_t k0, uint32_t k1) {
+  uint32_t r[4];
+  philox_words((uint32_t)i, (uint32_t)((uint64_t)i >> 32), stream, 0u, k0, k1, r);
+  const double u0 = ((double)r[0] + 0.5) * 2.3283064365386963e-10;
+  const double u1 = ((double)r[1] + 0.5) * 2.3283064365386963e-10;
+  if constexpr (std::is_same<T, float>::value) {
+    const float rad = sqrtf(-2.0f * logf((float)u0)) * (float)sg;
+    float sn, cs;
+    sincospif((float)(2.0 * u1), &sn, &cs);
+    return mk<T>(v.x + rad * cs, v.y + rad * sn);
+  } else {
+    const double rad = sqrt(-2.0 * log(u0));
+    double sn, cs;
+    sincospi(2.0 * u1, &sn, &cs);
+    return mk<T>((T)((double)v.x + sg * rad * cs), (T)((double)v.y + sg * rad * sn));
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Noise (Noise.m:3-10) then conv(h) truncated per frame (T5/Task5_part2.m:152), one segment per workgroup.
+// grid = (segments, frames); dynamic LDS = (TXF_SEG + halo) samples.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_fused_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                               const double* __restrict__ partial, int n_symb, int64_t len,
+                                                               double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                               TxfTaps<T> taps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char txf_smem[];
+  cx<T>* buf = (cx<T>*)txf_smem;
+  const int64_t f = blockIdx.y;
+  const int64_t n0 = (int64_t)blockIdx.x * TXF_SEG;
+  const int H = taps.halo;
+  const cx<T>* x = tx + f * len;
+  double sum = 0;                                                // Noise.m:3 -- the frame's symbols in order
+  for (int i = 0; i < n_symb; ++i) sum += partial[f * n_symb + i];
+  const double sg = sqrt(sum / (double)len / snr_lin / 2.0);     // :5, per-component sigma
+  const uint32_t stream = stream0 + (uint32_t)f;
+  for (int i = threadIdx.x; i < TXF_SEG + H; i += 256) {
+    const int64_t idx = n0 - H + i;                              // before the frame: silence (no signal, no noise)
+    cx<T> v = mk<T>(0, 0);
+    if (idx >= 0 && idx < len) v = txf_noisy<T>(x[idx], idx, sg, stream, k0, k1);
+    buf[i] = v;
+  }
+  __syncthreads();
+  cx<T>* y = rx + f * len;
+  for (int o = threadIdx.x; o < TXF_SEG; o += 256) {
+    if (n0 + o >= len) break;
+    cx<T> acc = mk<T>(0, 0);
+    for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
+    nt_store(y + n0 + o, acc);
+  }
+}
+
+__global__ __launch_bounds__(256) void ber_point_reduce_kernel(const uint32_t* __restrict__ frame_errors,
+                                                               int64_t frames_per_point,
+                                                               unsigned long long* __restrict__ errors) {
+  const int64_t p = blockIdx.x;
+  unsigned long long s = 0;
+  for (int64_t i = threadIdx.x; i < frames_per_point; i += 256) s += frame_errors[p * frames_per_point + i];
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  __shared__ unsigned long long part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) errors[p] = part[0] + part[1] + part[2] + part[3];
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+struct TxfChannel {                                  // nonzero taps of h (conv_common's rule: exact zeros are skipped)
+  std::vector<int32_t> delay;
+  std::vector<c64> amp;
+  int halo = 0;
+};
+
+static int txf_channel(const void* h, int h_len, bool f64, TxfChannel& ch) {
+  OFDM_ARG(h_len >= 0 && (h || h_len == 0), "tx_frames_fused: bad channel");
+  if (!h || h_len == 0) {                            // no channel: one unit tap (x * (1 + 0i) is exact)
+    ch.delay.assign(1, 0);
+    ch.amp.assign(1, c64{1.0, 0.0});
+    return OFDM_OK;
+  }
+  for (int d = 0; d < h_len; ++d) {
+    const double re = f64 ? ((const c64*)h)[d].x : ((const c32*)h)[d].x;
+    const double im = f64 ? ((const c64*)h)[d].y : ((const c32*)h)[d].y;
+    if (re != 0.0 || im != 0.0) {
+      OFDM_ARG(d <= TXF_MAX_DELAY, "tx_frames_fused: channel tap at delay %d (at most %d)", d, TXF_MAX_DELAY);
+      ch.delay.push_back(d);
+      ch.amp.push_back(c64{re, im});
+      ch.halo = d;
+    }
+  }
+  OFDM_ARG((int)ch.delay.size() <= TXF_MAX_TAPS, "tx_frames_fused: %d nonzero channel taps (at most %d)",
+           (int)ch.delay.size(), TXF_MAX_TAPS);
+  return OFDM_OK;
+}
+
+template <typename T>
+static TxfTaps<T> txf_taps(const TxfChannel& ch) {
+  TxfTaps<T> tp{};
+  tp.n = (int)ch.delay.size();
+  tp.halo = ch.halo;
+  for (int t = 0; t < tp.n; ++t) {
+    tp.delay[t] = ch.delay[t];
+    tp.amp[t] = mk<T>((T)ch.amp[t].x, (T)ch.amp[t].y);
+  }
+  return tp;
+}
+
+template <typename T, int N>
+static int launch_symbols(const ofdm_rx_plan* pl, const void* tw, void* tx, double* partial, const uint8_t* sc_bits,
+                          uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf) {
+  constexpr int XPW = fft_xforms_per_wg(N);
+  const int64_t n_sym = (int64_t)pl->n_symb * nf;
+  hipLaunchKernelGGL((tx_symbols_fused_kernel<T, N>), dim3(cdiv_u(n_sym, XPW)), dim3(fft_wg_threads(N)), 0, ctx().stream,
+                     (cx<T>*)tx, partial, (const cx<T>*)tw, (const int16_t*)pl->d_prole, (const int16_t*)pl->d_drole,
+                     (const cx<T>*)pl->d_pilots, (const cx<T>*)pl->d_dict, sc_bits, pl->n_symb, pl->t_guard, pl->nd, pl->bps,
+                     k0, k1, stream0, n_sym);
+  return check_launch("tx_symbols_fused_kernel");
+}
+
+template <typename T>
+static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
+                          double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf) {
+  const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
+  // > 64 KB for long channels: the attribute is per device, so it is set on every launch (not cached per process)
+  OFDM_HIP(hipFuncSetAttribute((const void*)tx_channel_fused_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  hipLaunchKernelGGL(tx_channel_fused_kernel<T>, dim3(cdiv_u(len, TXF_SEG), (unsigned)nf), dim3(256), dyn, ctx().stream,
+                     (const cx<T>*)tx, (cx<T>*)rx, partial, pl->n_symb, len, snr_lin, k0, k1, stream0, txf_taps<T>(ch));
+  return check_launch("tx_channel_fused_kernel");
+}
+
+// chunk buffers inside the plan-owned workspace
+struct TxfBuffers {
+  void* tx = nullptr;
+  double* partial = nullptr;
+  uint8_t* b0 = nullptr;                             // Scrambler on: payload bits, one byte each
+  uint8_t* b1 = nullptr;                             // Scrambler on: scrambled bits
+  void* rx = nullptr;                                // sweep: the chunk's RX frames
+  uint32_t* ref = nullptr;                           // sweep: their packed reference bits
+};
+
+static size_t a256(size_t b) { return (b + 255) & ~size_t(255); }
+
+static size_t txf_frame_bytes(const ofdm_rx_plan* pl, bool scr, bool sweep) {
+  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
+  const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
+  return cs * fs * (sweep ? 2 : 1) + 8 * (size_t)pl->n_symb + (scr ? 2 * frame_bits : 0) +
+         (sweep ? (size_t)pl->frame_words * 4 : 0);
+}
+
+static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, TxfBuffers& b) {
+  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
+  const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
+  const size_t t_bytes = a256(cs * fs * ch), p_bytes = a256(8 * (size_t)pl->n_symb * ch);
+  const size_t b_bytes = scr ? a256(frame_bits * ch) : 0;
+  const size_t r_bytes = sweep ? t_bytes : 0, f_bytes = sweep ? a256((size_t)pl->frame_words * 4 * ch) : 0;
+  const size_t need = t_bytes + p_bytes + 2 * b_bytes + r_bytes + f_bytes;
+  if (pl->ws_txf_bytes < need) {
+    OFDM_HIP(hipStreamSynchronize(ctx().stream));
+    if (pl->ws_txf) { (void)hipFree(pl->ws_txf); pl->ws_txf = nullptr; pl->ws_txf_bytes = 0; }
+    OFDM_HIP(hipMalloc(&pl->ws_txf, need));
+    pl->ws_txf_bytes = need;
+  }
+  unsigned char* base = (unsigned char*)pl->ws_txf;
+  b.tx = base;
+  b.partial = (double*)(base + t_bytes);
+  unsigned char* q = base + t_bytes + p_bytes;
+  if (scr) { b.b0 = q; b.b1 = q + b_bytes; q += 2 * b_bytes; }
+  if (sweep) { b.rx = q; b.ref = (uint32_t*)(q + r_bytes); }
+  return OFDM_OK;
+}
+
+static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n_frames, int64_t user_cap) {
+  int64_t ch = user_cap > 0 ? user_cap : std::max<int64_t>(1, (int64_t)(TXF_WS_BUDGET / txf_frame_bytes(pl, scr, sweep)));
+  return std::max<int64_t>(1, std::min<int64_t>({ch, n_frames, 65535}));
+}
+
+// one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
+static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                        int64_t nf, const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref) {
+  const int64_t frame_bits = (int64_t)pl->nd * pl->n_symb * pl->bps;
+  OFDM_TRY(tx_bits_device(pl, ref, scr_reg15 ? b.b0 : nullptr, k0, k1, stream0, nf));
+  if (scr_reg15) {                                              // Scrambler.m per frame, register reset (T5:58-69)
+    OFDM_TRY(ofdm_Scrambler_frames(scr_reg15, b.b0, frame_bits, nf, b.b1, OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0)));
+    if (scref) OFDM_TRY(tx_pack_bits_device(pl, b.b1, scref, nf));
+  }
+  const void* tw = nullptr;
+  OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
+  const uint8_t* sc = scr_reg15 ? b.b1 : nullptr;
+#define CALL(NN)                                                                                       \
+  if (pl->f64) OFDM_TRY((launch_symbols<double, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf))); \
+  else OFDM_TRY((launch_symbols<float, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf)));
+  OFDM_FFT_DISPATCH(pl->nfft, CALL)
+#undef CALL
+  if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
+  else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
+  return OFDM_OK;
+}
+
+static int txf_check_plan(ofdm_rx_plan* pl, int flags, int64_t frame0, int64_t n_frames, const char* what) {
+  OFDM_PLAN_DEVICE(pl);
+  OFDM_ARG((is_f64(flags) ? 1 : 0) == pl->f64, "%s: precision flag differs from the plan's", what);
+  OFDM_ARG(pl->nd >= 1, "%s: the plan has no data carriers", what);
+  OFDM_ARG(pl->pilots_in_band, "%s: pilots outside 1..N_carrier are not supported", what);
+  OFDM_ARG(fft_size_ok(pl->nfft) && pl->t_guard <= pl->nfft, "%s: unsupported Nfft %d / T_guard %d", what, pl->nfft,
+           pl->t_guard);
+  OFDM_ARG(frame0 >= 0 && n_frames >= 0 && frame0 + n_frames < ((int64_t)1 << 32),
+           "%s: frame index outside the 32-bit stream range", what);
+  return OFDM_OK;
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_tx_frames_fused(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
+                                    int64_t n_frames, const uint8_t* scr_reg15, void* rx_out, uint8_t* ref_bits_out,
+                                    uint8_t* sc_ref_bits_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused: sc_ref_bits_out needs the Scrambler register");
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  if (n_frames == 0) return OFDM_OK;
+  OFDM_TRY(tx_dict_device(pl));
+  const size_t cs = csize(flags);
+  const int64_t frame_samples = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t fb = (size_t)pl->frame_words * 4;
+  Stage st(flags);
+  void *drx, *dref, *dscref;
+  OFDM_TRY(st.out(rx_out, cs * (size_t)frame_samples * n_frames, &drx));
+  OFDM_TRY(st.out(ref_bits_out, fb * n_frames, &dref));
+  OFDM_TRY(st.out(sc_ref_bits_out, fb * n_frames, &dscref));
+  const bool scr = scr_reg15 != nullptr;
+  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0);
+  TxfBuffers b;
+  OFDM_TRY(txf_workspace(pl, CH, scr, false, b));
+  const double snr_lin = std::pow(10.0, snr_db / 10.0);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  for (int64_t c0 = 0; c0 < n_frames; c0 += CH) {
+    const int64_t nf = std::min<int64_t>(CH, n_frames - c0);
+    OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b,
+                          (unsigned char*)drx + cs * (size_t)frame_samples * c0,
+                          dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
+                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr));
+  }
+  return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && max_frames_per_chunk >= 0 && errors_out,
+           "ber_sweep_task5: bad arguments");
+  OFDM_ARG(n_points == 0 || (snr_db && seeds), "ber_sweep_task5: snr_db / seeds missing");
+  OFDM_ARG(n_points < ((int64_t)1 << 31), "ber_sweep_task5: too many points");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task5"));
+  OFDM_ARG(!pl->d_wt || n_points <= 1, "ber_sweep_task5: an MMSE-mode plan is built for one SNR (n_points must be 1)");
+  if (scr_reg15) {                                              // errors against the payload: the plan must descramble
+    uint32_t d = DESCR_ON;
+    for (int m = 1; m <= 14; ++m) {
+      OFDM_ARG(scr_reg15[m - 1] <= 1, "ber_sweep_task5: register entries must be 0 or 1");
+      d |= (uint32_t)scr_reg15[m - 1] << (m - 1);
+    }
+    OFDM_ARG(pl->descr == d, "ber_sweep_task5: with the Scrambler on the plan needs a DeScrambler with the same register "
+                             "(ofdm_rx_plan_set_descrambler)");
+  } else {
+    OFDM_ARG(!(pl->descr & DESCR_ON), "ber_sweep_task5: the plan descrambles but the frames are not scrambled");
+  }
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  if (n_points == 0) return OFDM_OK;
+  Stage st(flags);
+  void *derr, *dfe;
+  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
+  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
+  if (frames_per_point == 0) {
+    OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, ctx().stream));
+    return st.finish();
+  }
+  if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
+  OFDM_TRY(tx_dict_device(pl));
+  const bool scr = scr_reg15 != nullptr;
+  const int64_t CH = txf_chunk(pl, scr, true, frames_per_point, max_frames_per_chunk);
+  TxfBuffers b;
+  OFDM_TRY(txf_workspace(pl, CH, scr, true, b));
+  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
+  for (int64_t p = 0; p < n_points; ++p) {
+    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
+    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
+    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
+      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
+      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr));
+      OFDM_TRY(ofdm_rx_chain_task5(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
+                                   (uint32_t*)dfe + p * frames_per_point + c0, nullptr, nullptr, rxflags));
+    }
+  }
+  hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)dfe,
+                     frames_per_point, (unsigned long long*)derr);
+  OFDM_TRY(check_launch("ber_point_reduce_kernel"));
+  return st.finish();
+}

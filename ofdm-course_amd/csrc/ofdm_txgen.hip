@@ -18,45 +18,12 @@
 #include <algorithm>
 
 #include "rx_plan.hpp"
+#include "tx_philox.hpp"
 
 namespace ofdm {
 int mod_device(const void* x, void* y, int nfft, int64_t n_symb, int t_guard, bool f64);     // ofdm_modem.hip
 int sto_cfo_frames_device(const void* y, void* out, int64_t len, int64_t n_frames, const int64_t* d_sto, const double* d_cfo,
                           int nfft, bool f64);                                              // ofdm_channel.hip
-
-__device__ __forceinline__ uint32_t payload_code(uint64_t j, uint32_t stream, uint32_t k0, uint32_t k1, int bps) {
-  uint32_t c0 = (uint32_t)j, c1 = (uint32_t)(j >> 32), c2 = stream, c3 = 1u;
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c0 >> (32 - bps);
-}
-
-__device__ __forceinline__ void philox_words(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                             uint32_t (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-    const uint32_t n1 = (uint32_t)p1;
-    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    const uint32_t n3 = (uint32_t)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
 
 // per-frame impairment draws of T4/Main_model_Task_4.m:101-110 (mode 1: the fixed value, mode 2: drawn)
 __global__ __launch_bounds__(256) void tx_draw_kernel(int64_t* __restrict__ sto, double* __restrict__ cfo, int sto_mode,
@@ -142,6 +109,41 @@ __global__ __launch_bounds__(256) void tx_bits_kernel(uint32_t* __restrict__ pac
   }
 }
 
+// constellation table in the plan's precision (built on the first generator call)
+int tx_dict_device(ofdm_rx_plan* pl) {
+  if (pl->d_dict) return OFDM_OK;
+  const size_t n = pl->dict.size();
+  OFDM_HIP(hipMalloc(&pl->d_dict, (pl->f64 ? sizeof(c64) : sizeof(c32)) * n));
+  if (pl->f64) {
+    OFDM_HIP(hipMemcpy(pl->d_dict, pl->dict.data(), sizeof(c64) * n, hipMemcpyHostToDevice));
+  } else {
+    std::vector<c32> d32(n);
+    for (size_t i = 0; i < n; ++i) d32[i] = c32{(float)pl->dict[i].x, (float)pl->dict[i].y};
+    OFDM_HIP(hipMemcpy(pl->d_dict, d32.data(), sizeof(c32) * n, hipMemcpyHostToDevice));
+  }
+  return OFDM_OK;
+}
+
+// launchers of tx_bits_kernel / tx_pack_bits_kernel for the fused generator (ofdm_txfused.hip); nf frames from stream0
+int tx_bits_device(const ofdm_rx_plan* pl, uint32_t* packed, uint8_t* bits, uint32_t k0, uint32_t k1, uint32_t stream0,
+                   int64_t nf) {
+  if (nf == 0 || (!packed && !bits)) return OFDM_OK;
+  const int64_t groups = (int64_t)(((int64_t)pl->nd * pl->n_symb + 31) >> 5) * nf;
+  const unsigned g2 = (unsigned)std::min<int64_t>((groups + 255) / 256, (int64_t)ctx().num_cu * 16);
+  hipLaunchKernelGGL(tx_bits_kernel, dim3(g2), dim3(256), 0, ctx().stream, packed, bits, pl->n_symb, pl->nd, pl->bps,
+                     pl->frame_words, k0, k1, stream0, nf);
+  return check_launch("tx_bits_kernel");
+}
+
+int tx_pack_bits_device(const ofdm_rx_plan* pl, const uint8_t* bits, uint32_t* packed, int64_t nf) {
+  if (nf == 0) return OFDM_OK;
+  const int64_t words = (int64_t)pl->frame_words * nf;
+  const int64_t frame_bits = (int64_t)pl->nd * pl->n_symb * pl->bps;
+  hipLaunchKernelGGL(tx_pack_bits_kernel, dim3((unsigned)std::min<int64_t>((words + 255) / 256, (int64_t)ctx().num_cu * 16)),
+                     dim3(256), 0, ctx().stream, bits, packed, frame_bits, pl->frame_words, nf);
+  return check_launch("tx_pack_bits_kernel");
+}
+
 }  // namespace ofdm
 
 using namespace ofdm;
@@ -172,17 +174,7 @@ extern "C" int ofdm_tx_frames_ex(ofdm_rx_plan* pl, const void* h, int h_len, dou
   OFDM_TRY(st.out(sc_ref_bits_out, fb * n_frames, &dscref));
   OFDM_TRY(st.out(sto_out, sizeof(int64_t) * (size_t)n_frames, &dsto_o));
   OFDM_TRY(st.out(cfo_out, sizeof(double) * (size_t)n_frames, &dcfo_o));
-  if (!pl->d_dict) {                                              // constellation table in the plan's precision
-    const size_t n = pl->dict.size();
-    OFDM_HIP(hipMalloc(&pl->d_dict, cs * n));
-    if (pl->f64) {
-      OFDM_HIP(hipMemcpy(pl->d_dict, pl->dict.data(), sizeof(c64) * n, hipMemcpyHostToDevice));
-    } else {
-      std::vector<c32> d32(n);
-      for (size_t i = 0; i < n; ++i) d32[i] = c32{(float)pl->dict[i].x, (float)pl->dict[i].y};
-      OFDM_HIP(hipMemcpy(pl->d_dict, d32.data(), sizeof(c32) * n, hipMemcpyHostToDevice));
-    }
-  }
+  OFDM_TRY(tx_dict_device(pl));
   // chunks of frames through a plan-owned scratch: X [nfft x S], two guarded time signals [(nfft+tg) x S], and with the
   // Scrambler on the chunk's payload and scrambled bits (one byte each), plus the per-frame draws
   const int64_t CH = std::min<int64_t>(n_frames, 1024);

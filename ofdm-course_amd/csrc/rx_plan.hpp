@@ -35,6 +35,8 @@ struct ofdm_rx_plan {
   void* ws_gen = nullptr;  // ofdm_tx_frames: X / time-domain scratch for one chunk of frames
   size_t ws_gen_bytes = 0;
   void* d_dict = nullptr;  // constellation table in the plan's precision (ofdm_tx_frames)
+  void* ws_txf = nullptr;  // ofdm_tx_frames_fused / ofdm_ber_sweep_task5: TX samples, partials, bits (and RX) of a chunk
+  size_t ws_txf_bytes = 0;
   void* d_t4_tx = nullptr; // ofdm_rx_chain_task4: pilot matrix [np x n_symb] and spline operator [n_carrier x np] (built once)
   void* d_t4_w = nullptr;
   void *d_t4_bw = nullptr, *d_t4_bc0 = nullptr;      // fp32: the same operator cut to its band (spline_band_kernel)

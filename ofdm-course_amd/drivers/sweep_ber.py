@@ -8,6 +8,10 @@ multipath -> Noise, Philox streams keyed by the tile, so the table does not depe
 or packed on the host), runs `rx_chain_task5`, and adds
 its error / bit counts.  One SUM all-reduce of the int64 counters ends the sweep -- no samples are exchanged.
 
+--fused (opt-in): the reference's order, Noise -> conv(h) (T5/Task5_part2.m:134,:152), through `RxPlan.ber_sweep`
+(ofdm_ber_sweep_task5: the three-pass generator + the chain + a device reduction, one call for the points a rank holds of a
+batch, the same tile keys); the counters stay in a device tensor and are read once, before the all-reduce.
+
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 16
@@ -23,7 +27,7 @@ import numpy as np
 
 
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
-        rank=0, world=1, device_index=0, backend="nccl"):
+        rank=0, world=1, device_index=0, backend="nccl", fused=False):
     """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}."""
     import torch
     import ofdm_course_amd as ofdm
@@ -42,7 +46,26 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     counters = sweep.Counters(len(snrs))
     t0 = time.perf_counter()
     n_tiles = 0
-    for si, bi in sweep.tiles_for_rank(len(snrs), batches, rank, world):
+    if fused:
+        h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+        err = torch.zeros(len(snrs), dtype=torch.int64, device=dev)
+        by_batch = {}
+        for si, bi in sweep.tiles_for_rank(len(snrs), batches, rank, world):
+            by_batch.setdefault(bi, []).append(si)
+        for bi, sis in by_batch.items():
+            keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
+            groups = [[i] for i in range(len(sis))] if estimator == "mmse" else [list(range(len(sis)))]
+            for g in groups:                                   # an MMSE plan is built for one SNR: one point per call
+                if estimator == "mmse":
+                    plan.set_mmse(hh, float(snrs[sis[g[0]]]))
+                out = plan.ber_sweep(snrs[[sis[i] for i in g]], frames_per_tile, h=h, seeds=[keys[i][0] for i in g],
+                                     frame0=keys[g[0]][1], device=dev)
+                err[[sis[i] for i in g]] += out["errors"]
+            n_tiles += len(sis)
+            for si in sis:
+                counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
+        counters.errors[:, 0] += err.cpu().numpy()            # the one read of the device counters
+    for si, bi in [] if fused else sweep.tiles_for_rank(len(snrs), batches, rank, world):
         cfg.SNR_dB = float(snrs[si])
         key, stream0 = sweep.tile_seed_stream(seed, si, bi, frames_per_tile)
         data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=key, device=dev, frame0=stream0)
@@ -57,7 +80,8 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     return {"config": config, "estimator": estimator, "SNRs": snrs.tolist(), "errors": total.errors[:, 0].tolist(),
             "bits": total.bits[:, 0].tolist(), "BER": (total.errors[:, 0] / np.maximum(total.bits[:, 0], 1)).tolist(),
             "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world, "tiles_this_rank": n_tiles,
-            "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64"}
+            "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
+            **({"order": "noise_first", "fused": True} if fused else {})}
 
 
 def main():
@@ -70,6 +94,7 @@ def main():
     ap.add_argument("--estimator", choices=["omp", "mmse"], default="omp")
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI; gloo for rehearsals")
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank on this GPU")
+    ap.add_argument("--fused", action="store_true", help="reference order (Noise -> conv) through RxPlan.ber_sweep")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
@@ -85,7 +110,7 @@ def main():
         else:
             dist.init_process_group(a.backend)
     res = run(a.config, a.snrs, a.batches, a.frames_per_tile, a.precision, estimator=a.estimator, rank=rank, world=world,
-              device_index=dev_index, backend=a.backend)
+              device_index=dev_index, backend=a.backend, fused=a.fused)
     if rank == 0:
         text = json.dumps(res)
         if a.json:

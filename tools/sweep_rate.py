@@ -1,0 +1,95 @@
+"""BER(SNR) sweep rate: the frame generators against each other and the end-to-end sweep tile, one JSON line.
+
+Per config (fp32, the benchmark tiles): generation ms of tx_frames(noise_first=True) (the staged ofdm_tx_frames_ex) and of
+tx_frames_fused on the same frames, the RX ms of rx_chain_task5 on that tile, and one-point ber_sweep calls of the same
+size (generation + RX + reduction) as sym/s.  The roofline of the fused generator counts its bytes as 3 sample passes (TX
+write, TX read, RX write) + the packed reference bits, against 8 TB/s.
+
+    python tools/sweep_rate.py [M C4 C5]
+"""
+from __future__ import annotations
+
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import ofdm_course_amd as ofdm  # noqa: E402
+from ofdm_course_amd import frames as fr  # noqa: E402
+
+PEAK_TBS = 8.0
+
+
+def timed(fn, reps=5, warm=1):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return float(np.median(ms))
+
+
+def config(name):
+    if name == "M":
+        return fr.config_M(), 20480, False
+    if name == "C4":
+        return fr.FrameConfig("C4", 4096, 1024, 4, "64QAM"), 8192, True
+    return fr.config_C5(), 3072, False
+
+
+def measure(name, reps=5):
+    cfg, F, mmse = config(name)
+    dev = torch.device("cuda:0")
+    plan = fr.make_plan(cfg, ofdm, precision="fp32", device=0)
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    if mmse:
+        hh = np.zeros(cfg.N_carrier, dtype=np.complex64)
+        hh[: len(h)] = h
+        plan.set_mmse(hh, cfg.SNR_dB)
+    snr = cfg.SNR_dB
+    ms_ex = timed(lambda: plan.tx_frames(F, h=h, SNR=snr, seed=3, device=dev, noise_first=True), reps)
+    torch.cuda.empty_cache()
+    ms_fused = timed(lambda: plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev), reps)
+    gen = plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev)
+    ms_rx = timed(lambda: ofdm.rx_chain_task5(plan, gen["rx"], ref_bits_packed=gen["packed"]), reps)
+    ber_rx = float(ofdm.rx_chain_task5(plan, gen["rx"], ref_bits_packed=gen["packed"])["errors"].to(torch.int64).sum().item())
+    del gen
+    torch.cuda.empty_cache()
+    ms_sweep = timed(lambda: plan.ber_sweep([snr], F, h=h, seed=3, device=dev), reps)
+    res = plan.ber_sweep([snr], F, h=h, seed=3, device=dev)
+    err = int(res["errors"][0].item())
+    sample_bytes = 8 * cfg.frame_samples * F
+    counted = 3 * sample_bytes + plan.frame_bytes * F
+    plan.close()
+    torch.cuda.empty_cache()
+    nsym = F * cfg.N_symb
+    return {"config": name, "frames": F, "estimator": "mmse" if mmse else "omp", "snr_db": snr,
+            "gen_ex_ms": ms_ex, "gen_fused_ms": ms_fused, "gen_speedup": ms_ex / ms_fused, "rx_ms": ms_rx,
+            "sweep_ms": ms_sweep, "sweep_sym_per_s": nsym / ms_sweep * 1e3, "rx_sym_per_s": nsym / ms_rx * 1e3,
+            "ber": err / (F * plan.frame_bits), "sweep_errors_equal_composed": err == int(ber_rx),
+            "roofline": {"sample_pass_bytes": sample_bytes, "counted_bytes": counted,
+                         "gen_fused_tbs": counted / (ms_fused * 1e-3) / 1e12,
+                         "gen_fused_frac": counted / (ms_fused * 1e-3) / 1e12 / PEAK_TBS,
+                         "floor_ms": counted / (PEAK_TBS * 1e12) * 1e3}}
+
+
+def main():
+    names = sys.argv[1:] or ["M", "C4", "C5"]
+    ofdm.init(0)
+    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure(n) for n in names]}
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
