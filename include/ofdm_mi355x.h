@@ -259,8 +259,8 @@ int ofdm_tx_frames(ofdm_rx_plan* plan, const void* h, int h_len, double snr_db, 
  * -> Noise(snr_db) -> conv(h) truncated per frame.  The same draws as ofdm_tx_frames_ex(noise_first = 1, sto_mode =
  * cfo_mode = 0, noise_on = 1): payload Philox (seed, frame0 + f), noise Philox counter (i, 0, frame0 + f, 0) with the
  * Box-Muller of ofdm_Noise, the noise power from the frame's own mean |x|^2 (Noise.m:3).  No STO / CFO (the Task-5
- * receiver has no synchroniser; Task-4 sweeps keep ofdm_tx_frames_ex).  h: HOST array of h_len complex taps in the precision
- * of `flags`, at most 64 nonzero taps at delays <= 4096 (NULL = no channel); scr_reg15: HOST uint8[15] or NULL.
+ * receiver has no synchroniser; ofdm_tx_frames_fused_ex adds them for the Task-4 sweeps).  h: HOST array of h_len
+ * complex taps in the precision of `flags`, at most 64 nonzero taps at delays <= 4096 (NULL = no channel); scr_reg15: HOST uint8[15] or NULL.
  * rx_out [frame_samples x n_frames], ref_bits_out (packed payload bits, optional), sc_ref_bits_out (packed scrambled bits,
  * optional, Scrambler on) live where `flags` says.  Results depend on (seed, frame0 + f) only, not on the batching. */
 int ofdm_tx_frames_fused(ofdm_rx_plan* plan, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
@@ -278,6 +278,44 @@ int ofdm_tx_frames_fused(ofdm_rx_plan* plan, const void* h, int h_len, double sn
 int ofdm_ber_sweep_task5(ofdm_rx_plan* plan, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
                          int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
                          int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags);
+/* ofdm_tx_frames_fused with the Task-4 impairments, in the reference order (T4/Main_model_Task_4.m:94-110,:257-267,
+ * T5/Noise.m:3-10, T5/add_STO.m, T5/add_CFO.m): per frame f of length len = (Nfft + T_guard) * N_symb
+ *   w[j] = x[j] + sigma_f n(j)            the noise of Noise.m, Philox counter (j, 0, frame0 + f, 0) of the SOURCE index j
+ *   s[m] = w[m + sto_f] (0 outside 0..len-1)   add_STO.m, either sign
+ *   z[m] = s[m] exp(2 pi i cfo_f m / Nfft)     add_CFO.m on the shifted stream
+ *   rx[n] = sum_t h_t z[n - d_t]               conv truncated
+ * still in three sample passes.  sto_mode / cfo_mode: 0 = off, 1 = sto_value / cfo_value for every frame, 2 = drawn per
+ * frame from Philox counter (0, 0, frame0 + f, 2) -- the draws of ofdm_tx_frames_ex, which this call reproduces with
+ * noise_first = 1 (to rounding).  With both modes 0 the frames are bit-identical to ofdm_tx_frames_fused's.
+ * sto_out / cfo_out (optional): the per-frame draws (int64 / double; 0 for a mode-0 stage), where `flags` says.  The other
+ * arguments and limits are those of ofdm_tx_frames_fused.  Results depend on (seed, frame0 + f) only. */
+int ofdm_tx_frames_fused_ex(ofdm_rx_plan* plan, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
+                            int64_t n_frames, const uint8_t* scr_reg15, int sto_mode, int64_t sto_value, int cfo_mode,
+                            double cfo_value, void* rx_out, uint8_t* ref_bits_out, uint8_t* sc_ref_bits_out,
+                            int64_t* sto_out, double* cfo_out, int flags);
+/* One tile of a BER(SNR) sweep of the Task-4 receiver: for each point p the frames frame0 .. frame0 + frames_per_point - 1
+ * are generated as ofdm_tx_frames_fused_ex(h, snr_db[p], seeds[p], sto / cfo modes and values, ...) and decoded by
+ * ofdm_rx_chain_task4(time_desync, freq_desync, mp_desync) on this plan, each frame once.
+ *   flags (0,0,0), no STO / CFO / h: the BER(SNR) loop of T3/Main_model_Task_3.m:237-268 (Noise -> demodulator -> demap ->
+ *   DeScrambler); STO / CFO with the desync flags on: the synchronisation study of T4/Main_model_Task_4.m:99-134.
+ * snr_db[n_points] / seeds[n_points]: HOST arrays.  Outputs, where `flags` says:
+ *   errors_out[n_points] (uint64): bit errors per point;
+ *   status_counts_out[n_points][4] (uint64, optional): frames with rx_chain_task4 status 0, 1, -1, -2;
+ *   cfo_abs_err_out[n_points] (double, optional): sum over the point's frames of |FreqOffset + IFO - Freq_Shift|
+ *   (T4/Main_model_Task_4.m:113-134), 0 where freq_desync is off; summed in a fixed order, bitwise independent of the chunk;
+ *   frame_errors_out[n_points][frames_per_point] (uint32, optional).
+ * Scrambler rule of ofdm_ber_sweep_task5: with scr_reg15 the plan must carry a DeScrambler with the same register and the
+ * errors count against the payload bits; without it the plan must not descramble.
+ * max_frames_per_chunk: 0..65535 (the limit of ofdm_rx_chain_task4); 0 = the library's choice, which budgets the generator
+ * workspace and the Task-4 arena together (about 4 GB).  Results do not depend on it.
+ * With OFDM_DEVICE nothing is reduced on the host and nothing synchronises it, apart from first-call set-up (the plan's
+ * constellation table and workspace growth) and what ofdm_rx_chain_task4 does anyway: its arena growth and the once-per-plan
+ * copy of the pilot column. */
+int ofdm_ber_sweep_task4(ofdm_rx_plan* plan, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                         double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                         const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                         const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                         uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out, int flags);
 /* Per-frame DeScrambler inside ofdm_rx_chain_task5 / ofdm_rx_chain_task4 (T5/DeScrambler.m:1-16 with
  * the register reset for every frame, T5/Main_model_Task_5.m:257-274, T4/Main_model_Task_4.m:354-364): the demapped bits
  * of a frame go through d[i] = s[i] ^ s[i-13] ^ s[i-14], s[-m] = reg15[m-1], before they are written to bits_out and

@@ -83,6 +83,9 @@ SIGNATURES = {
     "ofdm_task5_mse_tile": [_vp, _vp, _vp, _vp, _i, _vp, _i64, C.c_uint64, C.c_uint32, _vp, _i],
     "ofdm_tx_frames_fused": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task5": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i],
+    "ofdm_tx_frames_fused_ex": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_ber_sweep_task4": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
+                             _vp, _i],
 }
 _RESTYPES = {"ofdm_last_error_string": C.c_char_p, "ofdm_rx_plan_frame_bytes": C.c_int64}
 

@@ -630,6 +630,17 @@ def calculateCCDF(PAPR_values):
 # fused Task-5 RX chain
 # ------------------------------------------------------------------------------------------------
 
+def _imp_mode(v, what):
+    """Time_Delay / Freq_Shift argument -> (mode, value): None = off (0), a number = fixed (1), "random" = drawn (2)."""
+    if v is None:
+        return 0, 0
+    if isinstance(v, str):
+        if v != "random":
+            raise OfdmError(f"{what}: Time_Delay / Freq_Shift must be None, a number or 'random'")
+        return 2, 0
+    return 1, v
+
+
 class RxPlan:
     """Device-resident description of one Task-5 RX configuration (ofdm_rx_plan_create)."""
 
@@ -725,16 +736,8 @@ class RxPlan:
             if reg.size != 15:
                 raise OfdmError("tx_frames: Register must have 15 entries")
 
-        def mode(v):
-            if v is None:
-                return 0, 0
-            if isinstance(v, str):
-                if v != "random":
-                    raise OfdmError("tx_frames: Time_Delay / Freq_Shift must be None, a number or 'random'")
-                return 2, 0
-            return 1, v
-        sm, sv = mode(Time_Delay)
-        cm, cv = mode(Freq_Shift)
+        sm, sv = _imp_mode(Time_Delay, "tx_frames")
+        cm, cv = _imp_mode(Freq_Shift, "tx_frames")
         L.check(self.lib.ofdm_tx_frames_ex(self.handle, hh.ctypes.data_as(C.c_void_p) if hh is not None else None,
                                            0 if hh is None else hh.size, float(SNR if SNR is not None else 0.0),
                                            int(SNR is not None), int(seed), int(frame0), n_frames,
@@ -764,14 +767,20 @@ class RxPlan:
         pr = reg.ctypes.data_as(C.c_void_p) if reg is not None else None
         return (hh, reg), ph, 0 if hh is None else hh.size, pr
 
-    def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None):
+    def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None, Time_Delay=None,
+                        Freq_Shift=None, want_draws=False):
         """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
         frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(SNR) -> conv(h) truncated
         (T5/Main_model_Task_5.m:50-127, T5/Task5_part2.m:134,:152).  The draws of tx_frames(noise_first=True): the same
-        frames up to rounding.  No STO / CFO.  h=None: no channel.
+        frames up to rounding.  h=None: no channel.
+        Time_Delay / Freq_Shift (as in tx_frames: None = off, a number = that value for every frame, "random" = the
+        per-frame draw of T4/Main_model_Task_4.m:101-110) add add_STO -> add_CFO between Noise and conv
+        (ofdm_tx_frames_fused_ex, T4:94-110); want_draws returns the per-frame values.
         Returns dict(rx=[frame_samples, n_frames], packed=[n_frames, frame_bytes] (the payload bits)
-        (+ sc_packed = the scrambled bits when Register is given)); torch CUDA tensors when `device` is given."""
+        (+ sc_packed = the scrambled bits when Register is given) (+ Time_Delay [n_frames] int64, Freq_Shift [n_frames]
+        float64 with want_draws)); torch CUDA tensors when `device` is given."""
         n_frames = int(n_frames)
+        ex = Time_Delay is not None or Freq_Shift is not None or want_draws
         flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
         scr = Register is not None
         if device is not None:
@@ -780,6 +789,8 @@ class RxPlan:
                              device=dev)
             packed = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev)
             scp = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev) if scr else None
+            sto = torch.empty((n_frames,), dtype=torch.int64, device=dev) if want_draws else None
+            cfo = torch.empty((n_frames,), dtype=torch.float64, device=dev) if want_draws else None
             L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
             flags |= L.OFDM_DEVICE
@@ -788,13 +799,24 @@ class RxPlan:
             rx = np.empty((n_frames, self.frame_samples), dtype=np.complex128 if self.f64 else np.complex64)
             packed = np.empty((n_frames, self.frame_bytes), dtype=np.uint8)
             scp = np.empty((n_frames, self.frame_bytes), dtype=np.uint8) if scr else None
+            sto = np.empty((n_frames,), dtype=np.int64) if want_draws else None
+            cfo = np.empty((n_frames,), dtype=np.float64) if want_draws else None
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
         keep, ph, nh, pr = self._fused_args(h, Register, "tx_frames_fused")
-        L.check(self.lib.ofdm_tx_frames_fused(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr, ptr(rx),
-                                              ptr(packed), ptr(scp), flags), "tx_frames_fused")
+        if ex:
+            sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
+            cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
+            L.check(self.lib.ofdm_tx_frames_fused_ex(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
+                                                     sm, int(sv), cm, float(cv), ptr(rx), ptr(packed), ptr(scp), ptr(sto),
+                                                     ptr(cfo), flags), "tx_frames_fused_ex")
+        else:
+            L.check(self.lib.ofdm_tx_frames_fused(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
+                                                  ptr(rx), ptr(packed), ptr(scp), flags), "tx_frames_fused")
         out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
         if scr:
             out["sc_packed"] = scp
+        if want_draws:
+            out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
@@ -832,6 +854,60 @@ class RxPlan:
                                               sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
                                               int(max_frames_per_chunk), ptr(err), ptr(fe), flags), "ber_sweep_task5")
         out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
+        if want_frame_errors:
+            out["frame_errors"] = fe
+        return out
+
+    def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
+                        freq_desync=None, mp_desync=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
+                        want_frame_errors=False, max_frames_per_chunk=0):
+        """One device-resident tile of a BER(SNR) sweep of the Task-4 receiver (ofdm_ber_sweep_task4): for every SNR of
+        `SNRs` the frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p], Time_Delay,
+        Freq_Shift) decoded by rx_chain_task4(time_desync, freq_desync, mp_desync) on this plan.  A desync flag left at None
+        follows its impairment, as the single flag of T4/Main_model_Task_4.m:81-110 switches both: time_desync = Time_Delay
+        given, freq_desync = Freq_Shift given, mp_desync = h given.  All flags off, no STO / CFO / h: the BER(SNR) loop of
+        T3/Main_model_Task_3.m:237-268.  Register: as in ber_sweep (the plan must descramble with the same register).
+        Returns dict(errors=[n] bit errors, bits=bits counted per point, status_counts=[n, 4] frames with rx_chain_task4
+        status 0, 1, -1, -2, cfo_abs_err=[n] sum of |FreqOffset + IFO - Freq_Shift| over the point's frames (0 with
+        freq_desync off) (+ frame_errors=[n, frames_per_point] with want_frame_errors)); torch tensors on `device` (no host
+        synchronisation) when it is given, numpy arrays otherwise."""
+        snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
+        n = snr.size
+        fpp = int(frames_per_point)
+        sd = np.full(n, int(seed), dtype=np.uint64) if seeds is None else \
+            np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
+        if sd.size != n:
+            raise OfdmError("ber_sweep_task4: seeds must have one entry per SNR point")
+        sm, sv = _imp_mode(Time_Delay, "ber_sweep_task4")
+        cm, cv = _imp_mode(Freq_Shift, "ber_sweep_task4")
+        td = Time_Delay is not None if time_desync is None else bool(time_desync)
+        fd = Freq_Shift is not None if freq_desync is None else bool(freq_desync)
+        md = h is not None if mp_desync is None else bool(mp_desync)
+        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
+        if device is not None:
+            dev = torch.device(device)
+            err = torch.empty((n,), dtype=torch.int64, device=dev)
+            stc = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            cae = torch.empty((n,), dtype=torch.float64, device=dev)
+            fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
+            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+            flags |= L.OFDM_DEVICE
+        else:
+            L.check(self.lib.ofdm_set_stream(None), "set_stream")
+            err = np.empty((n,), dtype=np.uint64)
+            stc = np.empty((n, 4), dtype=np.uint64)
+            cae = np.empty((n,), dtype=np.float64)
+            fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
+        L.check(self.lib.ofdm_ber_sweep_task4(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
+                                              snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                              int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
+                                              ptr(fe), flags), "ber_sweep_task4")
+        host = device is None
+        out = dict(errors=err.astype(np.int64) if host else err, bits=fpp * self.frame_bits,
+                   status_counts=stc.astype(np.int64) if host else stc, cfo_abs_err=cae)
         if want_frame_errors:
             out["frame_errors"] = fe
         return out

@@ -15,6 +15,16 @@
 //                                   the sparse FIR from LDS with the taps in kernel arguments, rx written once (nontemporal).
 //   ber_point_reduce_kernel         per-frame uint32 errors -> per-point uint64 (integers: exact in any order).
 // TX samples: one write, one read (+ halo), RX: one write -- 3 sample passes against ~9 for ofdm_tx_frames_ex's stages.
+//
+// ofdm_tx_frames_fused_ex / ofdm_ber_sweep_task4 add the Task-4 impairments (T4/Main_model_Task_4.m:99-110, add_STO.m,
+// add_CFO.m) in the reference order Noise -> add_STO -> add_CFO -> conv, still in three sample passes:
+//   tx_channel_imp_kernel<T>        the sibling of tx_channel_fused_kernel (which stays as it is): its LDS load stage builds
+//                                   z[m] = w[m + sto_f] e^{2 pi i cfo_f m / Nfft} for the segment and its halo, the noise of w
+//                                   drawn at the SOURCE index m + sto_f (Noise comes before the shift).  The shift is uniform
+//                                   per frame: no extra halo, the loads stay coalesced.
+//   t4_point_reduce_kernel          per-frame errors / status / |FreqOffset + IFO - Freq_Shift| of a whole point -> its sums,
+//                                   in a fixed order (the double sum does not depend on the chunking).
+// The per-frame draws are tx_draw_kernel's (ofdm_txgen.hip), the draws of ofdm_tx_frames_ex.
 #include <algorithm>
 #include <type_traits>
 
@@ -27,6 +37,8 @@ int tx_dict_device(ofdm_rx_plan* pl);                                           
 int tx_bits_device(const ofdm_rx_plan* pl, uint32_t* packed, uint8_t* bits, uint32_t k0, uint32_t k1, uint32_t stream0,
                    int64_t nf);
 int tx_pack_bits_device(const ofdm_rx_plan* pl, const uint8_t* bits, uint32_t* packed, int64_t nf);
+int tx_draw_device(const ofdm_rx_plan* pl, int64_t* sto, double* cfo, int sto_mode, int64_t sto_value, int cfo_mode,
+                   double cfo_value, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf);
 
 constexpr int TXF_MAX_TAPS = 64;
 constexpr int TXF_MAX_DELAY = 4096;
@@ -174,6 +186,54 @@ __global__ __launch_bounds__(256) void tx_channel_fused_kernel(const cx<T>* __re
   }
 }
 
+// Noise -> add_STO -> add_CFO -> conv(h) truncated per frame (T4/Main_model_Task_4.m:99-110,:257-267): the channel pass of
+// tx_channel_fused_kernel with the frame's shift sto[f] and rotation cfo[f] folded into the LDS load stage.
+//   w[j] = x[j] + sigma n(j)   s[m] = w[m + sto] (0 outside the frame, add_STO.m, either sign)
+//   z[m] = s[m] exp(2 pi i cfo m / Nfft)   (add_CFO.m on the shifted stream; the arithmetic of sto_cfo_frames_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                             const double* __restrict__ partial, int n_symb, int64_t len,
+                                                             double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                             const int64_t* __restrict__ sto, const double* __restrict__ cfo,
+                                                             double inv_nfft, TxfTaps<T> taps) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char txf_smem[];
+  cx<T>* buf = (cx<T>*)txf_smem;
+  const int64_t f = blockIdx.y;
+  const int64_t n0 = (int64_t)blockIdx.x * TXF_SEG;
+  const int H = taps.halo;
+  const cx<T>* x = tx + f * len;
+  double sum = 0;                                                // Noise.m:3 -- the frame's symbols in order
+  for (int i = 0; i < n_symb; ++i) sum += partial[f * n_symb + i];
+  const double sg = sqrt(sum / (double)len / snr_lin / 2.0);     // :5, per-component sigma
+  const uint32_t stream = stream0 + (uint32_t)f;
+  const int64_t sh = sto[f];
+  const double fo = cfo[f];
+  for (int i = threadIdx.x; i < TXF_SEG + H; i += 256) {
+    const int64_t m = n0 - H + i;                                // index of the shifted stream; before the frame: silence
+    const int64_t src = m + sh;
+    cx<T> v = mk<T>(0, 0);
+    if (m >= 0 && m < len && src >= 0 && src < len) {
+      v = txf_noisy<T>(x[src], src, sg, stream, k0, k1);         // the noise of the source sample
+      if (fo != 0.0) {                                           // cfo 0: a rotation by exactly 1, skipped (uniform per frame)
+        const double t = fo * (double)m * inv_nfft;
+        const double fr = t - floor(t);
+        double sn, cs;
+        sincospi(2.0 * fr, &sn, &cs);
+        v = mk<T>((T)((double)v.x * cs - (double)v.y * sn), (T)((double)v.x * sn + (double)v.y * cs));
+      }
+    }
+    buf[i] = v;
+  }
+  __syncthreads();
+  cx<T>* y = rx + f * len;
+  for (int o = threadIdx.x; o < TXF_SEG; o += 256) {
+    if (n0 + o >= len) break;
+    cx<T> acc = mk<T>(0, 0);
+    for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
+    nt_store(y + n0 + o, acc);
+  }
+}
+
 __global__ __launch_bounds__(256) void ber_point_reduce_kernel(const uint32_t* __restrict__ frame_errors,
                                                                int64_t frames_per_point,
                                                                unsigned long long* __restrict__ errors) {
@@ -185,6 +245,48 @@ __global__ __launch_bounds__(256) void ber_point_reduce_kernel(const uint32_t* _
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) errors[p] = part[0] + part[1] + part[2] + part[3];
+}
+
+// per point p of a Task-4 sweep: bit errors (uint64), status counts {0, 1, -1, -2} and, with freq_desync, the sum of
+// |FreqOffset + IFO - Freq_Shift| (T4/Main_model_Task_4.m:113-134) over the point's frames -- each thread a fixed stride,
+// then a fixed butterfly: the same order for any chunking of the frames
+__global__ __launch_bounds__(256) void t4_point_reduce_kernel(const uint32_t* __restrict__ frame_errors,
+                                                              const int32_t* __restrict__ status, const double* __restrict__ fo,
+                                                              const int32_t* __restrict__ ifo, const double* __restrict__ shift,
+                                                              int64_t frames_per_point, int freq_desync,
+                                                              unsigned long long* __restrict__ errors,
+                                                              unsigned long long* __restrict__ status_counts,
+                                                              double* __restrict__ cfo_abs_err) {
+  const int64_t p = blockIdx.x;
+  unsigned long long e = 0, c[4] = {0, 0, 0, 0};
+  double a = 0;
+  for (int64_t i = threadIdx.x; i < frames_per_point; i += 256) {
+    const int64_t k = p * frames_per_point + i;
+    e += frame_errors[k];
+    const int st = status[k];
+    c[st == 0 ? 0 : st == 1 ? 1 : st == -1 ? 2 : 3] += 1;
+    if (freq_desync) a += fabs(fo[k] + (double)ifo[k] - shift[k]);
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    e += __shfl_xor(e, off, 64);
+    for (int q = 0; q < 4; ++q) c[q] += __shfl_xor(c[q], off, 64);
+    a += __shfl_xor(a, off, 64);
+  }
+  __shared__ unsigned long long pe[4], pc[4][4];
+  __shared__ double pa[4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    pe[w] = e;
+    for (int q = 0; q < 4; ++q) pc[w][q] = c[q];
+    pa[w] = a;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    errors[p] = pe[0] + pe[1] + pe[2] + pe[3];
+    if (status_counts)
+      for (int q = 0; q < 4; ++q) status_counts[p * 4 + q] = pc[0][q] + pc[1][q] + pc[2][q] + pc[3][q];
+    if (cfo_abs_err) cfo_abs_err[p] = (pa[0] + pa[1]) + (pa[2] + pa[3]);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -254,6 +356,30 @@ static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const vo
   return check_launch("tx_channel_fused_kernel");
 }
 
+template <typename T>
+static int launch_channel_imp(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
+                              double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const int64_t* sto,
+                              const double* cfo, int64_t nf) {
+  const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
+  OFDM_HIP(hipFuncSetAttribute((const void*)tx_channel_imp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  hipLaunchKernelGGL(tx_channel_imp_kernel<T>, dim3(cdiv_u(len, TXF_SEG), (unsigned)nf), dim3(256), dyn, ctx().stream,
+                     (const cx<T>*)tx, (cx<T>*)rx, partial, pl->n_symb, len, snr_lin, k0, k1, stream0, sto, cfo,
+                     1.0 / (double)pl->nfft, txf_taps<T>(ch));
+  return check_launch("tx_channel_imp_kernel");
+}
+
+// the Task-4 impairments of a generator call (T4/Main_model_Task_4.m:99-110): modes 0 off, 1 fixed, 2 drawn; the chunk's
+// per-frame draws are written to sto / cfo (nf entries each)
+struct TxfImp {
+  int sto_mode = 0;
+  int64_t sto_value = 0;
+  int cfo_mode = 0;
+  double cfo_value = 0;
+  int64_t* sto = nullptr;
+  double* cfo = nullptr;
+};
+
 // chunk buffers inside the plan-owned workspace
 struct TxfBuffers {
   void* tx = nullptr;
@@ -262,26 +388,29 @@ struct TxfBuffers {
   uint8_t* b1 = nullptr;                             // Scrambler on: scrambled bits
   void* rx = nullptr;                                // sweep: the chunk's RX frames
   uint32_t* ref = nullptr;                           // sweep: their packed reference bits
+  int64_t* sto = nullptr;                            // impairments on: the chunk's draws
+  double* cfo = nullptr;
 };
 
 static size_t a256(size_t b) { return (b + 255) & ~size_t(255); }
 
-static size_t txf_frame_bytes(const ofdm_rx_plan* pl, bool scr, bool sweep) {
+static size_t txf_frame_bytes(const ofdm_rx_plan* pl, bool scr, bool sweep, bool imp = false) {
   const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
   const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
   return cs * fs * (sweep ? 2 : 1) + 8 * (size_t)pl->n_symb + (scr ? 2 * frame_bits : 0) +
-         (sweep ? (size_t)pl->frame_words * 4 : 0);
+         (sweep ? (size_t)pl->frame_words * 4 : 0) + (imp ? 16 : 0);
 }
 
-static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, TxfBuffers& b) {
+static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, TxfBuffers& b, bool imp = false) {
   const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
   const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
   const size_t t_bytes = a256(cs * fs * ch), p_bytes = a256(8 * (size_t)pl->n_symb * ch);
   const size_t b_bytes = scr ? a256(frame_bits * ch) : 0;
   const size_t r_bytes = sweep ? t_bytes : 0, f_bytes = sweep ? a256((size_t)pl->frame_words * 4 * ch) : 0;
-  const size_t need = t_bytes + p_bytes + 2 * b_bytes + r_bytes + f_bytes;
+  const size_t d_bytes = imp ? a256(8 * (size_t)ch) : 0;
+  const size_t need = t_bytes + p_bytes + 2 * b_bytes + r_bytes + f_bytes + 2 * d_bytes;
   if (pl->ws_txf_bytes < need) {
     OFDM_HIP(hipStreamSynchronize(ctx().stream));
     if (pl->ws_txf) { (void)hipFree(pl->ws_txf); pl->ws_txf = nullptr; pl->ws_txf_bytes = 0; }
@@ -293,18 +422,21 @@ static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, Txf
   b.partial = (double*)(base + t_bytes);
   unsigned char* q = base + t_bytes + p_bytes;
   if (scr) { b.b0 = q; b.b1 = q + b_bytes; q += 2 * b_bytes; }
-  if (sweep) { b.rx = q; b.ref = (uint32_t*)(q + r_bytes); }
+  if (sweep) { b.rx = q; b.ref = (uint32_t*)(q + r_bytes); q += r_bytes + f_bytes; }
+  if (imp) { b.sto = (int64_t*)q; b.cfo = (double*)(q + d_bytes); }
   return OFDM_OK;
 }
 
-static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n_frames, int64_t user_cap) {
-  int64_t ch = user_cap > 0 ? user_cap : std::max<int64_t>(1, (int64_t)(TXF_WS_BUDGET / txf_frame_bytes(pl, scr, sweep)));
+static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n_frames, int64_t user_cap, bool imp = false) {
+  int64_t ch = user_cap > 0 ? user_cap : std::max<int64_t>(1, (int64_t)(TXF_WS_BUDGET / txf_frame_bytes(pl, scr, sweep, imp)));
   return std::max<int64_t>(1, std::min<int64_t>({ch, n_frames, 65535}));
 }
 
 // one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
+// imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
 static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
-                        int64_t nf, const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref) {
+                        int64_t nf, const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
+                        const TxfImp* imp = nullptr) {
   const int64_t frame_bits = (int64_t)pl->nd * pl->n_symb * pl->bps;
   OFDM_TRY(tx_bits_device(pl, ref, scr_reg15 ? b.b0 : nullptr, k0, k1, stream0, nf));
   if (scr_reg15) {                                              // Scrambler.m per frame, register reset (T5:58-69)
@@ -319,8 +451,47 @@ static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, 
   else OFDM_TRY((launch_symbols<float, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf)));
   OFDM_FFT_DISPATCH(pl->nfft, CALL)
 #undef CALL
+  if (imp) {
+    OFDM_TRY(tx_draw_device(pl, imp->sto, imp->cfo, imp->sto_mode, imp->sto_value, imp->cfo_mode, imp->cfo_value, k0, k1,
+                            stream0, nf));
+    if (pl->f64)
+      OFDM_TRY(launch_channel_imp<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, nf));
+    else
+      OFDM_TRY(launch_channel_imp<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, nf));
+    return OFDM_OK;
+  }
   if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
   else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
+  return OFDM_OK;
+}
+
+// bytes per frame of the ofdm_rx_chain_task4 arena (pl->ws_t4, task4_run in ofdm_sync.hip): the aligned stream, the
+// demodulated symbols, the compact pilot rows, the remove_IFO segment + spectrum, the estimates (+ per-frame scalars)
+static size_t t4_frame_bytes(const ofdm_rx_plan* pl) {
+  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
+  const size_t len = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  return cs * (len + (size_t)pl->nfft * pl->n_symb + (size_t)pl->np * pl->n_symb + 2 * (size_t)pl->nfft + pl->np +
+               pl->n_carrier) + 128 + (size_t)pl->frame_words * 4;
+}
+
+static int txf_check_modes(int sto_mode, int cfo_mode, const char* what) {
+  OFDM_ARG(sto_mode >= 0 && sto_mode <= 2 && cfo_mode >= 0 && cfo_mode <= 2, "%s: sto_mode / cfo_mode must be 0, 1 or 2", what);
+  return OFDM_OK;
+}
+
+// the sweeps' Scrambler rule: with the Scrambler on the plan descrambles with the same register, else not at all
+static int txf_check_descrambler(const ofdm_rx_plan* pl, const uint8_t* scr_reg15, const char* what) {
+  if (scr_reg15) {                                              // errors against the payload: the plan must descramble
+    uint32_t d = DESCR_ON;
+    for (int m = 1; m <= 14; ++m) {
+      OFDM_ARG(scr_reg15[m - 1] <= 1, "%s: register entries must be 0 or 1", what);
+      d |= (uint32_t)scr_reg15[m - 1] << (m - 1);
+    }
+    OFDM_ARG(pl->descr == d, "%s: with the Scrambler on the plan needs a DeScrambler with the same register "
+                             "(ofdm_rx_plan_set_descrambler)", what);
+  } else {
+    OFDM_ARG(!(pl->descr & DESCR_ON), "%s: the plan descrambles but the frames are not scrambled", what);
+  }
   return OFDM_OK;
 }
 
@@ -385,17 +556,7 @@ extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, 
   OFDM_ARG(n_points < ((int64_t)1 << 31), "ber_sweep_task5: too many points");
   OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task5"));
   OFDM_ARG(!pl->d_wt || n_points <= 1, "ber_sweep_task5: an MMSE-mode plan is built for one SNR (n_points must be 1)");
-  if (scr_reg15) {                                              // errors against the payload: the plan must descramble
-    uint32_t d = DESCR_ON;
-    for (int m = 1; m <= 14; ++m) {
-      OFDM_ARG(scr_reg15[m - 1] <= 1, "ber_sweep_task5: register entries must be 0 or 1");
-      d |= (uint32_t)scr_reg15[m - 1] << (m - 1);
-    }
-    OFDM_ARG(pl->descr == d, "ber_sweep_task5: with the Scrambler on the plan needs a DeScrambler with the same register "
-                             "(ofdm_rx_plan_set_descrambler)");
-  } else {
-    OFDM_ARG(!(pl->descr & DESCR_ON), "ber_sweep_task5: the plan descrambles but the frames are not scrambled");
-  }
+  OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task5"));
   TxfChannel ch;
   OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
   if (n_points == 0) return OFDM_OK;
@@ -427,5 +588,122 @@ extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, 
   hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)dfe,
                      frames_per_point, (unsigned long long*)derr);
   OFDM_TRY(check_launch("ber_point_reduce_kernel"));
+  return st.finish();
+}
+
+extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed,
+                                       int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, int sto_mode,
+                                       int64_t sto_value, int cfo_mode, double cfo_value, void* rx_out, uint8_t* ref_bits_out,
+                                       uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused_ex: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused_ex"));
+  OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "tx_frames_fused_ex"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused_ex: sc_ref_bits_out needs the Scrambler register");
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  if (n_frames == 0) return OFDM_OK;
+  OFDM_TRY(tx_dict_device(pl));
+  const size_t cs = csize(flags);
+  const int64_t frame_samples = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t fb = (size_t)pl->frame_words * 4;
+  Stage st(flags);
+  void *drx, *dref, *dscref, *dsto, *dcfo;
+  OFDM_TRY(st.out(rx_out, cs * (size_t)frame_samples * n_frames, &drx));
+  OFDM_TRY(st.out(ref_bits_out, fb * n_frames, &dref));
+  OFDM_TRY(st.out(sc_ref_bits_out, fb * n_frames, &dscref));
+  OFDM_TRY(st.out(sto_out, sizeof(int64_t) * (size_t)n_frames, &dsto));
+  OFDM_TRY(st.out(cfo_out, sizeof(double) * (size_t)n_frames, &dcfo));
+  const bool scr = scr_reg15 != nullptr;
+  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0, true);
+  TxfBuffers b;
+  OFDM_TRY(txf_workspace(pl, CH, scr, false, b, true));
+  const double snr_lin = std::pow(10.0, snr_db / 10.0);
+  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  TxfImp imp;
+  imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
+  for (int64_t c0 = 0; c0 < n_frames; c0 += CH) {
+    const int64_t nf = std::min<int64_t>(CH, n_frames - c0);
+    imp.sto = dsto ? (int64_t*)dsto + c0 : b.sto;              // the draws go where the caller wants them, else the workspace
+    imp.cfo = dcfo ? (double*)dcfo + c0 : b.cfo;
+    OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b,
+                          (unsigned char*)drx + cs * (size_t)frame_samples * c0,
+                          dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
+                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, &imp));
+  }
+  return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                                    double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                                    const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                                    const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                                    uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                                    int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4: bad arguments");
+  OFDM_ARG(max_frames_per_chunk >= 0 && max_frames_per_chunk <= 65535,
+           "ber_sweep_task4: max_frames_per_chunk must be 0..65535 (the limit of rx_chain_task4)");
+  OFDM_ARG(n_points == 0 || (snr_db && seeds), "ber_sweep_task4: snr_db / seeds missing");
+  OFDM_ARG(n_points < ((int64_t)1 << 31), "ber_sweep_task4: too many points");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task4"));
+  OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "ber_sweep_task4"));
+  OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task4"));
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  if (n_points == 0) return OFDM_OK;
+  Stage st(flags);
+  const int64_t NF = n_points * frames_per_point;
+  void *derr, *dsc, *dabs, *dfe;
+  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
+  OFDM_TRY(st.out(status_counts_out, sizeof(uint64_t) * 4 * (size_t)n_points, &dsc));
+  OFDM_TRY(st.out(cfo_abs_err_out, sizeof(double) * (size_t)n_points, &dabs));
+  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)NF, &dfe));
+  hipStream_t s = ctx().stream;
+  if (frames_per_point == 0) {
+    OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, s));
+    if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, s));
+    if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, s));
+    return st.finish();
+  }
+  // the per-frame values of every point, reduced once after the last chunk
+  if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)NF, &dfe));
+  void *dtg, *dfo, *difo, *dstat, *dsto, *dcfo;
+  OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dtg));
+  OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dfo));
+  OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)NF, &difo));
+  OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)NF, &dstat));
+  OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dsto));
+  OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dcfo));
+  OFDM_TRY(tx_dict_device(pl));
+  const bool scr = scr_reg15 != nullptr;
+  // default chunk: the generator workspace and the Task-4 arena (shared with ofdm_task5_part2_tile) budgeted together
+  int64_t CH = max_frames_per_chunk;
+  if (CH == 0)
+    CH = std::max<int64_t>(1, (int64_t)(2 * TXF_WS_BUDGET / (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl))));
+  CH = std::max<int64_t>(1, std::min<int64_t>({CH, frames_per_point, 65535}));
+  TxfBuffers b;
+  OFDM_TRY(txf_workspace(pl, CH, scr, true, b, true));
+  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
+  TxfImp imp;
+  imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
+  for (int64_t p = 0; p < n_points; ++p) {
+    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
+    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
+    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
+      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
+      const int64_t o = p * frames_per_point + c0;
+      imp.sto = (int64_t*)dsto + o;
+      imp.cfo = (double*)dcfo + o;
+      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr, &imp));
+      OFDM_TRY(ofdm_rx_chain_task4(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr, (const uint8_t*)b.ref,
+                                   (uint32_t*)dfe + o, (int64_t*)dtg + o, (double*)dfo + o, (int32_t*)difo + o,
+                                   (int32_t*)dstat + o, nullptr, rxflags));
+    }
+  }
+  hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const uint32_t*)dfe,
+                     (const int32_t*)dstat, (const double*)dfo, (const int32_t*)difo, (const double*)dcfo, frames_per_point,
+                     freq_desync ? 1 : 0, (unsigned long long*)derr, (unsigned long long*)dsc, (double*)dabs);
+  OFDM_TRY(check_launch("t4_point_reduce_kernel"));
   return st.finish();
 }

@@ -135,6 +135,16 @@ int tx_bits_device(const ofdm_rx_plan* pl, uint32_t* packed, uint8_t* bits, uint
   return check_launch("tx_bits_kernel");
 }
 
+// launcher of tx_draw_kernel for the fused generator: both draws are written for every frame (mode 0 = 0)
+int tx_draw_device(const ofdm_rx_plan* pl, int64_t* sto, double* cfo, int sto_mode, int64_t sto_value, int cfo_mode,
+                   double cfo_value, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf) {
+  if (nf == 0) return OFDM_OK;
+  hipLaunchKernelGGL(tx_draw_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx().stream, sto, cfo, sto_mode,
+                     sto_mode ? sto_value : 0, cfo_mode, cfo_mode ? cfo_value : 0.0, (uint32_t)(pl->nfft + pl->t_guard + 1), k0,
+                     k1, stream0, nf);
+  return check_launch("tx_draw_kernel");
+}
+
 int tx_pack_bits_device(const ofdm_rx_plan* pl, const uint8_t* bits, uint32_t* packed, int64_t nf) {
   if (nf == 0) return OFDM_OK;
   const int64_t words = (int64_t)pl->frame_words * nf;

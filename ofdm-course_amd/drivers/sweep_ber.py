@@ -12,7 +12,14 @@ its error / bit counts.  One SUM all-reduce of the int64 counters ends the sweep
 (ofdm_ber_sweep_task5: the three-pass generator + the chain + a device reduction, one call for the points a rank holds of a
 batch, the same tile keys); the counters stay in a device tensor and are read once, before the all-reduce.
 
+--config C3: the Task-4 receiver (coarse sync, IFO, fine sync, spline equaliser; T4/Main_model_Task_4.m:99-134,:278-347) on
+frames with a random STO / CFO per frame, through `RxPlan.ber_sweep_task4` (ofdm_ber_sweep_task4), with the same tile keys
+and dealing as --fused.  Per point the JSON adds `status_counts` (frames with receiver status 0, 1, -1, -2) and
+`cfo_abs_err` (the sum of |FreqOffset + IFO - Freq_Shift| over the point's frames).  The integer counters travel in the int64
+all-reduce; the CFO sums in a second, float64 one.
+
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
+    python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
         -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 16
 """
@@ -36,13 +43,15 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
 
     ofdm.init(device_index)
     dev = torch.device("cuda", device_index)
-    cfg = {"C5": fr.config_C5, "M": fr.config_M}[config]()
+    cfg = {"C5": fr.config_C5, "M": fr.config_M, "C3": fr.config_C3}[config]()
     snrs = np.arange(0.0, 30.0, 1.5) if snrs is None else np.asarray(snrs, dtype=float)      # 20 points
     plan = fr.make_plan(cfg, ofdm, precision=precision, device=device_index)
     if estimator == "mmse":
         h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
         hh = np.zeros(cfg.N_carrier, dtype=np.complex128)
         hh[: len(h)] = h
+    if config == "C3":
+        return _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend)
     counters = sweep.Counters(len(snrs))
     t0 = time.perf_counter()
     n_tiles = 0
@@ -84,9 +93,53 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
             **({"order": "noise_first", "fused": True} if fused else {})}
 
 
+def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend):
+    """--config C3: every tile of a batch in one ber_sweep_task4 call, random STO / CFO, all three desync stages on."""
+    import torch
+    import torch.distributed as dist
+    import ofdm_course_amd as ofdm
+    from ofdm_course_amd import sweep
+
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    # columns: bit errors, then frames with status 0, 1, -1, -2 -- one int64 table for the existing all-reduce
+    cnt = torch.zeros((len(snrs), 5), dtype=torch.int64, device=dev)
+    cae = torch.zeros(len(snrs), dtype=torch.float64, device=dev)
+    counters = sweep.Counters(len(snrs), 5)
+    t0 = time.perf_counter()
+    n_tiles = 0
+    by_batch = {}
+    for si, bi in sweep.tiles_for_rank(len(snrs), batches, rank, world):
+        by_batch.setdefault(bi, []).append(si)
+    for bi, sis in by_batch.items():
+        keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
+        out = plan.ber_sweep_task4(snrs[sis], frames_per_tile, h=h, Time_Delay="random", Freq_Shift="random",
+                                   seeds=[k[0] for k in keys], frame0=keys[0][1], device=dev)
+        cnt[sis, 0] += out["errors"]
+        cnt[sis, 1:] += out["status_counts"]
+        cae[sis] += out["cfo_abs_err"]
+        n_tiles += len(sis)
+        for si in sis:
+            counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
+    counters.errors += cnt.cpu().numpy()                      # the one read of the device counters
+    cfo = cae.cpu()
+    torch.cuda.synchronize()
+    local_s = time.perf_counter() - t0
+    total = sweep.all_reduce_counters(counters, device=dev if backend == "nccl" else None)
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        t = cfo.to(dev) if backend == "nccl" else cfo
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        cfo = t.cpu()
+    errors, bits = total.errors[:, 0], total.bits[:, 0]
+    return {"config": "C3", "estimator": "task4", "SNRs": snrs.tolist(), "errors": errors.tolist(), "bits": bits.tolist(),
+            "BER": (errors / np.maximum(bits, 1)).tolist(), "status_counts": total.errors[:, 1:].tolist(),
+            "cfo_abs_err": cfo.numpy().tolist(), "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world,
+            "tiles_this_rank": n_tiles, "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
+            "order": "noise_first", "impairments": {"Time_Delay": "random", "Freq_Shift": "random"}}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--config", choices=["C5", "M"], default="C5")
+    ap.add_argument("--config", choices=["C5", "M", "C3"], default="C5")
     ap.add_argument("--batches", type=int, default=2, help="tiles per SNR point")
     ap.add_argument("--frames-per-tile", type=int, default=32)
     ap.add_argument("--snrs", type=float, nargs="*", default=None)

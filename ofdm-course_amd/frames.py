@@ -26,6 +26,9 @@ class FrameConfig:
     taps: np.ndarray = field(default_factory=lambda: TAPS6.copy())
     SNR_dB: float = 20.0                   # T5/Main_model_Task_5.m:106
     dominant_taps: int = 6
+    pilots: np.ndarray | None = None       # explicit pilot carriers (a percent layout) instead of the comb
+    pilot_amp: float = 2.0                 # pilot amplitude / max|dict| (T5/Task5_part2.m:85-91; T4 uses 4/3)
+    K_atoms: int | None = None             # dictionary columns when not ceil(N_carrier / comb)
 
     @property
     def T_guard(self):
@@ -33,6 +36,8 @@ class FrameConfig:
 
     @property
     def pilotCarriers(self):
+        if self.pilots is not None:
+            return np.asarray(self.pilots, dtype=np.float64)
         return np.arange(1, self.N_carrier + 1, self.comb, dtype=np.float64)   # T5:21
 
     @property
@@ -42,6 +47,8 @@ class FrameConfig:
 
     @property
     def K(self):
+        if self.K_atoms is not None:
+            return int(self.K_atoms)
         return int(np.ceil(self.N_carrier / self.comb))                         # T5:184
 
     @property
@@ -67,6 +74,16 @@ def config_C5(seed=5):
     return FrameConfig("C5", 8192, 2048, 4, "256QAM", taps=taps, dominant_taps=32)
 
 
+def config_C3():
+    """BASELINE config 3, the Task-4 geometry (T4/Main_model_Task_4.m): Nfft 2048, T_guard 256, 800 carriers with 15 %
+    pilots (the rule of T1/Main_model.m:14-21), pilots +-4/3 max|dict|, 64-QAM, frames of 50 symbols, the 3-tap channel of
+    T4:257-261, 30 dB.  The geometry tools/bench_configs.py:c3_batched builds by hand."""
+    from .drivers.common import layout_percent
+    _, pil, _ = layout_percent(2048, 800, 15, tail=2)
+    return FrameConfig("C3", 2048, 800, 6, "64QAM", N_symb=50, taps=np.array([[0, 1.0], [4, 0.6], [10, 0.3]]),
+                       SNR_dB=30.0, dominant_taps=3, pilots=pil, pilot_amp=4 / 3, K_atoms=int(np.ceil(800 / 6)))
+
+
 def config_small(nfft=256, n_carrier=64, comb=4, const="16QAM", n_symb=5, taps=None, dominant_taps=3):
     """Tiny configuration for oracle-speed parity tests."""
     if taps is None:
@@ -77,7 +94,7 @@ def config_small(nfft=256, n_carrier=64, comb=4, const="16QAM", n_symb=5, taps=N
 def pilot_column(cfg, api):
     """Pilot values of one symbol: alternating +-2*max|dict| (T5/Task5_part2.m:85-91)."""
     d, _ = api.constellation_func(cfg.Constellation)
-    amp = 2 * np.max(np.abs(d))
+    amp = cfg.pilot_amp * np.max(np.abs(d))
     n = len(cfg.pilotCarriers)
     return np.where(np.arange(n) % 2 == 0, amp, -amp).astype(np.complex128)
 

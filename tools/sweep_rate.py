@@ -5,7 +5,12 @@ tx_frames_fused on the same frames, the RX ms of rx_chain_task5 on that tile, an
 size (generation + RX + reduction) as sym/s.  The roofline of the fused generator counts its bytes as 3 sample passes (TX
 write, TX read, RX write) + the packed reference bits, against 8 TB/s.
 
-    python tools/sweep_rate.py [M C4 C5]
+C3 (the Task-4 receiver, 4096 frames of 50 symbols, random STO / CFO per frame, 30 dB): the staged
+tx_frames(noise_first=True, Time_Delay="random", Freq_Shift="random") against tx_frames_fused with the same draws (and
+without the CFO stage, the cost of the per-sample double sincos), rx_chain_task4 on the tile, and a one-point
+ber_sweep_task4 call of the same size.
+
+    python tools/sweep_rate.py [M C4 C5 C3]
 """
 from __future__ import annotations
 
@@ -84,10 +89,52 @@ def measure(name, reps=5):
                          "floor_ms": counted / (PEAK_TBS * 1e12) * 1e3}}
 
 
+def measure_c3(reps=5):
+    cfg, F = fr.config_C3(), 4096
+    dev = torch.device("cuda:0")
+    plan = fr.make_plan(cfg, ofdm, precision="fp32", device=0)
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    snr = cfg.SNR_dB
+    imp = dict(Time_Delay="random", Freq_Shift="random")
+    ms_ex = timed(lambda: plan.tx_frames(F, h=h, SNR=snr, seed=3, device=dev, noise_first=True, **imp), reps)
+    ex = plan.tx_frames(F, h=h, SNR=snr, seed=3, device=dev, noise_first=True, want_draws=True, **imp)
+    draws = (ex["Time_Delay"].clone(), ex["Freq_Shift"].clone())
+    del ex
+    torch.cuda.empty_cache()
+    ms_fused = timed(lambda: plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev, **imp), reps)
+    ms_no_cfo = timed(lambda: plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev, Time_Delay="random"), reps)
+    gen = plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev, want_draws=True, **imp)
+    same_draws = bool(torch.equal(gen["Time_Delay"], draws[0]) and torch.equal(gen["Freq_Shift"], draws[1]))
+    ms_rx = timed(lambda: ofdm.rx_chain_task4(plan, gen["rx"], 1, 1, 1, ref_bits_packed=gen["packed"]), reps)
+    out = ofdm.rx_chain_task4(plan, gen["rx"], 1, 1, 1, ref_bits_packed=gen["packed"])
+    err_rx = int(out["errors"].to(torch.int64).sum().item())
+    del gen, out
+    torch.cuda.empty_cache()
+    ms_sweep = timed(lambda: plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, **imp), reps)
+    res = plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, **imp)
+    err = int(res["errors"][0].item())
+    sample_bytes = 8 * cfg.frame_samples * F
+    counted = 3 * sample_bytes + plan.frame_bytes * F
+    nsym = F * cfg.N_symb
+    r = {"config": "C3", "frames": F, "estimator": "task4", "snr_db": snr, "impairments": "random STO / CFO",
+         "gen_ex_ms": ms_ex, "gen_fused_ms": ms_fused, "gen_speedup": ms_ex / ms_fused, "gen_fused_no_cfo_ms": ms_no_cfo,
+         "draws_equal_ex": same_draws, "rx_ms": ms_rx, "sweep_ms": ms_sweep, "sweep_sym_per_s": nsym / ms_sweep * 1e3,
+         "rx_sym_per_s": nsym / ms_rx * 1e3, "ber": err / (F * plan.frame_bits),
+         "status_counts": res["status_counts"][0].cpu().tolist(),
+         "cfo_abs_err_mean": float(res["cfo_abs_err"][0].item()) / F, "sweep_errors_equal_composed": err == err_rx,
+         "roofline": {"sample_pass_bytes": sample_bytes, "counted_bytes": counted,
+                      "gen_fused_tbs": counted / (ms_fused * 1e-3) / 1e12,
+                      "gen_fused_frac": counted / (ms_fused * 1e-3) / 1e12 / PEAK_TBS,
+                      "floor_ms": counted / (PEAK_TBS * 1e12) * 1e3}}
+    plan.close()
+    torch.cuda.empty_cache()
+    return r
+
+
 def main():
     names = sys.argv[1:] or ["M", "C4", "C5"]
     ofdm.init(0)
-    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure(n) for n in names]}
+    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure_c3() if n == "C3" else measure(n) for n in names]}
     print(json.dumps(out), flush=True)
 
 
