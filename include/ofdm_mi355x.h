@@ -229,6 +229,21 @@ int ofdm_rx_plan_set_mmse(ofdm_rx_plan* plan, const void* h, int64_t n_h, double
 int ofdm_rx_chain_task4(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
                         uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
                         double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int flags);
+/* ofdm_rx_chain_task4 that also returns the sums of MER_func (T5/MER_func.m:3-25; the MER reported beside the BER at
+ * T3/Main_model_Task_3.m:186, T4/Main_model_Task_4.m:374, and the MER(SNR) study of T4:136-200) over each frame's
+ * RX_IQ = get_payload(.)(:), the equalised, fine-synced points the demapper decides, taken from index mer_skip on:
+ *   mer_sums_out[n_frames][2] (double, where `flags` says) = {sum |ideal|^2, sum |ideal - RX_IQ|^2} with ideal the nearest
+ *   constellation point (the demapper's decision), over the 0-based IQ indices mer_skip .. nd * N_symb - 1.
+ * MER = 10 log10(sum s1 / sum s2); summed over frames it is MER_func of the frames' RX_IQ concatenated, as a multi-frame
+ * run of the reference computes it.  mer_skip = Nfft + T_guard reproduces RX_IQ(Nfft+T_Guard+1:end) of T4:163; it must lie
+ * in 0 .. nd * N_symb - 1.  Frames with status -1 or -2 are included, decoded as ofdm_rx_chain_task4 decodes them; a frame
+ * whose equaliser is not finite gives NaN sums, as MER_func is NaN on such an RX_IQ.  The
+ * per-frame sums are reduced in a fixed order (no atomics): bitwise independent of the batching.  mer_sums_out = NULL is
+ * ofdm_rx_chain_task4; every other output is that call's, bit for bit. */
+int ofdm_rx_chain_task4_ex(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int time_desync, int freq_desync,
+                           int mp_desync, uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out,
+                           int64_t* tg_position_out, double* freq_offset_out, int32_t* ifo_out, int32_t* status_out,
+                           void* h_out, int64_t mer_skip, double* mer_sums_out /* [n_frames][2] */, int flags);
 /* Synthetic RX frames of the plan's geometry, generated on the device (no host payload), per frame:
  *   payload (one Philox4x32-10 draw per QAM symbol, stream = frame0 + f)
  *   -> Scrambler with the register reset per frame (T5/Main_model_Task_5.m:55-69; scr_reg15 = HOST uint8[15], NULL = off)
@@ -316,6 +331,21 @@ int ofdm_ber_sweep_task4(ofdm_rx_plan* plan, const void* h, int h_len, int sto_m
                          const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
                          const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
                          uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out, int flags);
+/* ofdm_ber_sweep_task4 with the MER of every point: each frame is decoded by ofdm_rx_chain_task4_ex(mer_skip), and
+ *   mer_sums_out[n_points][2] (double, optional) = the point's {sum s1, sum s2}: MER_func of the point's RX_IQ concatenated,
+ *   MER = 10 log10(s1 / s2) (T4/Main_model_Task_4.m:163; with STO 12, time_desync = 1, freq_desync = mp_desync = 0 and
+ *   mer_skip = Nfft + T_guard a point is the MER(SNR) study of T4:136-200 over frames_per_point realisations);
+ *   frame_mer_sums_out[n_points][frames_per_point][2] (double, optional): the per-frame sums.
+ * The per-point sums are reduced on the device after the last chunk in a fixed order: bitwise independent of
+ * max_frames_per_chunk.  mer_skip: 0 .. nd * N_symb - 1.  Both MER outputs NULL is ofdm_ber_sweep_task4; every other output
+ * is that call's, bit for bit.  Outputs live where `flags` says; OFDM_DEVICE keeps the rule of ofdm_ber_sweep_task4. */
+int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* plan, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                            double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                            const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                            const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                            uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                            int64_t mer_skip, double* mer_sums_out /* [n_points][2] */,
+                            double* frame_mer_sums_out /* [n_points][frames_per_point][2] */, int flags);
 /* Per-frame DeScrambler inside ofdm_rx_chain_task5 / ofdm_rx_chain_task4 (T5/DeScrambler.m:1-16 with
  * the register reset for every frame, T5/Main_model_Task_5.m:257-274, T4/Main_model_Task_4.m:354-364): the demapped bits
  * of a frame go through d[i] = s[i] ^ s[i-13] ^ s[i-14], s[-m] = reg15[m-1], before they are written to bits_out and

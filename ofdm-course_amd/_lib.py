@@ -71,6 +71,7 @@ SIGNATURES = {
     "ofdm_rx_plan_destroy": [_vp],
     "ofdm_rx_plan_set_mmse": [_vp, _vp, _i64, _d, _i],
     "ofdm_rx_chain_task4": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_rx_chain_task4_ex": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i],
     "ofdm_tx_frames": [_vp, _vp, _i, _d, _i, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _i],
     "ofdm_tx_frames_ex": [_vp, _vp, _i, _d, _i, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_rx_plan_set_descrambler": [_vp, _vp],
@@ -86,6 +87,8 @@ SIGNATURES = {
     "ofdm_tx_frames_fused_ex": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task4": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
                              _vp, _i],
+    "ofdm_ber_sweep_task4_ex": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp,
+                                _vp, _vp, _i64, _vp, _vp, _i],
 }
 _RESTYPES = {"ofdm_last_error_string": C.c_char_p, "ofdm_rx_plan_frame_bytes": C.c_int64}
 

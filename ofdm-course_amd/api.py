@@ -860,7 +860,8 @@ class RxPlan:
 
     def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
                         freq_desync=None, mp_desync=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
-                        want_frame_errors=False, max_frames_per_chunk=0):
+                        want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, mer_skip=0,
+                        want_frame_mer=False):
         """One device-resident tile of a BER(SNR) sweep of the Task-4 receiver (ofdm_ber_sweep_task4): for every SNR of
         `SNRs` the frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p], Time_Delay,
         Freq_Shift) decoded by rx_chain_task4(time_desync, freq_desync, mp_desync) on this plan.  A desync flag left at None
@@ -870,7 +871,11 @@ class RxPlan:
         Returns dict(errors=[n] bit errors, bits=bits counted per point, status_counts=[n, 4] frames with rx_chain_task4
         status 0, 1, -1, -2, cfo_abs_err=[n] sum of |FreqOffset + IFO - Freq_Shift| over the point's frames (0 with
         freq_desync off) (+ frame_errors=[n, frames_per_point] with want_frame_errors)); torch tensors on `device` (no host
-        synchronisation) when it is given, numpy arrays otherwise."""
+        synchronisation) when it is given, numpy arrays otherwise.
+        want_mer (ofdm_ber_sweep_task4_ex): also mer_sums=[n, 2], the MER_func sums of each point's frames (RX_IQ from
+        0-based index mer_skip on, frames concatenated), and MER_dB=[n] (computed on `device` when it is given); with
+        want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2].  Time_Delay=12, time_desync=1,
+        freq_desync=0, mp_desync=0, mer_skip=Nfft+T_guard is the MER(SNR) study of T4/Main_model_Task_4.m:136-200."""
         snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
         n = snr.size
         fpp = int(frames_per_point)
@@ -890,6 +895,8 @@ class RxPlan:
             stc = torch.empty((n, 4), dtype=torch.int64, device=dev)
             cae = torch.empty((n,), dtype=torch.float64, device=dev)
             fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
+            ms = torch.empty((n, 2), dtype=torch.float64, device=dev) if want_mer else None
+            fm = torch.empty((n, fpp, 2), dtype=torch.float64, device=dev) if want_mer and want_frame_mer else None
             L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
             flags |= L.OFDM_DEVICE
@@ -899,17 +906,30 @@ class RxPlan:
             stc = np.empty((n, 4), dtype=np.uint64)
             cae = np.empty((n,), dtype=np.float64)
             fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
+            ms = np.empty((n, 2), dtype=np.float64) if want_mer else None
+            fm = np.empty((n, fpp, 2), dtype=np.float64) if want_mer and want_frame_mer else None
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
         keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-        L.check(self.lib.ofdm_ber_sweep_task4(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
-                                              snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
-                                              int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
-                                              ptr(fe), flags), "ber_sweep_task4")
+        if not want_mer:
+            L.check(self.lib.ofdm_ber_sweep_task4(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
+                                                  snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                                  int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
+                                                  ptr(fe), flags), "ber_sweep_task4")
+        else:
+            L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
+                                                     snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                                     int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
+                                                     ptr(fe), int(mer_skip), ptr(ms), ptr(fm), flags), "ber_sweep_task4_ex")
         host = device is None
         out = dict(errors=err.astype(np.int64) if host else err, bits=fpp * self.frame_bits,
                    status_counts=stc.astype(np.int64) if host else stc, cfo_abs_err=cae)
         if want_frame_errors:
             out["frame_errors"] = fe
+        if want_mer:
+            out["mer_sums"] = ms
+            out["MER_dB"] = _mer_db(ms)
+            if want_frame_mer:
+                out["frame_mer_sums"] = fm
         return out
 
     def set_timing(self, enable=True):
@@ -968,14 +988,18 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
     return dict(bits=bits, errors=errors, H=H, index=idx)
 
 
-def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, ref_bits_packed=None, want_h=False):
+def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, ref_bits_packed=None, want_h=False,
+                   want_mer=False, mer_skip=0):
     """Task-4 receiver over a batch of frames (T4/Main_model_Task_4.m:278-347 per frame): AutoCorrFunction -> add_STO x2 ->
     add_CFO -> remove_IFO -> OFDM_demodulator -> fine_sync -> estimate_channel -> equalize_signal -> get_payload -> demapping.
 
     rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
     Returns dict(bits=[n_frames, frame_bytes] packed demapped bits (not descrambled), errors vs ref_bits_packed or None,
     TgPosition=[n_frames] int64, FreqOffset=[n_frames] float64, IFO=[n_frames] int32, status=[n_frames] int32
-    (0 ok, 1 AutoCorrFunction fallback, -1 no IFO line, -2 TgPosition out of range), H=[N_carrier, n_frames] or None)."""
+    (0 ok, 1 AutoCorrFunction fallback, -1 no IFO line, -2 TgPosition out of range), H=[N_carrier, n_frames] or None).
+    want_mer (ofdm_rx_chain_task4_ex): also mer_sums=[n_frames, 2] float64, the sums {|ideal|^2, |ideal - RX_IQ|^2} of
+    MER_func (T5/MER_func.m:3-25) over each frame's get_payload(.)(:) from 0-based index mer_skip on (Nfft + T_guard =
+    RX_IQ(Nfft+T_Guard+1:end) of T4/Main_model_Task_4.m:163), and MER_dB=[n_frames] = 10 log10(s1 / s2)."""
     call = _Call(rx, f64=plan.f64)
     rows, nfr = _shape2(rx)
     if rows != plan.frame_samples:
@@ -995,10 +1019,26 @@ def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, 
     ifo, pifo = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
-    L.check(call.lib.ofdm_rx_chain_task4(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
-                                         int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, call.flags),
-            "rx_chain_task4")
-    return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
+    if not want_mer:
+        L.check(call.lib.ofdm_rx_chain_task4(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
+                                             int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, call.flags),
+                "rx_chain_task4")
+        return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
+    mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
+    mer = mer.T
+    L.check(call.lib.ofdm_rx_chain_task4_ex(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
+                                            int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, int(mer_skip),
+                                            pmer, call.flags), "rx_chain_task4_ex")
+    return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H, mer_sums=mer,
+                MER_dB=_mer_db(mer))
+
+
+def _mer_db(sums):
+    """10 log10(s1 / s2) of [..., 2] MER_func sums (T5/MER_func.m:25): on the device for a torch tensor, no synchronisation."""
+    if _is_torch(sums):
+        return 10.0 * torch.log10(sums[..., 0] / sums[..., 1])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return 10.0 * np.log10(sums[..., 0] / sums[..., 1])
 
 
 def task5_part2_tile(plan: RxPlan, tx_noised, taps_list, SNR_dB, ref_bits_packed):

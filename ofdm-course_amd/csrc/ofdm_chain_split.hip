@@ -35,14 +35,35 @@ __global__ __launch_bounds__(256) void pilot_ls_kernel(FastParams<T> P, const cx
 // symbol), four symbols x two pairs requested together, and decides every carrier it loads -- a carrier without data (pilot, or
 // past N_carrier) stores its decision to a dump byte behind the codes: no exec-mask branch per sample, half the load
 // instructions, twice the bytes in flight of the 8-byte form.
-template <typename T, int BA, bool HEXT, bool VEC = false>
+// MER (Mer = MerOut, eq_demap_run with mer_sums): the sums of MER_func.m:21-23 over the equalised points ye the thread
+// decides, s1 += |p|^2 and s2 += |p - ye|^2 with p = the decided point, for frame IQ indices i = s nd + d >= mer.skip (the
+// order of get_payload(:)), in double; wave butterfly, then the four wave partials in index order -> mer.sums[f] = {s1, s2}.
+// No atomics: the sums do not depend on the grid or the batching.  An empty Mer is the kernel as it always was (same
+// arguments, same instructions).
+struct MerOut {
+  int skip;
+  double* sums;                                                        // [n_frames][2]
+};
+
+template <typename T>
+__device__ __forceinline__ void mer_add(cx<T> p, cx<T> ye, double& s1, double& s2) {
+  const cx<T> e = p - ye;
+  s1 += (double)p.x * p.x + (double)p.y * p.y;
+  s2 += (double)e.x * e.x + (double)e.y * e.y;
+}
+
+template <typename T, int BA, bool HEXT, bool VEC = false, typename... Mer>
 __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft, const cx<T>* __restrict__ xk,
                                                        int x_stride /* rows per symbol column of xk */, int64_t n_frames, uint32_t* __restrict__ bits_out,
                                                        const uint32_t* __restrict__ ref_bits,
                                                        uint32_t* __restrict__ errors_out, cx<T>* __restrict__ h_out,
                                                        int32_t* __restrict__ index_out, DemapTable<T> tab,
                                                        const double* __restrict__ fine_est /* [n_frames][2] or null */,
-                                                       int time_desync, int freq_desync) {
+                                                       int time_desync, int freq_desync, Mer... mer) {
+  constexpr bool MER = sizeof...(Mer) == 1;
+  int mer_skip = 0;
+  double* mer_sums = nullptr;
+  if constexpr (MER) ((mer_skip = mer.skip, mer_sums = mer.sums), ...);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // fine_est: the residual timing / phase estimates of fine_sync (tau, phase) per frame; its rotation
   // exp(j (2 pi tau k + phase)) (fine_sync.m:36-43) is applied to every sample as it is read, with the rounding of the
@@ -55,6 +76,10 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
   __shared__ T sh_lut[DEMAP_LUT_ELEMS];
   const int gid = threadIdx.x;
   if constexpr (BA >= 2) demap_lut_fill<T, BA>(tab, sh_lut, gid);
+  __shared__ cx<T> sh_pts[MER ? 256 : 1];                               // MER: the decided point of every (byte) code
+  __shared__ double sh_mer[MER ? 4 : 1][2];
+  if constexpr (MER)
+    if (gid < (1 << tab.bps)) sh_pts[gid] = demap_point(tab, gid);
   const int taps = P.taps, nd = P.nd, nc = P.n_carrier;
   const int bps = BA > 0 ? 2 * BA : P.bps;
   const int n_codes = nd * P.n_symb;
@@ -63,6 +88,7 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
   __syncthreads();
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     if (gid == 0) sh_err = 0;
+    double s1 = 0, s2 = 0;                                            // MER sums of this thread's samples
     if (!HEXT && gid < taps) {
       const int idx = P.tap_idx[f * taps + gid];
       sh_tidx[gid] = idx;
@@ -167,8 +193,14 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
 #pragma unroll
               for (int u = 0; u < 2; ++u) {
                 const cx<T> y0 = mk<T>(xv[v][u].x, xv[v][u].y) * g[u][0], y1 = mk<T>(xv[v][u].z, xv[v][u].w) * g[u][1];
-                codes[ci[u][0] + (s0 + v) * cinc[u][0]] = (uint8_t)slice_symbol<T, BA>(tab, y0);
-                codes[ci[u][1] + (s0 + v) * cinc[u][1]] = (uint8_t)slice_symbol<T, BA>(tab, y1);
+                const int c0 = slice_symbol<T, BA>(tab, y0);
+                codes[ci[u][0] + (s0 + v) * cinc[u][0]] = (uint8_t)c0;
+                const int c1 = slice_symbol<T, BA>(tab, y1);
+                codes[ci[u][1] + (s0 + v) * cinc[u][1]] = (uint8_t)c1;
+                if constexpr (MER) {                                   // the dump slots (cinc 0) do not count
+                  if (cinc[u][0] && ci[u][0] + (s0 + v) * nd >= mer_skip) mer_add(sh_pts[(uint8_t)c0], y0, s1, s2);
+                  if (cinc[u][1] && ci[u][1] + (s0 + v) * nd >= mer_skip) mer_add(sh_pts[(uint8_t)c1], y1, s1, s2);
+                }
               }
             }
         }
@@ -201,14 +233,28 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
                 if constexpr (BA >= 2 && sizeof(T) == 8) code = demap_square_lut<T, BA>(tab, sh_lut, ye);   // parity mode: exact, 9 ops / axis
                 else code = slice_symbol<T, BA>(tab, ye);                                                  // fp32: arithmetic rank
                 codes[(s0 + v) * nd + dv[u]] = (uint8_t)code;
+                if constexpr (MER)
+                  if ((s0 + v) * nd + dv[u] >= mer_skip) mer_add(sh_pts[(uint8_t)code], ye, s1, s2);
               }
         }
       }
+    }
+    if constexpr (MER) {
+      for (int off = 32; off > 0; off >>= 1) {
+        s1 += __shfl_xor(s1, off, 64);
+        s2 += __shfl_xor(s2, off, 64);
+      }
+      if ((gid & 63) == 0) { sh_mer[gid >> 6][0] = s1; sh_mer[gid >> 6][1] = s2; }
     }
     __syncthreads();
     const unsigned int err = pack_frame<2 * BA>(codes, n_codes, bps, P.frame_words,
                                                 bits_out ? bits_out + f * P.frame_words : nullptr,
                                                 ref_bits ? ref_bits + f * P.frame_words : nullptr, gid, 256);
+    if constexpr (MER)
+      if (gid == 0) {
+        mer_sums[2 * f] = ((sh_mer[0][0] + sh_mer[1][0]) + sh_mer[2][0]) + sh_mer[3][0];
+        mer_sums[2 * f + 1] = ((sh_mer[0][1] + sh_mer[1][1]) + sh_mer[2][1]) + sh_mer[3][1];
+      }
     if (ref_bits && errors_out) {
       if (err) atomicAdd(&sh_err, err);
       __syncthreads();
@@ -547,7 +593,7 @@ bool chain_split_supported(int nfft, int n_carrier, int taps, int bps, int64_t n
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,
                  void* bits, const void* ref, void* errs, void* h_out, void* idx_out, const double* fine_est, int time_desync,
-                 int freq_desync) {
+                 int freq_desync, int mer_skip, double* mer_sums) {
   hipStream_t st = ctx().stream;
   DemapTable<T> tab;
   fill_demap_table<T>(*pv.dict, *pv.cinfo, tab);
@@ -555,17 +601,36 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
   const bool vec = std::is_same<T, float>::value && (pv.n_carrier & 1) == 0 && (x_stride & 1) == 0 && pv.n_carrier <= 2048 &&
                    !getenv("OFDM_EQD_SCALAR");
   OFDM_ARG(dyn <= 150 * 1024, "rx_chain: equalise / demap stage needs %zu bytes of LDS", dyn);
-  auto launch = [&](auto kern) -> int {
-    int per_cu = resident_blocks_per_cu((const void*)kern, 256, dyn);
+  auto grid_of = [&](const void* kern) {
+    int per_cu = resident_blocks_per_cu(kern, 256, dyn);
     if (const char* e = getenv("OFDM_EQD_WG_PER_CU")) per_cu = std::max(1, atoi(e));
-    const unsigned grid = (unsigned)std::min<int64_t>(n_frames, (int64_t)ctx().num_cu * per_cu);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), dyn, st, P, pv.nfft, xk, x_stride, n_frames, (uint32_t*)bits,
-                       (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, fine_est, time_desync,
-                       freq_desync);
+    return (unsigned)std::min<int64_t>(n_frames, (int64_t)ctx().num_cu * per_cu);
+  };
+  auto launch = [&](auto kern) -> int {
+    hipLaunchKernelGGL(kern, dim3(grid_of((const void*)kern)), dim3(256), dyn, st, P, pv.nfft, xk, x_stride, n_frames,
+                       (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, fine_est,
+                       time_desync, freq_desync);
+    return OFDM_OK;
+  };
+  auto launch_mer = [&](auto kern) -> int {                    // the MER variant: the same arguments + the MER sums
+    hipLaunchKernelGGL(kern, dim3(grid_of((const void*)kern)), dim3(256), dyn, st, P, pv.nfft, xk, x_stride, n_frames,
+                       (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, fine_est,
+                       time_desync, freq_desync, MerOut{mer_skip, mer_sums});
     return OFDM_OK;
   };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
 #define SPLIT_CASE(BAV)                                                                                    \
+  if (mer_sums) {                                                                                          \
+    if constexpr (std::is_same<T, float>::value) {                                                         \
+      if (vec) {                                                                                           \
+        if (hext) OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, true, true, MerOut>));                           \
+        else OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, false, true, MerOut>));                               \
+        break;                                                                                             \
+      }                                                                                                    \
+    }                                                                                                      \
+    if (hext) OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, true, false, MerOut>)); else OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, false, false, MerOut>)); \
+    break;                                                                                                 \
+  }                                                                                                        \
   if constexpr (std::is_same<T, float>::value) {                                                           \
     if (vec) {                                                                                             \
       if (hext) OFDM_TRY(launch(eq_demap_kernel<T, BAV, true, true>)); else OFDM_TRY(launch(eq_demap_kernel<T, BAV, false, true>)); \
@@ -583,9 +648,9 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
   return check_launch("eq_demap_kernel");
 }
 template int eq_demap_run<float>(const FastPlanView&, const FastParams<float>&, const cx<float>*, int, bool, int64_t, void*,
-                                 const void*, void*, void*, void*, const double*, int, int);
+                                 const void*, void*, void*, void*, const double*, int, int, int, double*);
 template int eq_demap_run<double>(const FastPlanView&, const FastParams<double>&, const cx<double>*, int, bool, int64_t, void*,
-                                  const void*, void*, void*, void*, const double*, int, int);
+                                  const void*, void*, void*, void*, const double*, int, int, int, double*);
 
 template <typename T>
 static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,

@@ -964,7 +964,7 @@ int t4_demod_wave_launch(const void* rx, void* X, const void* tw, int64_t len, i
 template <typename T>
 static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
                      void* dbits, const void* dref, void* derr, int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat,
-                     void* dh_out, Stage& st) {
+                     void* dh_out, int mer_skip, double* dmer, Stage& st) {
   const int N = pl->nfft, Tg = pl->t_guard, S = pl->n_symb, np = pl->np, nc = pl->n_carrier;
   const int64_t len = (int64_t)(N + Tg) * S;
   const int64_t n_out = len - Tg - N;
@@ -1153,7 +1153,7 @@ static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desy
   if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, F, &craw));
   OFDM_TRY(eq_demap_run<T>(pv2, P, (const cx<T>*)dX, direct ? nc : N, true, F, descr_pass ? craw : dbits,
                            descr_pass ? nullptr : dref, descr_pass ? nullptr : derr, dh_out, nullptr, lazy_rot,
-                           time_desync, freq_desync));                                                                   // T4:334-347
+                           time_desync, freq_desync, mer_skip, dmer));                          // T4:334-347 (+ MER_func sums, :163)
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, F));
   mark(5);
   return OFDM_OK;
@@ -1165,12 +1165,15 @@ using namespace ofdm;
 
 extern "C" {
 
-int ofdm_rx_chain_task4(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
-                        uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
-                        double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int flags) {
+int ofdm_rx_chain_task4_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                           uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                           double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
+                           double* mer_sums_out, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && rx && n_frames >= 0, "rx_chain_task4: bad arguments");
   OFDM_ARG(pl->nd >= 1, "rx_chain_task4: the plan has no data carriers");
+  OFDM_ARG(mer_skip >= 0 && mer_skip < (int64_t)pl->nd * pl->n_symb,
+           "rx_chain_task4_ex: mer_skip must be 0 .. nd * N_symb - 1 (%lld)", (long long)mer_skip);
   OFDM_PLAN_DEVICE(pl);
   OFDM_ARG((is_f64(flags) ? 1 : 0) == pl->f64, "rx_chain_task4: precision flag differs from the plan's");
   OFDM_ARG(pl->pilots_in_band, "rx_chain_task4: pilots outside 1..N_carrier are not supported");
@@ -1192,13 +1195,22 @@ int ofdm_rx_chain_task4(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int 
   if (freq_offset_out) OFDM_TRY(st.out(freq_offset_out, sizeof(double) * n_frames, &dfo)); else OFDM_TRY(st.scratch(sizeof(double) * n_frames, &dfo));
   if (ifo_out) OFDM_TRY(st.out(ifo_out, sizeof(int32_t) * n_frames, &difo)); else OFDM_TRY(st.scratch(sizeof(int32_t) * n_frames, &difo));
   if (status_out) OFDM_TRY(st.out(status_out, sizeof(int32_t) * n_frames, &dstat)); else OFDM_TRY(st.scratch(sizeof(int32_t) * n_frames, &dstat));
+  void* dmer;
+  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * n_frames, &dmer));
   if (pl->f64)
     OFDM_TRY(task4_run<double>(pl, drx, n_frames, time_desync, freq_desync, mp_desync, dbits, dref, derr, (int64_t*)dtg, (double*)dfo,
-                               (int32_t*)difo, (int32_t*)dstat, dh, st));
+                               (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer, st));
   else
     OFDM_TRY(task4_run<float>(pl, drx, n_frames, time_desync, freq_desync, mp_desync, dbits, dref, derr, (int64_t*)dtg, (double*)dfo,
-                              (int32_t*)difo, (int32_t*)dstat, dh, st));
+                              (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer, st));
   return st.finish();
+}
+
+int ofdm_rx_chain_task4(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                        uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                        double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int flags) {
+  return ofdm_rx_chain_task4_ex(pl, rx, n_frames, time_desync, freq_desync, mp_desync, bits_out, ref_bits, errors_out,
+                                tg_position_out, freq_offset_out, ifo_out, status_out, h_out, 0, nullptr, flags);
 }
 
 int ofdm_AutoCorrFunction(const void* rx, int64_t len, int width_window, int nfft, void* rho_out,

@@ -289,6 +289,32 @@ __global__ __launch_bounds__(256) void t4_point_reduce_kernel(const uint32_t* __
   }
 }
 
+// per point p of a Task-4 sweep with MER: the per-frame MER_func sums {s1, s2} of eq_demap_kernel's MER variant -> the
+// point's {sum s1, sum s2} (MER_func of the point's RX_IQ concatenated) -- the fixed order of t4_point_reduce_kernel:
+// each thread a fixed stride, a fixed butterfly, the four wave partials paired; bitwise independent of the chunking
+__global__ __launch_bounds__(256) void t4_point_mer_kernel(const double* __restrict__ frame_mer, int64_t frames_per_point,
+                                                           double* __restrict__ mer_sums) {
+  const int64_t p = blockIdx.x;
+  double a = 0, b = 0;
+  for (int64_t i = threadIdx.x; i < frames_per_point; i += 256) {
+    const int64_t k = p * frames_per_point + i;
+    a += frame_mer[2 * k];
+    b += frame_mer[2 * k + 1];
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    a += __shfl_xor(a, off, 64);
+    b += __shfl_xor(b, off, 64);
+  }
+  __shared__ double pa[4], pb[4];
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { pa[w] = a; pb[w] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mer_sums[2 * p] = (pa[0] + pa[1]) + (pa[2] + pa[3]);
+    mer_sums[2 * p + 1] = (pb[0] + pb[1]) + (pb[2] + pb[3]);
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -634,12 +660,13 @@ extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_le
   return st.finish();
 }
 
-extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
-                                    double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
-                                    const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
-                                    const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
-                                    uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
-                                    int flags) {
+extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
+                                       int cfo_mode, double cfo_value, int time_desync, int freq_desync, int mp_desync,
+                                       const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,
+                                       int64_t frame0, const uint8_t* scr_reg15, int64_t max_frames_per_chunk,
+                                       uint64_t* errors_out, uint64_t* status_counts_out, double* cfo_abs_err_out,
+                                       uint32_t* frame_errors_out, int64_t mer_skip, double* mer_sums_out,
+                                       double* frame_mer_sums_out, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4: bad arguments");
   OFDM_ARG(max_frames_per_chunk >= 0 && max_frames_per_chunk <= 65535,
@@ -649,25 +676,32 @@ extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, 
   OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task4"));
   OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "ber_sweep_task4"));
   OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task4"));
+  OFDM_ARG(mer_skip >= 0 && mer_skip < (int64_t)pl->nd * pl->n_symb,
+           "ber_sweep_task4_ex: mer_skip must be 0 .. nd * N_symb - 1 (%lld)", (long long)mer_skip);
   TxfChannel ch;
   OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
   if (n_points == 0) return OFDM_OK;
   Stage st(flags);
   const int64_t NF = n_points * frames_per_point;
-  void *derr, *dsc, *dabs, *dfe;
+  void *derr, *dsc, *dabs, *dfe, *dmer, *dfm;
   OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
   OFDM_TRY(st.out(status_counts_out, sizeof(uint64_t) * 4 * (size_t)n_points, &dsc));
   OFDM_TRY(st.out(cfo_abs_err_out, sizeof(double) * (size_t)n_points, &dabs));
   OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)NF, &dfe));
+  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_points, &dmer));
+  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * (size_t)NF, &dfm));
+  const bool mer = dmer || dfm;
   hipStream_t s = ctx().stream;
   if (frames_per_point == 0) {
     OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, s));
     if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, s));
     if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, s));
+    if (dmer) OFDM_HIP(hipMemsetAsync(dmer, 0, sizeof(double) * 2 * (size_t)n_points, s));
     return st.finish();
   }
   // the per-frame values of every point, reduced once after the last chunk
   if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)NF, &dfe));
+  if (mer && !dfm) OFDM_TRY(st.scratch(sizeof(double) * 2 * (size_t)NF, &dfm));
   void *dtg, *dfo, *difo, *dstat, *dsto, *dcfo;
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dtg));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dfo));
@@ -679,8 +713,9 @@ extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, 
   const bool scr = scr_reg15 != nullptr;
   // default chunk: the generator workspace and the Task-4 arena (shared with ofdm_task5_part2_tile) budgeted together
   int64_t CH = max_frames_per_chunk;
-  if (CH == 0)
-    CH = std::max<int64_t>(1, (int64_t)(2 * TXF_WS_BUDGET / (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl))));
+  if (CH == 0)                                                  // (+ the per-frame MER sums when they are wanted)
+    CH = std::max<int64_t>(1, (int64_t)(2 * TXF_WS_BUDGET /
+                                        (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl) + (mer ? 16 : 0))));
   CH = std::max<int64_t>(1, std::min<int64_t>({CH, frames_per_point, 65535}));
   TxfBuffers b;
   OFDM_TRY(txf_workspace(pl, CH, scr, true, b, true));
@@ -696,14 +731,30 @@ extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, 
       imp.sto = (int64_t*)dsto + o;
       imp.cfo = (double*)dcfo + o;
       OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr, &imp));
-      OFDM_TRY(ofdm_rx_chain_task4(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr, (const uint8_t*)b.ref,
-                                   (uint32_t*)dfe + o, (int64_t*)dtg + o, (double*)dfo + o, (int32_t*)difo + o,
-                                   (int32_t*)dstat + o, nullptr, rxflags));
+      OFDM_TRY(ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr, (const uint8_t*)b.ref,
+                                      (uint32_t*)dfe + o, (int64_t*)dtg + o, (double*)dfo + o, (int32_t*)difo + o,
+                                      (int32_t*)dstat + o, nullptr, mer_skip, mer ? (double*)dfm + 2 * o : nullptr, rxflags));
     }
   }
   hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const uint32_t*)dfe,
                      (const int32_t*)dstat, (const double*)dfo, (const int32_t*)difo, (const double*)dcfo, frames_per_point,
                      freq_desync ? 1 : 0, (unsigned long long*)derr, (unsigned long long*)dsc, (double*)dabs);
   OFDM_TRY(check_launch("t4_point_reduce_kernel"));
+  if (dmer) {
+    hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const double*)dfm, frames_per_point,
+                       (double*)dmer);
+    OFDM_TRY(check_launch("t4_point_mer_kernel"));
+  }
   return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                                    double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                                    const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                                    const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                                    uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                                    int flags) {
+  return ofdm_ber_sweep_task4_ex(pl, h, h_len, sto_mode, sto_value, cfo_mode, cfo_value, time_desync, freq_desync, mp_desync,
+                                 snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk, errors_out,
+                                 status_counts_out, cfo_abs_err_out, frame_errors_out, 0, nullptr, nullptr, flags);
 }

@@ -16,7 +16,9 @@ batch, the same tile keys); the counters stay in a device tensor and are read on
 frames with a random STO / CFO per frame, through `RxPlan.ber_sweep_task4` (ofdm_ber_sweep_task4), with the same tile keys
 and dealing as --fused.  Per point the JSON adds `status_counts` (frames with receiver status 0, 1, -1, -2) and
 `cfo_abs_err` (the sum of |FreqOffset + IFO - Freq_Shift| over the point's frames).  The integer counters travel in the int64
-all-reduce; the CFO sums in a second, float64 one.
+all-reduce; the CFO sums in a second, float64 one.  --mer (C3 only) adds per point `MER_dB`, the MER of the point's frames
+(MER_func of RX_IQ(Nfft+T_Guard+1:end) per frame, concatenated; ofdm_ber_sweep_task4_ex): its two MER_func sums travel in the
+float64 all-reduce beside the CFO sums.
 
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
@@ -34,7 +36,7 @@ import numpy as np
 
 
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
-        rank=0, world=1, device_index=0, backend="nccl", fused=False):
+        rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False):
     """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}."""
     import torch
     import ofdm_course_amd as ofdm
@@ -51,7 +53,9 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         hh = np.zeros(cfg.N_carrier, dtype=np.complex128)
         hh[: len(h)] = h
     if config == "C3":
-        return _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend)
+        return _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer)
+    if mer:
+        raise ValueError("sweep_ber: --mer needs --config C3 (the Task-4 receiver)")
     counters = sweep.Counters(len(snrs))
     t0 = time.perf_counter()
     n_tiles = 0
@@ -93,8 +97,9 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
             **({"order": "noise_first", "fused": True} if fused else {})}
 
 
-def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend):
-    """--config C3: every tile of a batch in one ber_sweep_task4 call, random STO / CFO, all three desync stages on."""
+def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer=False):
+    """--config C3: every tile of a batch in one ber_sweep_task4 call, random STO / CFO, all three desync stages on.
+    mer: the MER_func sums {s1, s2} per point (mer_skip = Nfft + T_guard) as two more float64 columns beside the CFO sum."""
     import torch
     import torch.distributed as dist
     import ofdm_course_amd as ofdm
@@ -103,7 +108,7 @@ def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank,
     h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
     # columns: bit errors, then frames with status 0, 1, -1, -2 -- one int64 table for the existing all-reduce
     cnt = torch.zeros((len(snrs), 5), dtype=torch.int64, device=dev)
-    cae = torch.zeros(len(snrs), dtype=torch.float64, device=dev)
+    cae = torch.zeros((len(snrs), 3 if mer else 1), dtype=torch.float64, device=dev)     # CFO sum (+ MER s1, s2)
     counters = sweep.Counters(len(snrs), 5)
     t0 = time.perf_counter()
     n_tiles = 0
@@ -113,10 +118,13 @@ def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank,
     for bi, sis in by_batch.items():
         keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
         out = plan.ber_sweep_task4(snrs[sis], frames_per_tile, h=h, Time_Delay="random", Freq_Shift="random",
-                                   seeds=[k[0] for k in keys], frame0=keys[0][1], device=dev)
+                                   seeds=[k[0] for k in keys], frame0=keys[0][1], device=dev, want_mer=mer,
+                                   mer_skip=cfg.Nfft + cfg.T_guard)
         cnt[sis, 0] += out["errors"]
         cnt[sis, 1:] += out["status_counts"]
-        cae[sis] += out["cfo_abs_err"]
+        cae[sis, 0] += out["cfo_abs_err"]
+        if mer:
+            cae[sis, 1:] += out["mer_sums"]
         n_tiles += len(sis)
         for si in sis:
             counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
@@ -130,11 +138,16 @@ def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank,
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         cfo = t.cpu()
     errors, bits = total.errors[:, 0], total.bits[:, 0]
-    return {"config": "C3", "estimator": "task4", "SNRs": snrs.tolist(), "errors": errors.tolist(), "bits": bits.tolist(),
-            "BER": (errors / np.maximum(bits, 1)).tolist(), "status_counts": total.errors[:, 1:].tolist(),
-            "cfo_abs_err": cfo.numpy().tolist(), "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world,
-            "tiles_this_rank": n_tiles, "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
-            "order": "noise_first", "impairments": {"Time_Delay": "random", "Freq_Shift": "random"}}
+    flt = cfo.numpy()
+    res = {"config": "C3", "estimator": "task4", "SNRs": snrs.tolist(), "errors": errors.tolist(), "bits": bits.tolist(),
+           "BER": (errors / np.maximum(bits, 1)).tolist(), "status_counts": total.errors[:, 1:].tolist(),
+           "cfo_abs_err": flt[:, 0].tolist(), "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world,
+           "tiles_this_rank": n_tiles, "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
+           "order": "noise_first", "impairments": {"Time_Delay": "random", "Freq_Shift": "random"}}
+    if mer:
+        res["mer_sums"] = flt[:, 1:].tolist()
+        res["MER_dB"] = (10.0 * np.log10(flt[:, 1] / flt[:, 2])).tolist()
+    return res
 
 
 def main():
@@ -148,6 +161,7 @@ def main():
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI; gloo for rehearsals")
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank on this GPU")
     ap.add_argument("--fused", action="store_true", help="reference order (Noise -> conv) through RxPlan.ber_sweep")
+    ap.add_argument("--mer", action="store_true", help="C3: per-point MER_dB (MER_func sums of the Task-4 receiver)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch
@@ -163,7 +177,7 @@ def main():
         else:
             dist.init_process_group(a.backend)
     res = run(a.config, a.snrs, a.batches, a.frames_per_tile, a.precision, estimator=a.estimator, rank=rank, world=world,
-              device_index=dev_index, backend=a.backend, fused=a.fused)
+              device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer)
     if rank == 0:
         text = json.dumps(res)
         if a.json:

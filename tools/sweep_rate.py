@@ -8,9 +8,11 @@ write, TX read, RX write) + the packed reference bits, against 8 TB/s.
 C3 (the Task-4 receiver, 4096 frames of 50 symbols, random STO / CFO per frame, 30 dB): the staged
 tx_frames(noise_first=True, Time_Delay="random", Freq_Shift="random") against tx_frames_fused with the same draws (and
 without the CFO stage, the cost of the per-sample double sincos), rx_chain_task4 on the tile, and a one-point
-ber_sweep_task4 call of the same size.
+ber_sweep_task4 call of the same size.  With --mer the C3 entry adds the same sweep with the MER sums on
+(ber_sweep_task4(want_mer=True, mer_skip=Nfft+T_guard), ofdm_ber_sweep_task4_ex) and rx_chain_task4 with want_mer, each timed
+in alternation with its MER-off form (rounds of `reps` calls each) so that the two medians see the same clocks.
 
-    python tools/sweep_rate.py [M C4 C5 C3]
+    python tools/sweep_rate.py [--mer] [M C4 C5 C3]
 """
 from __future__ import annotations
 
@@ -89,7 +91,16 @@ def measure(name, reps=5):
                          "floor_ms": counted / (PEAK_TBS * 1e12) * 1e3}}
 
 
-def measure_c3(reps=5):
+def ab_timed(fa, fb, reps=5, rounds=3):
+    """medians of fa and fb timed in alternating rounds (a drift of the clocks hits both)"""
+    a, b = [], []
+    for _ in range(rounds):
+        a.append(timed(fa, reps))
+        b.append(timed(fb, reps))
+    return float(np.median(a)), float(np.median(b))
+
+
+def measure_c3(reps=5, mer=False):
     cfg, F = fr.config_C3(), 4096
     dev = torch.device("cuda:0")
     plan = fr.make_plan(cfg, ofdm, precision="fp32", device=0)
@@ -126,15 +137,33 @@ def measure_c3(reps=5):
                       "gen_fused_tbs": counted / (ms_fused * 1e-3) / 1e12,
                       "gen_fused_frac": counted / (ms_fused * 1e-3) / 1e12 / PEAK_TBS,
                       "floor_ms": counted / (PEAK_TBS * 1e12) * 1e3}}
+    if mer:
+        skip = cfg.Nfft + cfg.T_guard
+        off, on = ab_timed(lambda: plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, **imp),
+                           lambda: plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, want_mer=True, mer_skip=skip, **imp),
+                           reps)
+        rm = plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, want_mer=True, mer_skip=skip, **imp)
+        gen = plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev, **imp)
+        rx_off, rx_on = ab_timed(lambda: ofdm.rx_chain_task4(plan, gen["rx"], 1, 1, 1, ref_bits_packed=gen["packed"]),
+                                 lambda: ofdm.rx_chain_task4(plan, gen["rx"], 1, 1, 1, ref_bits_packed=gen["packed"],
+                                                             want_mer=True, mer_skip=skip), reps)
+        del gen
+        torch.cuda.empty_cache()
+        r["mer"] = {"mer_skip": skip, "sweep_off_ms": off, "sweep_on_ms": on, "sweep_on_over_off": on / off,
+                    "sweep_on_sym_per_s": nsym / on * 1e3, "rx_off_ms": rx_off, "rx_on_ms": rx_on,
+                    "rx_on_over_off": rx_on / rx_off, "MER_dB": float(rm["MER_dB"][0].item()),
+                    "errors_equal_off": int(rm["errors"][0].item()) == err}
     plan.close()
     torch.cuda.empty_cache()
     return r
 
 
 def main():
-    names = sys.argv[1:] or ["M", "C4", "C5"]
+    args = sys.argv[1:]
+    mer = "--mer" in args
+    names = [a for a in args if a != "--mer"] or ["M", "C4", "C5"]
     ofdm.init(0)
-    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure_c3() if n == "C3" else measure(n) for n in names]}
+    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure_c3(mer=mer) if n == "C3" else measure(n) for n in names]}
     print(json.dumps(out), flush=True)
 
 
