@@ -293,6 +293,20 @@ int ofdm_tx_frames_fused(ofdm_rx_plan* plan, const void* h, int h_len, double sn
 int ofdm_ber_sweep_task5(ofdm_rx_plan* plan, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
                          int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
                          int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags);
+/* ofdm_ber_sweep_task5 with the MER of every point (T5/Main_model_Task_5.m:282 beside its BER): each frame is decoded by
+ * ofdm_rx_chain_task5_ex, and
+ *   mer_sums_out[n_points][2] (double, optional) = the point's {sum s1, sum s2}: MER_func of the point's RX_IQ concatenated,
+ *   MER = 10 log10(s1 / s2);
+ *   frame_mer_sums_out[n_points][frames_per_point][2] (double, optional): the per-frame sums.
+ * The per-point sums are reduced on the device after the last chunk in a fixed order: bitwise independent of
+ * max_frames_per_chunk.  Both MER outputs NULL is ofdm_ber_sweep_task5; every other output is that call's, bit for bit.
+ * Outputs live where `flags` says; OFDM_DEVICE keeps the no-host-synchronisation rule, MMSE-mode plans the n_points == 1
+ * rule of ofdm_ber_sweep_task5. */
+int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* plan, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                            int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                            int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
+                            double* mer_sums_out /* [n_points][2] */,
+                            double* frame_mer_sums_out /* [n_points][frames_per_point][2] */, int flags);
 /* ofdm_tx_frames_fused with the Task-4 impairments, in the reference order (T4/Main_model_Task_4.m:94-110,:257-267,
  * T5/Noise.m:3-10, T5/add_STO.m, T5/add_CFO.m): per frame f of length len = (Nfft + T_guard) * N_symb
  *   w[j] = x[j] + sigma_f n(j)            the noise of Noise.m, Philox counter (j, 0, frame0 + f, 0) of the SOURCE index j
@@ -395,6 +409,19 @@ int ofdm_rx_plan_last_task4_ms(ofdm_rx_plan* plan, float* ms5);
 int ofdm_rx_chain_task5(ofdm_rx_plan* plan, const void* rx, int64_t n_frames,
                         uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out,
                         void* h_out, int32_t* index_out, int flags);
+/* ofdm_rx_chain_task5 that also returns the sums of MER_func (T5/MER_func.m:3-25; T5/Main_model_Task_5.m:282 reports
+ * MER_func(RX_IQ, Constellation) beside the BER) over each frame's whole RX_IQ = get_payload(equalize_signal(.))(:), the
+ * equalised points of every data carrier and symbol, symbol 1 included:
+ *   mer_sums_out[n_frames][2] (double, where `flags` says) = {sum |ideal|^2, sum |ideal - RX_IQ|^2} with ideal the
+ *   constellation point of the demapper's decision, over the 0-based IQ indices 0 .. nd * N_symb - 1.
+ * MER = 10 log10(s1 / s2); summed over frames it is MER_func of the frames' RX_IQ concatenated.  A frame whose equaliser is
+ * not finite gives NaN sums, as MER_func is NaN on such an RX_IQ.  The sums are taken inside the symbol-stage kernels and
+ * reduced per frame in a fixed order (no atomics): bitwise independent of the batching.  With a DeScrambler the wave-per-frame
+ * path descrambles in a separate pass when MER is asked for; bits and errors are the same.  mer_sums_out = NULL is
+ * ofdm_rx_chain_task5; every other output is that call's, bit for bit. */
+int ofdm_rx_chain_task5_ex(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out /* [n_frames][2] */,
+                           int flags);
 
 #ifdef __cplusplus
 }

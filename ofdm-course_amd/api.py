@@ -820,7 +820,7 @@ class RxPlan:
         return out
 
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
-                  want_frame_errors=False, max_frames_per_chunk=0):
+                  want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False):
         """One device-resident tile of a BER(SNR) sweep (ofdm_ber_sweep_task5): for every SNR of `SNRs` the frames
         frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p]) decoded by rx_chain_task5 on this plan
         (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152).  seeds: one Philox key per point (default: `seed`
@@ -828,7 +828,12 @@ class RxPlan:
         errors count against the payload bits.
         Returns dict(errors=[n_points] int64 bit errors, bits=bits counted per point, frame_errors=[n_points,
         frames_per_point] (with want_frame_errors)); torch tensors on `device` (no host synchronisation) when it is given,
-        numpy arrays otherwise."""
+        numpy arrays otherwise.
+        want_mer (ofdm_ber_sweep_task5_ex): also mer_sums=[n, 2], the MER_func sums of each point's frames (the whole RX_IQ,
+        frames concatenated; T5/Main_model_Task_5.m:282), and MER_dB=[n] (computed on `device` when it is given); with
+        want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2]."""
+        if want_frame_mer and not want_mer:
+            raise OfdmError("ber_sweep: want_frame_mer needs want_mer")
         snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
         n = snr.size
         fpp = int(frames_per_point)
@@ -841,6 +846,8 @@ class RxPlan:
             dev = torch.device(device)
             err = torch.empty((n,), dtype=torch.int64, device=dev)
             fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
+            ms = torch.empty((n, 2), dtype=torch.float64, device=dev) if want_mer else None
+            fm = torch.empty((n, fpp, 2), dtype=torch.float64, device=dev) if want_frame_mer else None
             L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
             flags |= L.OFDM_DEVICE
@@ -848,14 +855,27 @@ class RxPlan:
             L.check(self.lib.ofdm_set_stream(None), "set_stream")
             err = np.empty((n,), dtype=np.uint64)
             fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
+            ms = np.empty((n, 2), dtype=np.float64) if want_mer else None
+            fm = np.empty((n, fpp, 2), dtype=np.float64) if want_frame_mer else None
             ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
         keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
-        L.check(self.lib.ofdm_ber_sweep_task5(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
-                                              sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                              int(max_frames_per_chunk), ptr(err), ptr(fe), flags), "ber_sweep_task5")
+        if not want_mer:
+            L.check(self.lib.ofdm_ber_sweep_task5(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
+                                                  sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                  int(max_frames_per_chunk), ptr(err), ptr(fe), flags), "ber_sweep_task5")
+        else:
+            L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
+                                                     sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                     int(max_frames_per_chunk), ptr(err), ptr(fe), ptr(ms), ptr(fm), flags),
+                    "ber_sweep_task5_ex")
         out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
         if want_frame_errors:
             out["frame_errors"] = fe
+        if want_mer:
+            out["mer_sums"] = ms
+            out["MER_dB"] = _mer_db(ms)
+            if want_frame_mer:
+                out["frame_mer_sums"] = fm
         return out
 
     def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
@@ -960,12 +980,15 @@ class RxPlan:
             pass
 
 
-def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_index=False):
+def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_index=False, want_mer=False):
     """Fused demod -> OMP -> equalise -> payload -> demap -> BER over a batch of frames.
 
     rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
     Returns dict(bits=[n_frames, frame_bytes] uint8 packed MSB-first (frame-major), errors=[n_frames] uint32 or None,
-    H=[N_carrier, n_frames] or None, index=[taps, n_frames] int32 or None)."""
+    H=[N_carrier, n_frames] or None, index=[taps, n_frames] int32 or None).
+    want_mer (ofdm_rx_chain_task5_ex): also mer_sums=[n_frames, 2] float64, the sums {|ideal|^2, |ideal - RX_IQ|^2} of
+    MER_func (T5/MER_func.m:3-25) over each frame's whole RX_IQ (T5/Main_model_Task_5.m:282), and MER_dB=[n_frames] =
+    10 log10(s1 / s2)."""
     call = _Call(rx, f64=plan.f64)
     rows, nfr = _shape2(rx)
     if rows != plan.frame_samples:
@@ -983,9 +1006,15 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
         errors, perr = call._out((nfr,), np.uint32, torch.int32 if call.dev else None)
     H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
     idx, pidx = (call._out((plan.taps, nfr), np.int32, torch.int32 if call.dev else None) if want_index else (None, None))
-    L.check(call.lib.ofdm_rx_chain_task5(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, call.flags),
-            "rx_chain_task5")
-    return dict(bits=bits, errors=errors, H=H, index=idx)
+    if not want_mer:
+        L.check(call.lib.ofdm_rx_chain_task5(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, call.flags),
+                "rx_chain_task5")
+        return dict(bits=bits, errors=errors, H=H, index=idx)
+    mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
+    mer = mer.T
+    L.check(call.lib.ofdm_rx_chain_task5_ex(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, pmer, call.flags),
+            "rx_chain_task5_ex")
+    return dict(bits=bits, errors=errors, H=H, index=idx, mer_sums=mer, MER_dB=_mer_db(mer))
 
 
 def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, ref_bits_packed=None, want_h=False,

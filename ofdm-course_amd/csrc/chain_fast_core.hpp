@@ -478,6 +478,49 @@ __device__ __forceinline__ int slice_symbol(const DemapTable<T>& tab, cx<T> z) {
   else return demap_square<T, BA>(tab, z);
 }
 
+// ---- MER variants of the symbol stages (T5/MER_func.m:19-23 over RX_IQ = every equalised data point of a frame, symbol 1
+// included).  A kernel takes a trailing `Mer... mer` argument pack: empty = the kernel as it always was (same arguments, same
+// instructions), one MerSums = also {sum |ideal|^2, sum |ideal - z|^2} per frame, in double, with ideal the constellation point
+// of the code the kernel's own slicer decided.  Lane partials, then the wave butterfly and the wave partials in index order:
+// no atomics, so a frame's sums do not depend on the grid or the batching.
+struct MerSums {
+  double* sums;                                                        // [n_frames][2]
+};
+template <typename... Mer>
+__device__ __forceinline__ double* mer_sums_of(Mer... mer) {
+  double* p = nullptr;
+  ((p = mer.sums), ...);
+  return p;
+}
+template <typename T>
+__device__ __forceinline__ void mer_add(cx<T> p, cx<T> ye, double& s1, double& s2) {
+  const cx<T> e = p - ye;
+  s1 += (double)p.x * p.x + (double)p.y * p.y;
+  s2 += (double)e.x * e.x + (double)e.y * e.y;
+}
+// 32-entry LDS table of the decided points: kind 1 the axis levels (I at 0..15, Q at 16..31), kind 0 the points interleaved
+template <typename T>
+__device__ __forceinline__ void mer_tab_fill(const DemapTable<T>& tab, T* __restrict__ mt, int tid) {
+  if (tid < 32) {
+    T v;
+    if (tab.kind == 0) v = tid < 16 ? ((tid & 1) ? tab.pts[tid >> 1].y : tab.pts[tid >> 1].x) : T(0);
+    else v = tid < 16 ? tab.axis_i[tid] : tab.axis_q[tid - 16];
+    mt[tid] = v;
+  }
+}
+template <typename T, int BA>
+__device__ __forceinline__ cx<T> mer_ideal(const DemapTable<T>& tab, const T* __restrict__ mt, int code) {
+  if constexpr (BA >= 2) return mk<T>(mt[code >> BA], mt[16 + (code & ((1 << BA) - 1))]);
+  else if (tab.kind == 0) return mk<T>(mt[2 * code], mt[2 * code + 1]);
+  else return mk<T>(mt[code >> tab.bits_per_axis], mt[16 + (code & ((1 << tab.bits_per_axis) - 1))]);
+}
+__device__ __forceinline__ void mer_wave_sum(double& s1, double& s2) {
+  for (int off = 32; off > 0; off >>= 1) {
+    s1 += __shfl_xor(s1, off, 64);
+    s2 += __shfl_xor(s2, off, 64);
+  }
+}
+
 // Per-frame DeScrambler of the fused receivers (T5/DeScrambler.m:8-13 with the register reset per frame,
 // T5/Main_model_Task_5.m:257-274): the register holds the last received bits, newest first, and the taps of array_xor pick
 // Register(13), Register(14), so  d[i] = s[i] ^ s[i-13] ^ s[i-14]  with  s[-m] = Register0(m).  On the packed stream (a word
@@ -671,12 +714,12 @@ inline int mmse_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_
 // ofdm_chain_wave.hip: the symbol stage with one wavefront per frame (Nfft 2048, fp32, N_carrier <= 512)
 bool chain_wave_supported(const FastPlanView& pv);
 int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
-                           const void* ref, void* errs, void* h_out, void* idx_out);
+                           const void* ref, void* errs, void* h_out, void* idx_out, double* mer = nullptr /* MER variant */);
 
 // ofdm_chain_coop.hip: the symbol stage for Nfft 8192 (fp32, N_carrier <= 2048) in one pass over the samples
 bool chain_coop_supported(const FastPlanView& pv);
 int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
-                           const void* ref, void* errs, void* h_out, void* idx_out);
+                           const void* ref, void* errs, void* h_out, void* idx_out, double* mer = nullptr /* MER variant */);
 
 // ofdm_chain_pilot.hip: symbol-1 transform + OMP of every frame in one launch (comb pilots, taps <= OMP_RT)
 template <typename T>

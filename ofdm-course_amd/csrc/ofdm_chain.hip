@@ -103,14 +103,17 @@ static void chain_layout(ChainParams<T>& P, int nfft, int bps) {
   (void)bps;
 }
 
-template <typename T, int N>
+// Mer (MerSums, chain_fast_core.hpp): the MER variant -- the sums of MER_func.m:19-23 over the frame's data points in double,
+// reduced over the frame's group by group_sum (fixed order).  An empty Mer is the kernel as it always was.
+template <typename T, int N, typename... Mer>
 __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams<T> P, const cx<T>* __restrict__ rx,
                                                                      int64_t n_frames,
                                                                      uint32_t* __restrict__ bits_out,
                                                                      const uint32_t* __restrict__ ref_bits,
                                                                      uint32_t* __restrict__ errors_out,
                                                                      cx<T>* __restrict__ h_out,
-                                                                     int32_t* __restrict__ index_out) {
+                                                                     int32_t* __restrict__ index_out, Mer... mer) {
+  constexpr bool MER = sizeof...(Mer) == 1;
   constexpr int TPX = N / 8;
   constexpr int FPW = fft_xforms_per_wg(N);
   constexpr int WGW = fft_wg_threads(N) / 64;
@@ -135,6 +138,13 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
   const int ldg = P.taps;
   const int L = N + P.t_guard;
   const cx<T>* frx = rx + (live ? frame : 0) * (int64_t)L * P.n_symb;
+  double* const mer_out = mer_sums_of(mer...);
+  const T* mt = nullptr;                                               // MER: the decided points (mer_ideal)
+  if constexpr (MER) {
+    __shared__ T mer_tab[32];
+    mer_tab_fill<T>(P.tab, mer_tab, threadIdx.x);                      // (read after the barriers of symbol 1)
+    mt = mer_tab;
+  }
 
   // ================= symbol 1: demodulate, pilots, OMP ==========================================
   cx<T> v[8];
@@ -275,6 +285,7 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
 
   // ================= all symbols: equalise, payload, demap =======================================
   const int bps = P.tab.bps;
+  double s1 = 0, s2 = 0;                                               // MER sums of this thread's points
   for (int s = 0; s < P.n_symb; ++s) {
     if (s > 0) {
       const cx<T>* src = frx + (int64_t)s * L + P.t_guard;
@@ -287,7 +298,12 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
       const int k = j + e * TPX;
       if (k < P.n_carrier) {
         const int d = P.drole[k];
-        if (d >= 0) codes[s * P.nd + d] = (uint8_t)demap_decide(P.tab, v[e] * geq[e]);
+        if (d >= 0) {
+          const cx<T> z = v[e] * geq[e];
+          const int code = demap_decide(P.tab, z);
+          codes[s * P.nd + d] = (uint8_t)code;
+          if constexpr (MER) mer_add(mer_ideal<T, 0>(P.tab, mt, code), z, s1, s2);
+        }
       }
     }
   }
@@ -315,6 +331,11 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
   if (ref_bits && errors_out) {
     const double tot = group_sum<TPX>((double)err, sh_sum);
     if (live && j == 0) errors_out[frame] = (uint32_t)tot;
+  }
+  if constexpr (MER) {
+    s1 = group_sum<TPX>(s1, sh_sum);
+    s2 = group_sum<TPX>(s2, sh_sum);
+    if (live && j == 0) *(double2*)(mer_out + 2 * frame) = make_double2(s1, s2);
   }
 }
 
@@ -380,9 +401,9 @@ int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t*
                         int m_pad, std::vector<c64>& wt);                                  // ofdm_chain_mmse.hip
 bool chain_split_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb, bool f64);   // ofdm_chain_split.hip
 int chain_split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                    const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0);
+                    const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0, double* mer);
 int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                   const void* ref, void* errs, void* h_out, void* idx_out);
+                   const void* ref, void* errs, void* h_out, void* idx_out, double* mer);
 }  // namespace ofdm
 
 constexpr size_t GENERIC_LDS_LIMIT = 158 * 1024;
@@ -402,7 +423,7 @@ static size_t generic_lds_bytes(const ofdm_rx_plan* pl) {
 
 template <typename T, int N>
 static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                        const void* ref, void* errs, void* h_out, void* idx_out) {
+                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   ChainParams<T> P;
   P.n_symb = pl->n_symb; P.t_guard = pl->t_guard; P.n_carrier = pl->n_carrier; P.np = pl->np; P.nd = pl->nd;
   P.k_atoms = pl->k_atoms; P.taps = pl->taps;
@@ -415,6 +436,13 @@ static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, 
   chain_layout<T>(P, N, pl->bps);
   const size_t dyn = (size_t)P.group_bytes * FPW;
   OFDM_ARG(dyn <= GENERIC_LDS_LIMIT, "rx_chain_task5: configuration needs %zu bytes of LDS (limit 158 KiB; use fp32 or a smaller frame)", dyn);
+  if (mer) {                                                           // the MER variant
+    OFDM_HIP(hipFuncSetAttribute((const void*)rx_chain_kernel<T, N, MerSums>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    hipLaunchKernelGGL((rx_chain_kernel<T, N, MerSums>), dim3(cdiv_u(n_frames, FPW)), dim3(fft_wg_threads(N)), dyn, ctx().stream,
+                       P, (const cx<T>*)rx, n_frames, (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs,
+                       (cx<T>*)h_out, (int32_t*)idx_out, MerSums{mer});
+    return check_launch("rx_chain_kernel");
+  }
   OFDM_HIP(hipFuncSetAttribute((const void*)rx_chain_kernel<T, N>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
   hipLaunchKernelGGL((rx_chain_kernel<T, N>), dim3(cdiv_u(n_frames, FPW)), dim3(fft_wg_threads(N)), dyn, ctx().stream,
                      P, (const cx<T>*)rx, n_frames, (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs,
@@ -652,8 +680,8 @@ int ofdm_rx_plan_last_task4_ms(ofdm_rx_plan* pl, float* ms5) {
 
 int64_t ofdm_rx_plan_frame_bytes(const ofdm_rx_plan* pl) { return pl ? (int64_t)pl->frame_words * 4 : 0; }
 
-int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out,
-                        const uint8_t* ref_bits, uint32_t* errors_out, void* h_out, int32_t* index_out, int flags) {
+int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && rx && n_frames >= 0, "rx_chain_task5: bad arguments");
   OFDM_PLAN_DEVICE(pl);
@@ -672,6 +700,8 @@ int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint
   OFDM_TRY(st.out(errors_out, sizeof(uint32_t) * n_frames, &derr));
   OFDM_TRY(st.out(h_out, cs * (size_t)pl->n_carrier * n_frames, &dh));
   OFDM_TRY(st.out(index_out, sizeof(int32_t) * (size_t)pl->taps * n_frames, &didx));
+  void* dmer;
+  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_frames, &dmer));
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
   const bool fast = pl->pilots_in_band &&
@@ -682,15 +712,16 @@ int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint
   if (!fast && pl->pilots_in_band &&
       chain_split_supported(pl->nfft, pl->n_carrier, pl->taps, pl->bps, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0))
     split = pl->nfft > 4096 || pl->d_wt != nullptr || generic_lds_bytes(pl) > GENERIC_LDS_LIMIT;
-  // DeScrambler of the plan: fused into the pack stage of the wave-per-frame symbol kernel; every other path hands its raw
-  // decisions to descr_pass_kernel (the stages themselves then neither compare nor count)
+  // DeScrambler of the plan: fused into the pack stage of the wave-per-frame symbol kernel; every other path -- and the wave
+  // kernel's MER variant -- hands its raw decisions to descr_pass_kernel (the stages themselves then neither compare nor count)
   void* craw = nullptr;
   bool descr_pass = false;
+  double* mer = (double*)dmer;
   if (fast || split) {
     FastPlanView pv;
     make_plan_view(pl, pv);
     pl->last_fast = 1;
-    descr_pass = (pl->descr & DESCR_ON) && !(fast && chain_wave_supported(pv));
+    descr_pass = (pl->descr & DESCR_ON) && (mer || !(fast && chain_wave_supported(pv)));
     if (descr_pass) {
       OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
       pv.descr = 0;
@@ -698,8 +729,8 @@ int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint
     void* cb = descr_pass ? craw : dbits;
     const void* cr = descr_pass ? nullptr : dref;
     void* ce = descr_pass ? nullptr : derr;
-    if (fast) OFDM_TRY(chain_fast_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx));
-    else OFDM_TRY(chain_split_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, (const int32_t*)pl->d_pc0));
+    if (fast) OFDM_TRY(chain_fast_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, mer));
+    else OFDM_TRY(chain_split_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, (const int32_t*)pl->d_pc0, mer));
     if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
     return st.finish();
   }
@@ -714,14 +745,19 @@ int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint
     const void* cr = descr_pass ? nullptr : dref;
     void* ce = descr_pass ? nullptr : derr;
 #define CALL(NN)                                                                                        \
-  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx)));       \
-  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx)));
+  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer)));  \
+  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer)));
     OFDM_FFT_DISPATCH(pl->nfft, CALL)
 #undef CALL
   }
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[3], ctx().stream));
   return st.finish();
+}
+
+int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out,
+                        const uint8_t* ref_bits, uint32_t* errors_out, void* h_out, int32_t* index_out, int flags) {
+  return ofdm_rx_chain_task5_ex(pl, rx, n_frames, bits_out, ref_bits, errors_out, h_out, index_out, nullptr, flags);
 }
 
 }  // extern "C"

@@ -52,13 +52,17 @@ __device__ __forceinline__ cx<float> cp_w32(int m) {
   }
 }
 
-template <int BA, bool HEXT>
+// Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the lane decides, the
+// wave butterfly, the four wave partials in index order.  An empty Mer is the kernel as it always was.
+template <int BA, bool HEXT, typename... Mer>
 __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<float> P, unsigned codes_bytes,
                                                                   const cx<float>* __restrict__ rx, int64_t n_frames,
                                                                   uint32_t* __restrict__ bits_out, const uint32_t* __restrict__ ref_bits,
                                                                   uint32_t* __restrict__ errors_out, cx<float>* __restrict__ h_out,
-                                                                  int32_t* __restrict__ index_out, DemapTable<float> tab) {
+                                                                  int32_t* __restrict__ index_out, DemapTable<float> tab,
+                                                                  Mer... mer) {
   using T = float;
+  constexpr bool MER = sizeof...(Mer) == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int tap_i[FAST_MAXT];
   const int lane = threadIdx.x & 63;
@@ -97,6 +101,16 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
   for (int j = 0; j < 8; ++j) wq[j] = P.tw[512 * wave + lane + 64 * j];
 #pragma unroll
   for (int kb = 1; kb < 4; ++kb) wkb[kb - 1] = P.tw[(32 * lane * kb) & (CP_N - 1)];
+  double* const mer_out = mer_sums_of(mer...);
+  const T* mt = nullptr;                                               // MER: the decided points (mer_ideal)
+  double* mw = nullptr;                                                // MER: the wave partials of a frame [4][2]
+  if constexpr (MER) {
+    __shared__ T mer_tab[32];
+    __shared__ double mer_w[CP_R][2];
+    mer_tab_fill<T>(tab, mer_tab, threadIdx.x);
+    mt = mer_tab;
+    mw = &mer_w[0][0];
+  }
   __syncthreads();
   bool any_data = false;
 #pragma unroll
@@ -225,10 +239,16 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
       __syncthreads();                                                 // hbuf (= exchange slot 0) is free again
     }
     // ---- symbol 1 from the stash of the pilot pass -> codes slot 0
+    double s1 = 0, s2 = 0;                                             // MER sums of this lane's points
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const int d = dd_of(t);
-      if (d >= 0) codes0[d] = (uint8_t)slice_symbol<T, BA>(tab, P.stash[f * nc + kk_of(t)] * geq[t]);
+      if (d >= 0) {
+        const cx<T> z = P.stash[f * nc + kk_of(t)] * geq[t];
+        const int code = slice_symbol<T, BA>(tab, z);
+        codes0[d] = (uint8_t)code;
+        if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+      }
     }
     unsigned err = 0;
     auto pack = [&](int sy) __attribute__((always_inline)) {          // wavefront 0 only
@@ -267,7 +287,12 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
         uint8_t* const cslot = codes0 + (sy & 1) * codes_bytes;
         transform(v, [&](int t, cx<T> X) {
           const int d = dd_of(t);
-          if (d >= 0) cslot[d] = (uint8_t)slice_symbol<T, BA>(tab, X * geq[t]);
+          if (d >= 0) {
+            const cx<T> z = X * geq[t];
+            const int code = slice_symbol<T, BA>(tab, z);
+            cslot[d] = (uint8_t)code;
+            if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+          }
         }, [&](int kb) { if (fetch) load_quarter(nsrc, kb); });
       }
       __syncthreads();                                                 // E: codes of symbol sy complete, exchange free
@@ -279,6 +304,13 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
     if (wave == 0 && ref_bits && errors_out) {
       for (int off = 32; off > 0; off >>= 1) err += __shfl_xor(err, off, 64);
       if (lane == 0) errors_out[f] = err;
+    }
+    if constexpr (MER) {                                               // (the loop's first barrier guards mer_w's reuse)
+      mer_wave_sum(s1, s2);
+      if (lane == 0) { mw[2 * wave] = s1; mw[2 * wave + 1] = s2; }
+      __syncthreads();
+      if (threadIdx.x == 0)
+        *(double2*)(mer_out + 2 * f) = make_double2(((mw[0] + mw[2]) + mw[4]) + mw[6], ((mw[1] + mw[3]) + mw[5]) + mw[7]);
     }
   }
 }
@@ -294,23 +326,26 @@ bool chain_coop_supported(const FastPlanView& pv) {
 }
 
 int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
-                           const void* ref, void* errs, void* h_out, void* idx_out) {
+                           const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   const unsigned codes_bytes = (unsigned)((pv.nd + 63) & ~31);
   const unsigned lds = CP_OFF_CODES + 2 * codes_bytes;
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const bool mmse = pv.d_wt != nullptr;
-  auto launch = [&](auto kern) -> int {
+  auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 256, lds);
     if (const char* e = getenv("OFDM_COOP_WG_PER_CU")) per_cu = std::max(1, atoi(e));
     const unsigned grid = (unsigned)std::min<int64_t>(n_frames, (int64_t)ctx().num_cu * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, ctx().stream, P, codes_bytes, (const cx<float>*)rx, n_frames, (uint32_t*)bits,
-                       (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab);
+                       (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab, mer_arg...);
     return OFDM_OK;
   };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-#define COOP_CASE(BAV)                                                     \
-  if (mmse) OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, true>));          \
+#define COOP_CASE(BAV)                                                                               \
+  if (mer) {                                                                                         \
+    if (mmse) OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, true, MerSums>, MerSums{mer}));           \
+    else OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, false, MerSums>, MerSums{mer}));               \
+  } else if (mmse) OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, true>));                            \
   else OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, false>))
   switch (ba) {
     case 2: COOP_CASE(2); break;

@@ -233,14 +233,17 @@ __global__ __launch_bounds__(256) void omp_batch_kernel(FastParams<T> P, OmpLayo
 // HEXT: the channel estimate of every frame comes from P.h_in (MMSE mode) instead of the OMP taps.
 // (second launch bound = wavefronts per SIMD the register allocation must allow: 5 <-> 96 VGPRs, i.e. five resident
 // 256-thread workgroups per CU for the pruned Nfft <= 2048 instantiations, which is where the benchmark runs)
-template <typename T, int NW, bool PRUNE2, int BA, bool HEXT = false>
+// Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the lane decides, the
+// wave butterfly, the NW wave partials in index order.  An empty Mer is the kernel as it always was.
+template <typename T, int NW, bool PRUNE2, int BA, bool HEXT = false, typename... Mer>
 __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 4) : 3) : 2) void rx_symbols_kernel(FastParams<T> P, const cx<T>* __restrict__ rx,
                                                              int64_t n_frames, uint32_t* __restrict__ bits_out,
                                                              const uint32_t* __restrict__ ref_bits,
                                                              uint32_t* __restrict__ errors_out,
                                                              cx<T>* __restrict__ h_out, int32_t* __restrict__ index_out,
-                                                             DemapTable<T> tab) {
+                                                             DemapTable<T> tab, Mer... mer) {
   constexpr int N = 512 * NW;
+  constexpr bool MER = sizeof...(Mer) == 1;
   constexpr int NOUT = PRUNE2 ? 2 : 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cx<T>* lwv = (cx<T>*)smem;                                           // [NW][WAVE_LDS_ELEMS]
@@ -275,6 +278,16 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
   const int64_t frame_bits = (int64_t)nd * P.n_symb * bps;
   const int n_codes = nd * P.n_symb;
   if (gid < 32) codes[((n_codes + 31) & ~31) - 32 + gid] = 0;      // zero padding of the last 32-symbol group
+  double* const mer_out = mer_sums_of(mer...);
+  const T* mt = nullptr;                                               // MER: the decided points (mer_ideal)
+  double* mw = nullptr;                                                // MER: the wave partials of a frame [NW][2]
+  if constexpr (MER) {
+    __shared__ T mer_tab[32];
+    __shared__ double mer_w[NW][2];
+    mer_tab_fill<T>(tab, mer_tab, gid);
+    mt = mer_tab;
+    mw = &mer_w[0][0];
+  }
   __syncthreads();
   cx<T> v[8], nx[8];
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
@@ -326,9 +339,15 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
       }
     }
     // ---- symbol 1 from the stash
+    double s1 = 0, s2 = 0;                                             // MER sums of this thread's points
 #pragma unroll
     for (int t = 0; t < NOUT; ++t)
-      if (dd[t] >= 0) codes[dd[t]] = (uint8_t)slice_symbol<T, BA>(tab, P.stash[f * P.n_carrier + kk[t]] * geq[t]);
+      if (dd[t] >= 0) {
+        const cx<T> z = P.stash[f * P.n_carrier + kk[t]] * geq[t];
+        const int code = slice_symbol<T, BA>(tab, z);
+        codes[dd[t]] = (uint8_t)code;
+        if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+      }
     // ---- symbols 2..S: the next symbol's samples are in flight while this one is transformed.  Measured and
     //      rejected: alternating two register sets instead of copying (-1 workgroup of occupancy), two symbols in
     //      flight (119 VGPRs, 11 % slower) -- the kernel is not HBM-latency bound.
@@ -347,8 +366,17 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
         wave_fft512<T, PRUNE2, true, true>(v, lane, twb, twl, lwv + wave * WAVE_LDS_ELEMS);
 #pragma unroll
         for (int t = 0; t < NOUT; ++t)
-          if (dd[t] >= 0) codes[s * nd + dd[t]] = (uint8_t)slice_symbol<T, BA>(tab, v[t] * geq[t]);
+          if (dd[t] >= 0) {
+            const cx<T> z = v[t] * geq[t];
+            const int code = slice_symbol<T, BA>(tab, z);
+            codes[s * nd + dd[t]] = (uint8_t)code;
+            if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+          }
       }
+    }
+    if constexpr (MER) {
+      mer_wave_sum(s1, s2);
+      if (lane == 0) { mw[2 * wave] = s1; mw[2 * wave + 1] = s2; }
     }
     __syncthreads();
     // ---- pack (bit i of the frame -> byte i/8, bit 7-i%8) + BER numerator.  A group of 32 decided
@@ -361,6 +389,13 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
       if (err) atomicAdd(&sh_err, err);
       __syncthreads();
       if (gid == 0) errors_out[f] = sh_err;
+    }
+    if constexpr (MER) {
+      if (gid == 0) {
+        double a = mw[0], b = mw[1];
+        for (int w2 = 1; w2 < NW; ++w2) { a += mw[2 * w2]; b += mw[2 * w2 + 1]; }
+        *(double2*)(mer_out + 2 * f) = make_double2(a, b);
+      }
     }
     __syncthreads();                     // codes / sh_err are reused by the next frame
   }
@@ -445,7 +480,7 @@ template int omp_batch_run<double>(const FastParams<double>&, int64_t);
 
 template <typename T, int NW, bool PRUNE2>
 static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                       const void* ref, void* errs, void* h_out, void* idx_out) {
+                       const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   FastParams<T> P;
   OFDM_TRY(fast_params_prepare<T>(pv, tw, n_frames, P));
   const bool mmse = pv.d_wt != nullptr;
@@ -478,8 +513,9 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
   if (pv.ev && !fused) OFDM_HIP(hipEventRecord(pv.ev[2], st));
   // kernel 3
   if constexpr (std::is_same<T, float>::value && NW == 4 && PRUNE2) {
-    if (chain_wave_supported(pv)) {                  // one wavefront per frame, no workgroup barrier (ofdm_chain_wave.hip)
-      OFDM_TRY(chain_wave_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out));
+    // (a MER request under the exact-slicer switch takes the four-wavefront MER variant below)
+    if (chain_wave_supported(pv) && !(mer && getenv("OFDM_WAVE_EXACT_SLICER"))) {   // one wavefront per frame (ofdm_chain_wave.hip)
+      OFDM_TRY(chain_wave_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
       return OFDM_OK;
     }
@@ -491,16 +527,28 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
     OFDM_ARG(dyn <= 150 * 1024, "rx_chain_task5: symbol stage needs %zu bytes of LDS", dyn);
     // persistent grid = CUs x resident workgroups per CU (from the occupancy API: registers + LDS);
     // workgroups are independent, so an optimistic answer only queues a few of them.
-    auto launch = [&](auto kern) -> int {
+    auto launch = [&](auto kern, auto... mer_arg) -> int {          // (mer_arg: MerSums for a MER variant)
       int per_cu = resident_blocks_per_cu((const void*)kern, 64 * NW, dyn);
       if (const char* e = getenv("OFDM_FAST_WG_PER_CU")) per_cu = std::max(1, atoi(e));
       const unsigned grid = (unsigned)std::min<int64_t>(n_frames, (int64_t)ncu * per_cu);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * NW), dyn, st, P, (const cx<T>*)rx, n_frames, (uint32_t*)bits,
-                         (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab);
+                         (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, mer_arg...);
       return OFDM_OK;
     };
     const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-    if (mmse) {
+    if (mer) {
+      const MerSums ms{mer};
+      switch (ba) {
+        case 2: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 2, true, MerSums>, ms)
+                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 2, false, MerSums>, ms)); break;
+        case 3: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 3, true, MerSums>, ms)
+                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 3, false, MerSums>, ms)); break;
+        case 4: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 4, true, MerSums>, ms)
+                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 4, false, MerSums>, ms)); break;
+        default: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 0, true, MerSums>, ms)
+                               : launch(rx_symbols_kernel<T, NW, PRUNE2, 0, false, MerSums>, ms)); break;
+      }
+    } else if (mmse) {
       switch (ba) {
         case 2: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 2, true>)); break;
         case 3: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 3, true>)); break;
@@ -523,12 +571,12 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
 
 template <typename T>
 static int dispatch_fast(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                         const void* ref, void* errs, void* h_out, void* idx_out) {
+                         const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   const int nw = pv.nfft / 512;
   const bool prune = pv.n_carrier <= 128 * nw;
 #define FAST_CALL(NWV)                                                                                       \
-  return prune ? launch_fast<T, NWV, true>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out)            \
-               : launch_fast<T, NWV, false>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out)
+  return prune ? launch_fast<T, NWV, true>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer)       \
+               : launch_fast<T, NWV, false>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer)
   switch (nw) {
     case 1: FAST_CALL(1);
     case 2: FAST_CALL(2);
@@ -541,9 +589,9 @@ static int dispatch_fast(const FastPlanView& pv, const void* tw, const void* rx,
 }
 
 int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                   const void* ref, void* errs, void* h_out, void* idx_out) {
-  if (pv.f64) return dispatch_fast<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out);
-  return dispatch_fast<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out);
+                   const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
+  if (pv.f64) return dispatch_fast<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
+  return dispatch_fast<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
 }
 
 }  // namespace ofdm

@@ -45,13 +45,6 @@ struct MerOut {
   double* sums;                                                        // [n_frames][2]
 };
 
-template <typename T>
-__device__ __forceinline__ void mer_add(cx<T> p, cx<T> ye, double& s1, double& s2) {
-  const cx<T> e = p - ye;
-  s1 += (double)p.x * p.x + (double)p.y * p.y;
-  s2 += (double)e.x * e.x + (double)e.y * e.y;
-}
-
 template <typename T, int BA, bool HEXT, bool VEC = false, typename... Mer>
 __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft, const cx<T>* __restrict__ xk,
                                                        int x_stride /* rows per symbol column of xk */, int64_t n_frames, uint32_t* __restrict__ bits_out,
@@ -407,15 +400,18 @@ static int demod_keep8192_run(const void* y, void* x, int64_t n_symb, int t_guar
 // (2k', 2k'+1 for two k'), multiplies by its 1 ./ H (synthesised once per frame from the OMP taps, or read in MMSE mode), slices,
 // and the frame's decisions are packed and counted from LDS -- rx_symbols_kernel's frame loop around the 8192-point transform.
 // Sixteen wavefronts per CU (two 512-thread workgroups, 128 VGPRs) against the eight of rx_symbols_coop4_kernel (250 VGPRs, 79 KB).
-template <int BA, bool HEXT>
+// Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the thread decides, the
+// wave butterfly, the eight wave partials in index order.  An empty Mer is the kernel as it always was.
+template <int BA, bool HEXT, typename... Mer>
 __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float> P, const cx<float>* __restrict__ rx,
                                                                const cx<float>* __restrict__ tw4096, const cx<float>* __restrict__ tw8192,
                                                                int64_t n_frames, uint32_t* __restrict__ bits_out,
                                                                const uint32_t* __restrict__ ref_bits, uint32_t* __restrict__ errors_out,
                                                                cx<float>* __restrict__ h_out, int32_t* __restrict__ index_out,
-                                                               DemapTable<float> tab) {
+                                                               DemapTable<float> tab, Mer... mer) {
   using T = float;
   constexpr int NW = 8, N = 8192, NOUT = 2;
+  constexpr bool MER = sizeof...(Mer) == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cx<T>* lwv = (cx<T>*)smem;                                   // [NW][WAVE_LDS_ELEMS]
   cx<T>* const ex = lwv;
@@ -451,6 +447,16 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
   const int taps = P.taps, bps = BA > 0 ? 2 * BA : P.bps, nd = P.nd;
   const int n_codes = nd * P.n_symb;
   if (gid < 32) codes[((n_codes + 31) & ~31) - 32 + gid] = 0;      // zero padding of the last 32-symbol group
+  double* const mer_out = mer_sums_of(mer...);
+  const T* mt = nullptr;                                           // MER: the decided points (mer_ideal)
+  double* mw = nullptr;                                            // MER: the wave partials of a frame [NW][2]
+  if constexpr (MER) {
+    __shared__ T mer_tab[32];
+    __shared__ double mer_w[NW][2];
+    mer_tab_fill<T>(tab, mer_tab, gid);
+    mt = mer_tab;
+    mw = &mer_w[0][0];
+  }
   __syncthreads();
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     const cx<T>* frx = rx + f * (int64_t)Lsym * P.n_symb;
@@ -489,9 +495,15 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
       }
     }
     // ---- symbol 1 from the stash
+    double s1 = 0, s2 = 0;                                       // MER sums of this thread's points
 #pragma unroll
     for (int t = 0; t < 2 * NOUT; ++t)
-      if (dd[t] >= 0) codes[dd[t]] = (uint8_t)slice_symbol<T, BA>(tab, P.stash[f * P.n_carrier + kc[t]] * geq[t]);
+      if (dd[t] >= 0) {
+        const cx<T> z = P.stash[f * P.n_carrier + kc[t]] * geq[t];
+        const int code = slice_symbol<T, BA>(tab, z);
+        codes[dd[t]] = (uint8_t)code;
+        if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+      }
     // ---- symbols 2..S
     for (int s = 1; s < P.n_symb; ++s) {
       const cx<T>* src = frx + (int64_t)s * Lsym + P.t_guard;
@@ -514,7 +526,12 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
         wave_fft512<T, true>(a, lane, twb, twl, lwv + wave * WAVE_LDS_ELEMS);
 #pragma unroll
         for (int t = 0; t < NOUT; ++t)
-          if (dd[2 * t] >= 0) codes[s * nd + dd[2 * t]] = (uint8_t)slice_symbol<T, BA>(tab, a[t] * geq[2 * t]);
+          if (dd[2 * t] >= 0) {
+            const cx<T> z = a[t] * geq[2 * t];
+            const int code = slice_symbol<T, BA>(tab, z);
+            codes[s * nd + dd[2 * t]] = (uint8_t)code;
+            if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+          }
       }
       // odd bins
       dif_stage<T, NW>(b, dt);
@@ -526,8 +543,17 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
         wave_fft512<T, true>(b, lane, twb, twl, lwv + wave * WAVE_LDS_ELEMS);
 #pragma unroll
         for (int t = 0; t < NOUT; ++t)
-          if (dd[2 * t + 1] >= 0) codes[s * nd + dd[2 * t + 1]] = (uint8_t)slice_symbol<T, BA>(tab, b[t] * geq[2 * t + 1]);
+          if (dd[2 * t + 1] >= 0) {
+            const cx<T> z = b[t] * geq[2 * t + 1];
+            const int code = slice_symbol<T, BA>(tab, z);
+            codes[s * nd + dd[2 * t + 1]] = (uint8_t)code;
+            if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+          }
       }
+    }
+    if constexpr (MER) {
+      mer_wave_sum(s1, s2);
+      if (lane == 0) { mw[2 * wave] = s1; mw[2 * wave + 1] = s2; }
     }
     __syncthreads();
     const unsigned int err = pack_frame<2 * BA>(codes, n_codes, bps, P.frame_words,
@@ -537,6 +563,13 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
       if (err) atomicAdd(&sh_err, err);
       __syncthreads();
       if (gid == 0) errors_out[f] = sh_err;
+    }
+    if constexpr (MER) {
+      if (gid == 0) {
+        double a1 = mw[0], a2 = mw[1];
+        for (int w8 = 1; w8 < NW; ++w8) { a1 += mw[2 * w8]; a2 += mw[2 * w8 + 1]; }
+        *(double2*)(mer_out + 2 * f) = make_double2(a1, a2);
+      }
     }
     __syncthreads();                     // codes / sh_err are reused by the next frame
   }
@@ -551,7 +584,7 @@ static bool chain_r2_supported(const FastPlanView& pv) {
   return r2_lds_bytes(pv) <= 78u * 1024;                       // two workgroups per CU
 }
 static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
-                                const void* ref, void* errs, void* h_out, void* idx_out) {
+                                const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   const size_t lds = r2_lds_bytes(pv);
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
@@ -559,17 +592,21 @@ static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>&
   OFDM_TRY(get_twiddles(4096, false, &tw4));
   OFDM_TRY(get_twiddles(8192, false, &tw8));
   const bool mmse = pv.d_wt != nullptr;
-  auto launch = [&](auto kern) -> int {
+  auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 512, lds);
     if (const char* e = getenv("OFDM_R2_WG_PER_CU")) per_cu = std::max(1, atoi(e));
     const unsigned grid = (unsigned)std::min<int64_t>(n_frames, (int64_t)ctx().num_cu * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, ctx().stream, P, (const cx<float>*)rx, (const cx<float>*)tw4, (const cx<float>*)tw8,
-                       n_frames, (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab);
+                       n_frames, (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab,
+                       mer_arg...);
     return OFDM_OK;
   };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-#define R2_CASE(BAV)                                                   \
-  if (mmse) OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, true>));         \
+#define R2_CASE(BAV)                                                                              \
+  if (mer) {                                                                                      \
+    if (mmse) OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, true, MerSums>, MerSums{mer}));           \
+    else OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, false, MerSums>, MerSums{mer}));               \
+  } else if (mmse) OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, true>));                            \
   else OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, false>))
   switch (ba) {
     case 2: R2_CASE(2); break;
@@ -654,7 +691,7 @@ template int eq_demap_run<double>(const FastPlanView&, const FastParams<double>&
 
 template <typename T>
 static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                     const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0) {
+                     const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0, double* mer) {
   FastParams<T> P;
   OFDM_TRY(fast_params_prepare<T>(pv, tw, n_frames, P));
   const bool mmse = pv.d_wt != nullptr;
@@ -673,8 +710,8 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
       if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
       else OFDM_TRY(omp_batch_run<T>(P, n_frames));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
-      if (r2) OFDM_TRY(chain_r2_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out));
-      else OFDM_TRY(chain_coop_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out));
+      if (r2) OFDM_TRY(chain_r2_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
+      else OFDM_TRY(chain_coop_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
       return OFDM_OK;
     }
@@ -712,15 +749,16 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
   else OFDM_TRY(omp_batch_run<T>(P, n_frames));
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
-  OFDM_TRY(eq_demap_run<T>(pv, P, xk, pv.n_carrier, mmse, n_frames, bits, ref, errs, h_out, idx_out, nullptr, 0, 0));
+  OFDM_TRY(eq_demap_run<T>(pv, P, xk, pv.n_carrier, mmse, n_frames, bits, ref, errs, h_out, idx_out, nullptr, 0, 0, 0,
+                           mer));                                      // (+ the MER_func sums of the whole RX_IQ: skip 0)
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
   return OFDM_OK;
 }
 
 int chain_split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                    const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0) {
-  if (pv.f64) return split_run<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, d_pc0);
-  return split_run<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, d_pc0);
+                    const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0, double* mer) {
+  if (pv.f64) return split_run<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, d_pc0, mer);
+  return split_run<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, d_pc0, mer);
 }
 
 }  // namespace ofdm

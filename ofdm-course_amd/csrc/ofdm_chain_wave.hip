@@ -88,15 +88,22 @@ __device__ __forceinline__ int slice_wave(const DemapTable<float>& tab, const fl
   else return slice_symbol<float, BA, true>(tab, z);
 }
 
-template <int BA, bool HEXT, int WPB = WV_WPB, int ABL = 0, bool WBUF = true, int LUT = 2, int SKIP = 0, bool DESCR = false>
-__global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_kernel(FastParams<float> P, WaveLayout lay,
+// Mer (MerSums, chain_fast_core.hpp): the MER variant -- the sums of MER_func.m:19-23 over every data point the kernel decides,
+// lane partials in double, the wave butterfly at the end of a frame, lane 0 stores the frame's pair.  It is built for two
+// workgroups per CU (<= 256 VGPRs): at the 168 of three the four live doubles spilled ~230 registers.  An empty Mer is the
+// kernel as it always was.
+template <int BA, bool HEXT, int WPB = WV_WPB, int ABL = 0, bool WBUF = true, int LUT = 2, int SKIP = 0, bool DESCR = false,
+          typename... Mer>
+__global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) void rx_symbols_wave_kernel(FastParams<float> P, WaveLayout lay,
                                                                   const cx<float>* __restrict__ rx, int64_t n_frames,
                                                                   uint32_t* __restrict__ bits_out,
                                                                   const uint32_t* __restrict__ ref_bits,
                                                                   uint32_t* __restrict__ errors_out,
                                                                   cx<float>* __restrict__ h_out,
-                                                                  int32_t* __restrict__ index_out, DemapTable<float> tab) {
+                                                                  int32_t* __restrict__ index_out, DemapTable<float> tab,
+                                                                  Mer... mer) {
   using T = float;
+  constexpr bool MER = sizeof...(Mer) == 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // Compile-time LDS layout (WV_OFF_*): every address below is one of four per-lane registers (lane8, trl, t1r, t2w) plus
   // an immediate offset of the DS instruction -- run-time table offsets cost a VGPR each, and the kernel has none to spare.
@@ -138,6 +145,13 @@ __global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_ke
   }
   const T* const lut = (const T*)(smem + WV_OFF_LUT);
   if constexpr (BA >= 2) demap_lut_fill<T, BA>(tab, (T*)(smem + WV_OFF_LUT), threadIdx.x);
+  double* const mer_out = mer_sums_of(mer...);
+  const T* mt = nullptr;                                               // MER: the decided points (mer_ideal)
+  if constexpr (MER) {
+    __shared__ T mer_tab[32];
+    mer_tab_fill<T>(tab, mer_tab, threadIdx.x);
+    mt = mer_tab;
+  }
   __syncthreads();                                                     // the only workgroup barrier of the kernel
   // wave-private region: transposes [576 complex] | 64 spare 8-byte slots | codes
   const unsigned wbase = WV_OFF_WAVE + (unsigned)wave * lay.wave_bytes;
@@ -147,6 +161,11 @@ __global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_ke
   auto code_ptr = [&](uint8_t* base, int t) {
     const unsigned d = (*(const unsigned*)(smem + WV_OFF_DD + 512 * (t >> 1) + lane8) >> (16 * (t & 1))) & 0xffffu;
     return d == 0xffffu ? (uint8_t*)(trl + WV_TRASH_OFF) : base + d;
+  };
+  // MER: the decided code and its equalised point, counted when output t holds a data carrier
+  auto mer_take = [&](int t, int code, cx<T> z, double& s1, double& s2) __attribute__((always_inline)) {
+    const unsigned d = (*(const unsigned*)(smem + WV_OFF_DD + 512 * (t >> 1) + lane8) >> (16 * (t & 1))) & 0xffffu;
+    if (d != 0xffffu) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
   };
   // LDS addresses of the two transposes
   cx<T>* const t1w = (cx<T>*)trl;                                                              // + 72 c
@@ -224,10 +243,14 @@ __global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_ke
       }
     }
     // ---- symbol 1 from the stash of the pilot stage
+    double s1 = 0, s2 = 0;                                             // MER sums of this lane's points
 #pragma unroll
-    for (int t = 0; t < 8; ++t)
-      *code_ptr(codes, t) = (uint8_t)slice_wave<BA, LUT>(
-          tab, lut, (kk_of(t) < n_carrier ? P.stash[f * n_carrier + kk_of(t)] : mk<T>(0, 0)) * geq[t]);
+    for (int t = 0; t < 8; ++t) {
+      const cx<T> z = (kk_of(t) < n_carrier ? P.stash[f * n_carrier + kk_of(t)] : mk<T>(0, 0)) * geq[t];
+      const int code = slice_wave<BA, LUT>(tab, lut, z);
+      *code_ptr(codes, t) = (uint8_t)code;
+      if constexpr (MER) mer_take(t, code, z, s1, s2);
+    }
     unsigned err = 0;
     int slot = 1;                                                      // symbols in the codes buffer
     int64_t code0 = 0;                                                 // first code index of the buffer within the frame
@@ -310,8 +333,12 @@ __global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_ke
             wave_sync();
             dft8_first2<T>(u);
 #pragma unroll
-            for (int kb = 0; kb < 2; ++kb)
-              *code_ptr(cslot, 2 * r + kb) = (uint8_t)slice_wave<BA, LUT>(tab, lut, u[kb] * geq[2 * r + kb]);
+            for (int kb = 0; kb < 2; ++kb) {
+              const cx<T> z = u[kb] * geq[2 * r + kb];
+              const int code = slice_wave<BA, LUT>(tab, lut, z);
+              *code_ptr(cslot, 2 * r + kb) = (uint8_t)code;
+              if constexpr (MER) mer_take(2 * r + kb, code, z, s1, s2);
+            }
           }
         }
       }
@@ -354,6 +381,10 @@ __global__ __launch_bounds__(64 * WPB, WPB == 8 ? 4 : 3) void rx_symbols_wave_ke
       for (int off = 32; off > 0; off >>= 1) err += __shfl_xor(err, off, 64);
       if (lane == 0) errors_out[f] = err;
     }
+    if constexpr (MER) {
+      mer_wave_sum(s1, s2);
+      if (lane == 0) *(double2*)(mer_out + 2 * f) = make_double2(s1, s2);
+    }
   };
   // a frame of an odd number of transforms leaves the samples of the next frame in the other layout
   const bool odd = ((n_symb - 1) & 1) != 0;
@@ -395,7 +426,7 @@ bool chain_wave_supported(const FastPlanView& pv) {
 }
 
 int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
-                           const void* ref, void* errs, void* h_out, void* idx_out) {
+                           const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   // two builds of the kernel: 4 wavefronts per workgroup at <= 168 VGPRs (three workgroups = 12 wavefronts per CU) and
   // 8 per workgroup at <= 128 VGPRs (two workgroups = 16 wavefronts per CU)
   const int wpb = WV_WPB;       // (eight wavefronts per workgroup at <= 128 VGPRs, the LUT slicer and the form without look-ahead
@@ -405,13 +436,14 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const bool mmse = pv.d_wt != nullptr;
-  auto launch = [&](auto kern) -> int {
+  auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 64 * wpb, lay.total);
     if (const char* e = getenv("OFDM_WAVE_WG_PER_CU")) per_cu = std::max(1, atoi(e));
     const int64_t want = (n_frames + wpb - 1) / wpb;
     const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx().num_cu * per_cu);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lay.total, ctx().stream, P, lay, (const cx<float>*)rx, n_frames,
-                       (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab);
+                       (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab,
+                       mer_arg...);
     return OFDM_OK;
   };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
@@ -431,7 +463,21 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   else if (skip0) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 1, true>));     \
   else if (skip02) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 5, true>));    \
   else OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 0, true>))
-  if (P.descr & DESCR_ON) {
+  // MER variants (default slicer only; the caller routes MER requests under OFDM_WAVE_EXACT_SLICER and DeScrambler plans
+  // elsewhere): P.descr must be off here, descr_pass_kernel descrambles
+#define WAVE_CASE_M(BAV, HX)                                                                                         \
+  if (skip0) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 1, false, MerSums>, MerSums{mer}));      \
+  else if (skip02) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 5, false, MerSums>, MerSums{mer})); \
+  else OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 0, false, MerSums>, MerSums{mer}))
+  if (mer) {
+    OFDM_ARG(!exact && !(P.descr & DESCR_ON), "rx_chain_task5(wave): no MER variant of the exact-slicer / DeScrambler forms");
+    switch (ba) {
+      case 2: if (mmse) { WAVE_CASE_M(2, true); } else { WAVE_CASE_M(2, false); } break;
+      case 3: if (mmse) { WAVE_CASE_M(3, true); } else { WAVE_CASE_M(3, false); } break;
+      case 4: if (mmse) { WAVE_CASE_M(4, true); } else { WAVE_CASE_M(4, false); } break;
+      default: if (mmse) { WAVE_CASE_M(0, true); } else { WAVE_CASE_M(0, false); } break;
+    }
+  } else if (P.descr & DESCR_ON) {
     OFDM_ARG(!mmse, "rx_chain_task5(wave): the DeScrambler variant exists in OMP mode only");
     switch (ba) {
       case 2: WAVE_CASE_D(2); break;
@@ -461,6 +507,7 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   }
 #undef WAVE_CASE
 #undef WAVE_CASE_D
+#undef WAVE_CASE_M
   return check_launch("rx_symbols_wave_kernel");
 }
 

@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void t4_point_reduce_kernel(const uint32_t* __
   }
 }
 
-// per point p of a Task-4 sweep with MER: the per-frame MER_func sums {s1, s2} of eq_demap_kernel's MER variant -> the
+// per point p of a Task-4 / Task-5 sweep with MER: the per-frame MER_func sums {s1, s2} of the symbol stages' MER variants -> the
 // point's {sum s1, sum s2} (MER_func of the point's RX_IQ concatenated) -- the fixed order of t4_point_reduce_kernel:
 // each thread a fixed stride, a fixed butterfly, the four wave partials paired; bitwise independent of the chunking
 __global__ __launch_bounds__(256) void t4_point_mer_kernel(const double* __restrict__ frame_mer, int64_t frames_per_point,
@@ -572,9 +572,10 @@ extern "C" int ofdm_tx_frames_fused(ofdm_rx_plan* pl, const void* h, int h_len, 
   return st.finish();
 }
 
-extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
-                                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
-                                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags) {
+extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                                       int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                       int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
+                                       double* mer_sums_out, double* frame_mer_sums_out, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && max_frames_per_chunk >= 0 && errors_out,
            "ber_sweep_task5: bad arguments");
@@ -587,14 +588,20 @@ extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, 
   OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
   if (n_points == 0) return OFDM_OK;
   Stage st(flags);
-  void *derr, *dfe;
+  void *derr, *dfe, *dmer, *dfm;
   OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
   OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
+  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_points, &dmer));
+  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * (size_t)(n_points * frames_per_point), &dfm));
+  const bool mer = dmer || dfm;
   if (frames_per_point == 0) {
     OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, ctx().stream));
+    if (dmer) OFDM_HIP(hipMemsetAsync(dmer, 0, sizeof(double) * 2 * (size_t)n_points, ctx().stream));
     return st.finish();
   }
   if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
+  // the per-frame MER sums of every point, reduced once after the last chunk
+  if (mer && !dfm) OFDM_TRY(st.scratch(sizeof(double) * 2 * (size_t)(n_points * frames_per_point), &dfm));
   OFDM_TRY(tx_dict_device(pl));
   const bool scr = scr_reg15 != nullptr;
   const int64_t CH = txf_chunk(pl, scr, true, frames_per_point, max_frames_per_chunk);
@@ -607,14 +614,27 @@ extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, 
     for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
       const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
       OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr));
-      OFDM_TRY(ofdm_rx_chain_task5(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
-                                   (uint32_t*)dfe + p * frames_per_point + c0, nullptr, nullptr, rxflags));
+      const int64_t o = p * frames_per_point + c0;
+      OFDM_TRY(ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref, (uint32_t*)dfe + o, nullptr, nullptr,
+                                      mer ? (double*)dfm + 2 * o : nullptr, rxflags));
     }
   }
   hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)dfe,
                      frames_per_point, (unsigned long long*)derr);
   OFDM_TRY(check_launch("ber_point_reduce_kernel"));
+  if (dmer) {                                                   // the Task-4 sweep's fixed-order reduction of the frame sums
+    hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)dfm,
+                       frames_per_point, (double*)dmer);
+    OFDM_TRY(check_launch("t4_point_mer_kernel"));
+  }
   return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags) {
+  return ofdm_ber_sweep_task5_ex(pl, h, h_len, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15,
+                                 max_frames_per_chunk, errors_out, frame_errors_out, nullptr, nullptr, flags);
 }
 
 extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed,

@@ -16,9 +16,10 @@ batch, the same tile keys); the counters stay in a device tensor and are read on
 frames with a random STO / CFO per frame, through `RxPlan.ber_sweep_task4` (ofdm_ber_sweep_task4), with the same tile keys
 and dealing as --fused.  Per point the JSON adds `status_counts` (frames with receiver status 0, 1, -1, -2) and
 `cfo_abs_err` (the sum of |FreqOffset + IFO - Freq_Shift| over the point's frames).  The integer counters travel in the int64
-all-reduce; the CFO sums in a second, float64 one.  --mer (C3 only) adds per point `MER_dB`, the MER of the point's frames
-(MER_func of RX_IQ(Nfft+T_Guard+1:end) per frame, concatenated; ofdm_ber_sweep_task4_ex): its two MER_func sums travel in the
-float64 all-reduce beside the CFO sums.
+all-reduce; the CFO sums in a second, float64 one.  --mer adds per point `mer_sums` and `MER_dB`, the MER of the point's
+frames: at C3 MER_func of RX_IQ(Nfft+T_Guard+1:end) per frame, concatenated (ofdm_ber_sweep_task4_ex), beside the CFO sums;
+at C5 / M MER_func of each frame's whole RX_IQ (T5/Main_model_Task_5.m:282; ofdm_ber_sweep_task5_ex with --fused,
+rx_chain_task5(want_mer) per tile otherwise).  The two MER_func sums travel in a float64 all-reduce.
 
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
@@ -54,9 +55,8 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         hh[: len(h)] = h
     if config == "C3":
         return _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer)
-    if mer:
-        raise ValueError("sweep_ber: --mer needs --config C3 (the Task-4 receiver)")
     counters = sweep.Counters(len(snrs))
+    msum = torch.zeros((len(snrs), 2), dtype=torch.float64, device=dev) if mer else None      # MER_func sums s1, s2
     t0 = time.perf_counter()
     n_tiles = 0
     if fused:
@@ -72,8 +72,10 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
                 if estimator == "mmse":
                     plan.set_mmse(hh, float(snrs[sis[g[0]]]))
                 out = plan.ber_sweep(snrs[[sis[i] for i in g]], frames_per_tile, h=h, seeds=[keys[i][0] for i in g],
-                                     frame0=keys[g[0]][1], device=dev)
+                                     frame0=keys[g[0]][1], device=dev, want_mer=mer)
                 err[[sis[i] for i in g]] += out["errors"]
+                if mer:
+                    msum[[sis[i] for i in g]] += out["mer_sums"]
             n_tiles += len(sis)
             for si in sis:
                 counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
@@ -84,17 +86,30 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=key, device=dev, frame0=stream0)
         if estimator == "mmse":
             plan.set_mmse(hh, cfg.SNR_dB)
-        out = ofdm.rx_chain_task5(plan, data["rx"], ref_bits_packed=data["packed"])
+        out = ofdm.rx_chain_task5(plan, data["rx"], ref_bits_packed=data["packed"], want_mer=mer)
         counters.add(si, 0, int(out["errors"].sum().item()), frames_per_tile * plan.frame_bits)
+        if mer:
+            msum[si] += out["mer_sums"].sum(dim=0)
         n_tiles += 1
     torch.cuda.synchronize()
     local_s = time.perf_counter() - t0
     total = sweep.all_reduce_counters(counters, device=dev if backend == "nccl" else None)
-    return {"config": config, "estimator": estimator, "SNRs": snrs.tolist(), "errors": total.errors[:, 0].tolist(),
-            "bits": total.bits[:, 0].tolist(), "BER": (total.errors[:, 0] / np.maximum(total.bits[:, 0], 1)).tolist(),
-            "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world, "tiles_this_rank": n_tiles,
-            "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
-            **({"order": "noise_first", "fused": True} if fused else {})}
+    res = {"config": config, "estimator": estimator, "SNRs": snrs.tolist(), "errors": total.errors[:, 0].tolist(),
+           "bits": total.bits[:, 0].tolist(), "BER": (total.errors[:, 0] / np.maximum(total.bits[:, 0], 1)).tolist(),
+           "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world, "tiles_this_rank": n_tiles,
+           "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
+           **({"order": "noise_first", "fused": True} if fused else {})}
+    if mer:
+        import torch.distributed as dist
+        m = msum.cpu()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = m.to(dev) if backend == "nccl" else m
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            m = t.cpu()
+        m = m.numpy()
+        res["mer_sums"] = m.tolist()
+        res["MER_dB"] = (10.0 * np.log10(m[:, 0] / m[:, 1])).tolist()
+    return res
 
 
 def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer=False):
@@ -161,7 +176,7 @@ def main():
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI; gloo for rehearsals")
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank on this GPU")
     ap.add_argument("--fused", action="store_true", help="reference order (Noise -> conv) through RxPlan.ber_sweep")
-    ap.add_argument("--mer", action="store_true", help="C3: per-point MER_dB (MER_func sums of the Task-4 receiver)")
+    ap.add_argument("--mer", action="store_true", help="per-point MER_dB (MER_func sums of the receiver)")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     import torch

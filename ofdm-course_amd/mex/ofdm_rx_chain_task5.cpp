@@ -2,7 +2,7 @@
 // sequence Task 5/Task5_part2.m:169-193,:296-303 (OFDM_demodulator -> Y = RX(pilotCarriers,1)./pilotValues(:,1) ->
 // OMP_estimate -> equalize_signal -> get_payload -> demapping) and, with ref_bits, BER_func's numerator.
 //
-//   [bits, H_OMP, index, errors] = ofdm_rx_chain_task5(Rx, Nfft, T_guard, N_carrier, pilotCarriers, dataCarriers, ...
+//   [bits, H_OMP, index, errors, mer] = ofdm_rx_chain_task5(Rx, Nfft, T_guard, N_carrier, pilotCarriers, dataCarriers, ...
 //                                                      pilotValues, K, dominant_taps, Constellation, ref_bits, Register)
 //   Rx            [(Nfft+T_guard)*N_symb x n_frames] complex: every column one received frame (Rx_OFDM_mapped_carriers of :160-166)
 //   pilotValues   [Np x N_symb] (or [Np x 1]): the pilot column of the first symbol is what the estimator uses (:190)
@@ -12,6 +12,8 @@
 //                 before `bits` and `errors` -- ref_bits then holds the payload BEFORE the Scrambler
 //   bits          [bits_per_frame x n_frames] 0/1 demapped bits (get_payload order: column-major over [Nd x N_symb])
 //   H_OMP         [N_carrier x n_frames];  index [dominant_taps x n_frames] (1-based picks, 0 = unused);  errors [1 x n_frames]
+//   mer           optional [2 x n_frames]: the sums {sum |ideal|^2, sum |ideal - RX_IQ|^2} of MER_func over each frame's whole RX_IQ
+//                 (Main_model_Task_5.m:282; MER = 10*log10(sum(mer(1,:)) / sum(mer(2,:))) over the frames)
 // N_symb is taken from size(Rx,1).  The plan (carrier tables, dictionary in closed form, Gram table) is built on the first
 // call and kept until the geometry changes or MATLAB clears the MEX file.
 #include "ofdm_mex_common.hpp"
@@ -85,9 +87,11 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   std::vector<uint8_t> bits_packed((size_t)fb * n_frames);
   std::vector<uint32_t> errs(n_frames);
   std::vector<int32_t> idx((size_t)taps * n_frames);
+  std::vector<double> mer(nlhs > 4 ? 2 * n_frames : 0);
   CBuf H = alloc_complex((size_t)nc * n_frames);
-  check(ofdm_rx_chain_task5(g_plan, rx.ptr(), (int64_t)n_frames, bits_packed.data(), have_ref ? ref_packed.data() : nullptr,
-                            have_ref ? errs.data() : nullptr, nlhs > 1 ? H.ptr() : nullptr, nlhs > 2 ? idx.data() : nullptr, flags()), fn);
+  check(ofdm_rx_chain_task5_ex(g_plan, rx.ptr(), (int64_t)n_frames, bits_packed.data(), have_ref ? ref_packed.data() : nullptr,
+                               have_ref ? errs.data() : nullptr, nlhs > 1 ? H.ptr() : nullptr, nlhs > 2 ? idx.data() : nullptr,
+                               nlhs > 4 ? mer.data() : nullptr, flags()), fn);
   std::vector<uint8_t> bits01(frame_bits * n_frames);
   for (size_t f = 0; f < n_frames; ++f)
     for (size_t i = 0; i < frame_bits; ++i) bits01[f * frame_bits + i] = (bits_packed[f * fb + i / 8] >> (7 - i % 8)) & 1u;
@@ -100,5 +104,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   if (nlhs > 3) {
     plhs[3] = mxCreateDoubleMatrix(1, n_frames, mxREAL);
     for (size_t f = 0; f < n_frames; ++f) mxGetDoubles(plhs[3])[f] = have_ref ? (double)errs[f] : 0.0;
+  }
+  if (nlhs > 4) {                                                     // [2 x n_frames]: memory order [n_frames][2]
+    plhs[4] = mxCreateDoubleMatrix(2, n_frames, mxREAL);
+    for (size_t i = 0; i < mer.size(); ++i) mxGetDoubles(plhs[4])[i] = mer[i];
   }
 }
