@@ -641,6 +641,15 @@ def _imp_mode(v, what):
     return 1, v
 
 
+def _torch_dtype(npdt):
+    """The torch dtype of a device output declared with numpy dtype `npdt`: a wide unsigned type becomes the signed type of
+    its width (uint64 counters -> int64, uint32 -> int32)."""
+    dt = np.dtype(npdt)
+    if dt.kind == "u" and dt.itemsize > 1:
+        dt = np.dtype(f"i{dt.itemsize}")
+    return torch.from_numpy(np.empty(0, dt)).dtype
+
+
 class RxPlan:
     """Device-resident description of one Task-5 RX configuration (ofdm_rx_plan_create)."""
 
@@ -703,47 +712,18 @@ class RxPlan:
         (+ Time_Delay [n_frames] int64, Freq_Shift [n_frames] float64 with want_draws));
         torch CUDA tensors when `device` is given, numpy arrays otherwise."""
         n_frames = int(n_frames)
-        cdt_np = np.complex128 if self.f64 else np.complex64
-        flags = (L.OFDM_F64 if self.f64 else L.OFDM_F32)
         scr = Register is not None
-        if device is not None:
-            dev = torch.device(device)
-            rx = torch.empty((n_frames, self.frame_samples), dtype=torch.complex128 if self.f64 else torch.complex64,
-                             device=dev)
-            packed = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev)
-            bits = torch.empty((n_frames, self.frame_bits), dtype=torch.uint8, device=dev) if want_bits else None
-            scp = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev) if scr else None
-            sto = torch.empty((n_frames,), dtype=torch.int64, device=dev) if want_draws else None
-            cfo = torch.empty((n_frames,), dtype=torch.float64, device=dev) if want_draws else None
-            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            flags |= L.OFDM_DEVICE
-        else:
-            L.check(self.lib.ofdm_set_stream(None), "set_stream")
-            rx = np.empty((n_frames, self.frame_samples), dtype=cdt_np)
-            packed = np.empty((n_frames, self.frame_bytes), dtype=np.uint8)
-            bits = np.empty((n_frames, self.frame_bits), dtype=np.uint8) if want_bits else None
-            scp = np.empty((n_frames, self.frame_bytes), dtype=np.uint8) if scr else None
-            sto = np.empty((n_frames,), dtype=np.int64) if want_draws else None
-            cfo = np.empty((n_frames,), dtype=np.float64) if want_draws else None
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-        hh = None
-        if h is not None:
-            hh = np.ascontiguousarray(np.asarray(h.cpu().numpy() if _is_torch(h) else h).ravel().astype(cdt_np))
-        reg = None
-        if scr:
-            reg = np.ascontiguousarray(np.asarray(Register).ravel().astype(np.uint8))
-            if reg.size != 15:
-                raise OfdmError("tx_frames: Register must have 15 entries")
-
+        (rx, packed, bits, scp, sto, cfo), ptrs, flags = self._outputs(
+            device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
+            ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bits), np.uint8) if want_bits else None,
+            ((n_frames, self.frame_bytes), np.uint8) if scr else None, ((n_frames,), np.int64) if want_draws else None,
+            ((n_frames,), np.float64) if want_draws else None)
+        keep, ph, nh, pr = self._fused_args(h, Register, "tx_frames")
         sm, sv = _imp_mode(Time_Delay, "tx_frames")
         cm, cv = _imp_mode(Freq_Shift, "tx_frames")
-        L.check(self.lib.ofdm_tx_frames_ex(self.handle, hh.ctypes.data_as(C.c_void_p) if hh is not None else None,
-                                           0 if hh is None else hh.size, float(SNR if SNR is not None else 0.0),
-                                           int(SNR is not None), int(seed), int(frame0), n_frames,
-                                           reg.ctypes.data_as(C.c_void_p) if scr else None, sm, int(sv), cm, float(cv),
-                                           int(bool(noise_first)), ptr(rx), ptr(packed), ptr(bits), ptr(scp), ptr(sto),
-                                           ptr(cfo), flags), "tx_frames")
+        L.check(self.lib.ofdm_tx_frames_ex(self.handle, ph, nh, float(SNR if SNR is not None else 0.0), int(SNR is not None),
+                                           int(seed), int(frame0), n_frames, pr, sm, int(sv), cm, float(cv),
+                                           int(bool(noise_first)), *ptrs, flags), "tx_frames")
         out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
         if want_bits:
             out["bits"] = bits
@@ -767,6 +747,30 @@ class RxPlan:
         pr = reg.ctypes.data_as(C.c_void_p) if reg is not None else None
         return (hh, reg), ph, 0 if hh is None else hh.size, pr
 
+    def _outputs(self, device, *specs):
+        """Row-major outputs of one plan call, one per (shape, numpy dtype) spec, None for an output not wanted: torch
+        tensors on `device` (the call runs on its current stream) when it is given, numpy arrays on the default stream
+        otherwise.  -> (arrays, their pointers, the call's flags)"""
+        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
+        if device is not None:
+            dev = torch.device(device)
+            arrs = [None if sp is None else torch.empty(sp[0], dtype=_torch_dtype(sp[1]), device=dev) for sp in specs]
+            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
+            return arrs, [None if t is None else C.c_void_p(t.data_ptr()) for t in arrs], flags | L.OFDM_DEVICE
+        L.check(self.lib.ofdm_set_stream(None), "set_stream")
+        arrs = [None if sp is None else np.empty(sp[0], dtype=sp[1]) for sp in specs]
+        return arrs, [None if x is None else x.ctypes.data_as(C.c_void_p) for x in arrs], flags
+
+    @staticmethod
+    def _points(SNRs, seeds, seed, what):
+        """The SNR row of a sweep and one Philox key per point (`seed` for every point when `seeds` is None)."""
+        snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
+        sd = np.full(snr.size, int(seed), dtype=np.uint64) if seeds is None else \
+            np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
+        if sd.size != snr.size:
+            raise OfdmError(f"{what}: seeds must have one entry per SNR point")
+        return snr, sd
+
     def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None, Time_Delay=None,
                         Freq_Shift=None, want_draws=False):
         """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
@@ -781,37 +785,20 @@ class RxPlan:
         float64 with want_draws)); torch CUDA tensors when `device` is given."""
         n_frames = int(n_frames)
         ex = Time_Delay is not None or Freq_Shift is not None or want_draws
-        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
         scr = Register is not None
-        if device is not None:
-            dev = torch.device(device)
-            rx = torch.empty((n_frames, self.frame_samples), dtype=torch.complex128 if self.f64 else torch.complex64,
-                             device=dev)
-            packed = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev)
-            scp = torch.empty((n_frames, self.frame_bytes), dtype=torch.uint8, device=dev) if scr else None
-            sto = torch.empty((n_frames,), dtype=torch.int64, device=dev) if want_draws else None
-            cfo = torch.empty((n_frames,), dtype=torch.float64, device=dev) if want_draws else None
-            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            flags |= L.OFDM_DEVICE
-        else:
-            L.check(self.lib.ofdm_set_stream(None), "set_stream")
-            rx = np.empty((n_frames, self.frame_samples), dtype=np.complex128 if self.f64 else np.complex64)
-            packed = np.empty((n_frames, self.frame_bytes), dtype=np.uint8)
-            scp = np.empty((n_frames, self.frame_bytes), dtype=np.uint8) if scr else None
-            sto = np.empty((n_frames,), dtype=np.int64) if want_draws else None
-            cfo = np.empty((n_frames,), dtype=np.float64) if want_draws else None
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        (rx, packed, scp, sto, cfo), ptrs, flags = self._outputs(
+            device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
+            ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bytes), np.uint8) if scr else None,
+            ((n_frames,), np.int64) if want_draws else None, ((n_frames,), np.float64) if want_draws else None)
         keep, ph, nh, pr = self._fused_args(h, Register, "tx_frames_fused")
         if ex:
             sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
             cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
             L.check(self.lib.ofdm_tx_frames_fused_ex(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
-                                                     sm, int(sv), cm, float(cv), ptr(rx), ptr(packed), ptr(scp), ptr(sto),
-                                                     ptr(cfo), flags), "tx_frames_fused_ex")
-        else:
+                                                     sm, int(sv), cm, float(cv), *ptrs, flags), "tx_frames_fused_ex")
+        else:                           # the entry without impairments launches no draw kernel and the plain channel pass
             L.check(self.lib.ofdm_tx_frames_fused(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
-                                                  ptr(rx), ptr(packed), ptr(scp), flags), "tx_frames_fused")
+                                                  *ptrs[:3], flags), "tx_frames_fused")
         out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
         if scr:
             out["sc_packed"] = scp
@@ -834,40 +821,16 @@ class RxPlan:
         want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2]."""
         if want_frame_mer and not want_mer:
             raise OfdmError("ber_sweep: want_frame_mer needs want_mer")
-        snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
-        n = snr.size
-        fpp = int(frames_per_point)
-        sd = np.full(n, int(seed), dtype=np.uint64) if seeds is None else \
-            np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
-        if sd.size != n:
-            raise OfdmError("ber_sweep: seeds must have one entry per SNR point")
-        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
-        if device is not None:
-            dev = torch.device(device)
-            err = torch.empty((n,), dtype=torch.int64, device=dev)
-            fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
-            ms = torch.empty((n, 2), dtype=torch.float64, device=dev) if want_mer else None
-            fm = torch.empty((n, fpp, 2), dtype=torch.float64, device=dev) if want_frame_mer else None
-            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            flags |= L.OFDM_DEVICE
-        else:
-            L.check(self.lib.ofdm_set_stream(None), "set_stream")
-            err = np.empty((n,), dtype=np.uint64)
-            fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
-            ms = np.empty((n, 2), dtype=np.float64) if want_mer else None
-            fm = np.empty((n, fpp, 2), dtype=np.float64) if want_frame_mer else None
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        snr, sd = self._points(SNRs, seeds, seed, "ber_sweep")
+        n, fpp = snr.size, int(frames_per_point)
+        (err, fe, ms, fm), ptrs, flags = self._outputs(
+            device, ((n,), np.uint64), ((n, fpp), np.uint32) if want_frame_errors else None,
+            ((n, 2), np.float64) if want_mer else None, ((n, fpp, 2), np.float64) if want_frame_mer else None)
         keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
-        if not want_mer:
-            L.check(self.lib.ofdm_ber_sweep_task5(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
-                                                  sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                  int(max_frames_per_chunk), ptr(err), ptr(fe), flags), "ber_sweep_task5")
-        else:
-            L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
-                                                     sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                     int(max_frames_per_chunk), ptr(err), ptr(fe), ptr(ms), ptr(fm), flags),
-                    "ber_sweep_task5_ex")
+        L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
+                                                 sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                 int(max_frames_per_chunk), *ptrs, flags),
+                "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
         out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
         if want_frame_errors:
             out["frame_errors"] = fe
@@ -896,50 +859,23 @@ class RxPlan:
         0-based index mer_skip on, frames concatenated), and MER_dB=[n] (computed on `device` when it is given); with
         want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2].  Time_Delay=12, time_desync=1,
         freq_desync=0, mp_desync=0, mer_skip=Nfft+T_guard is the MER(SNR) study of T4/Main_model_Task_4.m:136-200."""
-        snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
-        n = snr.size
-        fpp = int(frames_per_point)
-        sd = np.full(n, int(seed), dtype=np.uint64) if seeds is None else \
-            np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
-        if sd.size != n:
-            raise OfdmError("ber_sweep_task4: seeds must have one entry per SNR point")
+        snr, sd = self._points(SNRs, seeds, seed, "ber_sweep_task4")
+        n, fpp = snr.size, int(frames_per_point)
         sm, sv = _imp_mode(Time_Delay, "ber_sweep_task4")
         cm, cv = _imp_mode(Freq_Shift, "ber_sweep_task4")
         td = Time_Delay is not None if time_desync is None else bool(time_desync)
         fd = Freq_Shift is not None if freq_desync is None else bool(freq_desync)
         md = h is not None if mp_desync is None else bool(mp_desync)
-        flags = L.OFDM_F64 if self.f64 else L.OFDM_F32
-        if device is not None:
-            dev = torch.device(device)
-            err = torch.empty((n,), dtype=torch.int64, device=dev)
-            stc = torch.empty((n, 4), dtype=torch.int64, device=dev)
-            cae = torch.empty((n,), dtype=torch.float64, device=dev)
-            fe = torch.empty((n, fpp), dtype=torch.int32, device=dev) if want_frame_errors else None
-            ms = torch.empty((n, 2), dtype=torch.float64, device=dev) if want_mer else None
-            fm = torch.empty((n, fpp, 2), dtype=torch.float64, device=dev) if want_mer and want_frame_mer else None
-            L.check(self.lib.ofdm_set_stream(C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "set_stream")
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-            flags |= L.OFDM_DEVICE
-        else:
-            L.check(self.lib.ofdm_set_stream(None), "set_stream")
-            err = np.empty((n,), dtype=np.uint64)
-            stc = np.empty((n, 4), dtype=np.uint64)
-            cae = np.empty((n,), dtype=np.float64)
-            fe = np.empty((n, fpp), dtype=np.uint32) if want_frame_errors else None
-            ms = np.empty((n, 2), dtype=np.float64) if want_mer else None
-            fm = np.empty((n, fpp, 2), dtype=np.float64) if want_mer and want_frame_mer else None
-            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        (err, stc, cae, fe, ms, fm), ptrs, flags = self._outputs(
+            device, ((n,), np.uint64), ((n, 4), np.uint64), ((n,), np.float64),
+            ((n, fpp), np.uint32) if want_frame_errors else None, ((n, 2), np.float64) if want_mer else None,
+            ((n, fpp, 2), np.float64) if want_mer and want_frame_mer else None)
         keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-        if not want_mer:
-            L.check(self.lib.ofdm_ber_sweep_task4(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
-                                                  snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
-                                                  int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
-                                                  ptr(fe), flags), "ber_sweep_task4")
-        else:
-            L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
-                                                     snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
-                                                     int(frame0), pr, int(max_frames_per_chunk), ptr(err), ptr(stc), ptr(cae),
-                                                     ptr(fe), int(mer_skip), ptr(ms), ptr(fm), flags), "ber_sweep_task4_ex")
+        L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
+                                                 snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                                 int(frame0), pr, int(max_frames_per_chunk), *ptrs[:4],
+                                                 int(mer_skip) if want_mer else 0, *ptrs[4:], flags),
+                "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
         host = device is None
         out = dict(errors=err.astype(np.int64) if host else err, bits=fpp * self.frame_bits,
                    status_counts=stc.astype(np.int64) if host else stc, cfo_abs_err=cae)

@@ -18,13 +18,20 @@
 //
 // ofdm_tx_frames_fused_ex / ofdm_ber_sweep_task4 add the Task-4 impairments (T4/Main_model_Task_4.m:99-110, add_STO.m,
 // add_CFO.m) in the reference order Noise -> add_STO -> add_CFO -> conv, still in three sample passes:
-//   tx_channel_imp_kernel<T>        the sibling of tx_channel_fused_kernel (which stays as it is): its LDS load stage builds
+//   tx_channel_imp_kernel<T>        tx_channel_fused_kernel's body (tx_channel_body) with IMP on: its LDS load stage builds
 //                                   z[m] = w[m + sto_f] e^{2 pi i cfo_f m / Nfft} for the segment and its halo, the noise of w
 //                                   drawn at the SOURCE index m + sto_f (Noise comes before the shift).  The shift is uniform
 //                                   per frame: no extra halo, the loads stay coalesced.
 //   t4_point_reduce_kernel          per-frame errors / status / |FreqOffset + IFO - Freq_Shift| of a whole point -> its sums,
 //                                   in a fixed order (the double sum does not depend on the chunking).
+//   t4_point_mer_kernel             per-frame MER_func sums -> per-point sums in the same fixed order (both sweeps with MER).
 // The per-frame draws are tx_draw_kernel's (ofdm_txgen.hip), the draws of ofdm_tx_frames_ex.
+//
+// Host side: both generator entries forward to one body (txf_frames); given impairments it launches the draw kernel and
+// tx_channel_imp_kernel, else tx_channel_fused_kernel.  The two sweeps share their common checks and outputs
+// (txf_check_sweep, txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points, the receiver
+// passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
+// per-point reduction.
 #include <algorithm>
 #include <type_traits>
 
@@ -154,48 +161,16 @@ __device__ __forceinline__ cx<T> txf_noisy(cx<T> v, int64_t i, double sg, uint32
 // ---------------------------------------------------------------------------------------------
 // Noise (Noise.m:3-10) then conv(h) truncated per frame (T5/Task5_part2.m:152), one segment per workgroup.
 // grid = (segments, frames); dynamic LDS = (TXF_SEG + halo) samples.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void tx_channel_fused_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
-                                                               const double* __restrict__ partial, int n_symb, int64_t len,
-                                                               double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
-                                                               TxfTaps<T> taps) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char txf_smem[];
-  cx<T>* buf = (cx<T>*)txf_smem;
-  const int64_t f = blockIdx.y;
-  const int64_t n0 = (int64_t)blockIdx.x * TXF_SEG;
-  const int H = taps.halo;
-  const cx<T>* x = tx + f * len;
-  double sum = 0;                                                // Noise.m:3 -- the frame's symbols in order
-  for (int i = 0; i < n_symb; ++i) sum += partial[f * n_symb + i];
-  const double sg = sqrt(sum / (double)len / snr_lin / 2.0);     // :5, per-component sigma
-  const uint32_t stream = stream0 + (uint32_t)f;
-  for (int i = threadIdx.x; i < TXF_SEG + H; i += 256) {
-    const int64_t idx = n0 - H + i;                              // before the frame: silence (no signal, no noise)
-    cx<T> v = mk<T>(0, 0);
-    if (idx >= 0 && idx < len) v = txf_noisy<T>(x[idx], idx, sg, stream, k0, k1);
-    buf[i] = v;
-  }
-  __syncthreads();
-  cx<T>* y = rx + f * len;
-  for (int o = threadIdx.x; o < TXF_SEG; o += 256) {
-    if (n0 + o >= len) break;
-    cx<T> acc = mk<T>(0, 0);
-    for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
-    nt_store(y + n0 + o, acc);
-  }
-}
-
-// Noise -> add_STO -> add_CFO -> conv(h) truncated per frame (T4/Main_model_Task_4.m:99-110,:257-267): the channel pass of
-// tx_channel_fused_kernel with the frame's shift sto[f] and rotation cfo[f] folded into the LDS load stage.
+// IMP adds add_STO -> add_CFO between Noise and conv (T4/Main_model_Task_4.m:99-110,:257-267), folded into the LDS load
+// stage with the frame's shift sto[f] and rotation cfo[f]:
 //   w[j] = x[j] + sigma n(j)   s[m] = w[m + sto] (0 outside the frame, add_STO.m, either sign)
 //   z[m] = s[m] exp(2 pi i cfo m / Nfft)   (add_CFO.m on the shifted stream; the arithmetic of sto_cfo_frames_kernel)
-template <typename T>
-__global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
-                                                             const double* __restrict__ partial, int n_symb, int64_t len,
-                                                             double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
-                                                             const int64_t* __restrict__ sto, const double* __restrict__ cfo,
-                                                             double inv_nfft, TxfTaps<T> taps) {
+// ---------------------------------------------------------------------------------------------
+template <typename T, bool IMP>
+__device__ __forceinline__ void tx_channel_body(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                const double* __restrict__ partial, int n_symb, int64_t len, double snr_lin,
+                                                uint32_t k0, uint32_t k1, uint32_t stream0, const int64_t* __restrict__ sto,
+                                                const double* __restrict__ cfo, double inv_nfft, const TxfTaps<T>& taps) {
   extern __shared__ __attribute__((aligned(16))) unsigned char txf_smem[];
   cx<T>* buf = (cx<T>*)txf_smem;
   const int64_t f = blockIdx.y;
@@ -206,20 +181,26 @@ __global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __rest
   for (int i = 0; i < n_symb; ++i) sum += partial[f * n_symb + i];
   const double sg = sqrt(sum / (double)len / snr_lin / 2.0);     // :5, per-component sigma
   const uint32_t stream = stream0 + (uint32_t)f;
-  const int64_t sh = sto[f];
-  const double fo = cfo[f];
+  int64_t sh = 0;                                                // uniform per frame: no extra halo, coalesced loads
+  double fo = 0.0;
+  if constexpr (IMP) {
+    sh = sto[f];
+    fo = cfo[f];
+  }
   for (int i = threadIdx.x; i < TXF_SEG + H; i += 256) {
     const int64_t m = n0 - H + i;                                // index of the shifted stream; before the frame: silence
     const int64_t src = m + sh;
     cx<T> v = mk<T>(0, 0);
     if (m >= 0 && m < len && src >= 0 && src < len) {
-      v = txf_noisy<T>(x[src], src, sg, stream, k0, k1);         // the noise of the source sample
-      if (fo != 0.0) {                                           // cfo 0: a rotation by exactly 1, skipped (uniform per frame)
-        const double t = fo * (double)m * inv_nfft;
-        const double fr = t - floor(t);
-        double sn, cs;
-        sincospi(2.0 * fr, &sn, &cs);
-        v = mk<T>((T)((double)v.x * cs - (double)v.y * sn), (T)((double)v.x * sn + (double)v.y * cs));
+      v = txf_noisy<T>(x[src], src, sg, stream, k0, k1);         // the noise of the source sample (Noise before add_STO)
+      if constexpr (IMP) {
+        if (fo != 0.0) {                                         // cfo 0: a rotation by exactly 1, skipped (uniform per frame)
+          const double t = fo * (double)m * inv_nfft;
+          const double fr = t - floor(t);
+          double sn, cs;
+          sincospi(2.0 * fr, &sn, &cs);
+          v = mk<T>((T)((double)v.x * cs - (double)v.y * sn), (T)((double)v.x * sn + (double)v.y * cs));
+        }
       }
     }
     buf[i] = v;
@@ -232,6 +213,23 @@ __global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __rest
     for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
     nt_store(y + n0 + o, acc);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_fused_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                               const double* __restrict__ partial, int n_symb, int64_t len,
+                                                               double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                               TxfTaps<T> taps) {
+  tx_channel_body<T, false>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, nullptr, nullptr, 0.0, taps);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                             const double* __restrict__ partial, int n_symb, int64_t len,
+                                                             double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                             const int64_t* __restrict__ sto, const double* __restrict__ cfo,
+                                                             double inv_nfft, TxfTaps<T> taps) {
+  tx_channel_body<T, true>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, sto, cfo, inv_nfft, taps);
 }
 
 __global__ __launch_bounds__(256) void ber_point_reduce_kernel(const uint32_t* __restrict__ frame_errors,
@@ -370,31 +368,6 @@ static int launch_symbols(const ofdm_rx_plan* pl, const void* tw, void* tx, doub
   return check_launch("tx_symbols_fused_kernel");
 }
 
-template <typename T>
-static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
-                          double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf) {
-  const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
-  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
-  // > 64 KB for long channels: the attribute is per device, so it is set on every launch (not cached per process)
-  OFDM_HIP(hipFuncSetAttribute((const void*)tx_channel_fused_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-  hipLaunchKernelGGL(tx_channel_fused_kernel<T>, dim3(cdiv_u(len, TXF_SEG), (unsigned)nf), dim3(256), dyn, ctx().stream,
-                     (const cx<T>*)tx, (cx<T>*)rx, partial, pl->n_symb, len, snr_lin, k0, k1, stream0, txf_taps<T>(ch));
-  return check_launch("tx_channel_fused_kernel");
-}
-
-template <typename T>
-static int launch_channel_imp(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
-                              double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const int64_t* sto,
-                              const double* cfo, int64_t nf) {
-  const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
-  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
-  OFDM_HIP(hipFuncSetAttribute((const void*)tx_channel_imp_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-  hipLaunchKernelGGL(tx_channel_imp_kernel<T>, dim3(cdiv_u(len, TXF_SEG), (unsigned)nf), dim3(256), dyn, ctx().stream,
-                     (const cx<T>*)tx, (cx<T>*)rx, partial, pl->n_symb, len, snr_lin, k0, k1, stream0, sto, cfo,
-                     1.0 / (double)pl->nfft, txf_taps<T>(ch));
-  return check_launch("tx_channel_imp_kernel");
-}
-
 // the Task-4 impairments of a generator call (T4/Main_model_Task_4.m:99-110): modes 0 off, 1 fixed, 2 drawn; the chunk's
 // per-frame draws are written to sto / cfo (nf entries each)
 struct TxfImp {
@@ -405,6 +378,25 @@ struct TxfImp {
   int64_t* sto = nullptr;
   double* cfo = nullptr;
 };
+
+// imp (optional): tx_channel_imp_kernel with the chunk's draws imp->sto / imp->cfo, else tx_channel_fused_kernel
+template <typename T>
+static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
+                          double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const TxfImp* imp, int64_t nf) {
+  const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
+  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
+  const dim3 grid(cdiv_u(len, TXF_SEG), (unsigned)nf);
+  const void* kernel = imp ? (const void*)tx_channel_imp_kernel<T> : (const void*)tx_channel_fused_kernel<T>;
+  // > 64 KB for long channels: the attribute is per device, so it is set on every launch (not cached per process)
+  OFDM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (imp)
+    hipLaunchKernelGGL(tx_channel_imp_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
+                       pl->n_symb, len, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, 1.0 / (double)pl->nfft, txf_taps<T>(ch));
+  else
+    hipLaunchKernelGGL(tx_channel_fused_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
+                       pl->n_symb, len, snr_lin, k0, k1, stream0, txf_taps<T>(ch));
+  return check_launch(imp ? "tx_channel_imp_kernel" : "tx_channel_fused_kernel");
+}
 
 // chunk buffers inside the plan-owned workspace
 struct TxfBuffers {
@@ -477,17 +469,11 @@ static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, 
   else OFDM_TRY((launch_symbols<float, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf)));
   OFDM_FFT_DISPATCH(pl->nfft, CALL)
 #undef CALL
-  if (imp) {
+  if (imp)
     OFDM_TRY(tx_draw_device(pl, imp->sto, imp->cfo, imp->sto_mode, imp->sto_value, imp->cfo_mode, imp->cfo_value, k0, k1,
                             stream0, nf));
-    if (pl->f64)
-      OFDM_TRY(launch_channel_imp<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, nf));
-    else
-      OFDM_TRY(launch_channel_imp<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, nf));
-    return OFDM_OK;
-  }
-  if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
-  else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, nf));
+  if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, nf));
+  else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, nf));
   return OFDM_OK;
 }
 
@@ -533,119 +519,11 @@ static int txf_check_plan(ofdm_rx_plan* pl, int flags, int64_t frame0, int64_t n
   return OFDM_OK;
 }
 
-}  // namespace ofdm
-
-using namespace ofdm;
-
-extern "C" int ofdm_tx_frames_fused(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
-                                    int64_t n_frames, const uint8_t* scr_reg15, void* rx_out, uint8_t* ref_bits_out,
-                                    uint8_t* sc_ref_bits_out, int flags) {
-  OFDM_TRY(ensure_init());
-  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused: bad arguments");
-  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused"));
-  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused: sc_ref_bits_out needs the Scrambler register");
-  TxfChannel ch;
-  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
-  if (n_frames == 0) return OFDM_OK;
-  OFDM_TRY(tx_dict_device(pl));
-  const size_t cs = csize(flags);
-  const int64_t frame_samples = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
-  const size_t fb = (size_t)pl->frame_words * 4;
-  Stage st(flags);
-  void *drx, *dref, *dscref;
-  OFDM_TRY(st.out(rx_out, cs * (size_t)frame_samples * n_frames, &drx));
-  OFDM_TRY(st.out(ref_bits_out, fb * n_frames, &dref));
-  OFDM_TRY(st.out(sc_ref_bits_out, fb * n_frames, &dscref));
-  const bool scr = scr_reg15 != nullptr;
-  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0);
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr, false, b));
-  const double snr_lin = std::pow(10.0, snr_db / 10.0);
-  const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  for (int64_t c0 = 0; c0 < n_frames; c0 += CH) {
-    const int64_t nf = std::min<int64_t>(CH, n_frames - c0);
-    OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b,
-                          (unsigned char*)drx + cs * (size_t)frame_samples * c0,
-                          dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
-                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr));
-  }
-  return st.finish();
-}
-
-extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
-                                       int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
-                                       int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
-                                       double* mer_sums_out, double* frame_mer_sums_out, int flags) {
-  OFDM_TRY(ensure_init());
-  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && max_frames_per_chunk >= 0 && errors_out,
-           "ber_sweep_task5: bad arguments");
-  OFDM_ARG(n_points == 0 || (snr_db && seeds), "ber_sweep_task5: snr_db / seeds missing");
-  OFDM_ARG(n_points < ((int64_t)1 << 31), "ber_sweep_task5: too many points");
-  OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task5"));
-  OFDM_ARG(!pl->d_wt || n_points <= 1, "ber_sweep_task5: an MMSE-mode plan is built for one SNR (n_points must be 1)");
-  OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task5"));
-  TxfChannel ch;
-  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
-  if (n_points == 0) return OFDM_OK;
-  Stage st(flags);
-  void *derr, *dfe, *dmer, *dfm;
-  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
-  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
-  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_points, &dmer));
-  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * (size_t)(n_points * frames_per_point), &dfm));
-  const bool mer = dmer || dfm;
-  if (frames_per_point == 0) {
-    OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, ctx().stream));
-    if (dmer) OFDM_HIP(hipMemsetAsync(dmer, 0, sizeof(double) * 2 * (size_t)n_points, ctx().stream));
-    return st.finish();
-  }
-  if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)(n_points * frames_per_point), &dfe));
-  // the per-frame MER sums of every point, reduced once after the last chunk
-  if (mer && !dfm) OFDM_TRY(st.scratch(sizeof(double) * 2 * (size_t)(n_points * frames_per_point), &dfm));
-  OFDM_TRY(tx_dict_device(pl));
-  const bool scr = scr_reg15 != nullptr;
-  const int64_t CH = txf_chunk(pl, scr, true, frames_per_point, max_frames_per_chunk);
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr, true, b));
-  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr));
-      const int64_t o = p * frames_per_point + c0;
-      OFDM_TRY(ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref, (uint32_t*)dfe + o, nullptr, nullptr,
-                                      mer ? (double*)dfm + 2 * o : nullptr, rxflags));
-    }
-  }
-  hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)dfe,
-                     frames_per_point, (unsigned long long*)derr);
-  OFDM_TRY(check_launch("ber_point_reduce_kernel"));
-  if (dmer) {                                                   // the Task-4 sweep's fixed-order reduction of the frame sums
-    hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)dfm,
-                       frames_per_point, (double*)dmer);
-    OFDM_TRY(check_launch("t4_point_mer_kernel"));
-  }
-  return st.finish();
-}
-
-extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
-                                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
-                                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags) {
-  return ofdm_ber_sweep_task5_ex(pl, h, h_len, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15,
-                                 max_frames_per_chunk, errors_out, frame_errors_out, nullptr, nullptr, flags);
-}
-
-extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed,
-                                       int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, int sto_mode,
-                                       int64_t sto_value, int cfo_mode, double cfo_value, void* rx_out, uint8_t* ref_bits_out,
-                                       uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, int flags) {
-  OFDM_TRY(ensure_init());
-  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused_ex: bad arguments");
-  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused_ex"));
-  OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "tx_frames_fused_ex"));
-  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused_ex: sc_ref_bits_out needs the Scrambler register");
+// the body of both generator entries: n_frames frames from frame0 on in chunks of the plan-owned workspace.
+// imp (optional): the Task-4 impairments -- the draws go to sto_out / cfo_out when they are given, else to the workspace
+static int txf_frames(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
+                      int64_t n_frames, const uint8_t* scr_reg15, const TxfImp* imp, void* rx_out, uint8_t* ref_bits_out,
+                      uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, int flags) {
   TxfChannel ch;
   OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
   if (n_frames == 0) return OFDM_OK;
@@ -661,23 +539,160 @@ extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(st.out(sto_out, sizeof(int64_t) * (size_t)n_frames, &dsto));
   OFDM_TRY(st.out(cfo_out, sizeof(double) * (size_t)n_frames, &dcfo));
   const bool scr = scr_reg15 != nullptr;
-  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0, true);
+  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0, imp != nullptr);
   TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr, false, b, true));
+  OFDM_TRY(txf_workspace(pl, CH, scr, false, b, imp != nullptr));
   const double snr_lin = std::pow(10.0, snr_db / 10.0);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-  TxfImp imp;
-  imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
+  TxfImp ci;
+  if (imp) ci = *imp;
   for (int64_t c0 = 0; c0 < n_frames; c0 += CH) {
     const int64_t nf = std::min<int64_t>(CH, n_frames - c0);
-    imp.sto = dsto ? (int64_t*)dsto + c0 : b.sto;              // the draws go where the caller wants them, else the workspace
-    imp.cfo = dcfo ? (double*)dcfo + c0 : b.cfo;
+    ci.sto = dsto ? (int64_t*)dsto + c0 : b.sto;
+    ci.cfo = dcfo ? (double*)dcfo + c0 : b.cfo;
     OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b,
                           (unsigned char*)drx + cs * (size_t)frame_samples * c0,
                           dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
-                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, &imp));
+                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, imp ? &ci : nullptr));
   }
   return st.finish();
+}
+
+// the checks both sweeps make after their own argument checks
+static int txf_check_sweep(ofdm_rx_plan* pl, const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                           int64_t frames_per_point, int64_t frame0, int flags, const char* what) {
+  OFDM_ARG(n_points == 0 || (snr_db && seeds), "%s: snr_db / seeds missing", what);
+  OFDM_ARG(n_points < ((int64_t)1 << 31), "%s: too many points", what);
+  return txf_check_plan(pl, flags, frame0, frames_per_point, what);
+}
+
+// the outputs both sweeps have: per point the bit errors and MER sums, per frame the errors and MER sums
+struct TxfSweepOut {
+  void *err = nullptr, *fe = nullptr, *mer = nullptr, *fm = nullptr;
+};
+
+// stages the common outputs; with no frames the per-point sums are zeroed, else the per-frame values of every point
+// (reduced once after the last chunk) get scratch where the caller wants none
+static int txf_sweep_outputs(Stage& st, int64_t n_points, int64_t frames_per_point, uint64_t* errors_out,
+                             uint32_t* frame_errors_out, double* mer_sums_out, double* frame_mer_sums_out, TxfSweepOut& o) {
+  const size_t np = (size_t)n_points, nf = (size_t)(n_points * frames_per_point);
+  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * np, &o.err));
+  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * nf, &o.fe));
+  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * np, &o.mer));
+  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * nf, &o.fm));
+  if (frames_per_point == 0) {
+    OFDM_HIP(hipMemsetAsync(o.err, 0, sizeof(uint64_t) * np, ctx().stream));
+    if (o.mer) OFDM_HIP(hipMemsetAsync(o.mer, 0, sizeof(double) * 2 * np, ctx().stream));
+    return OFDM_OK;
+  }
+  if (!o.fe) OFDM_TRY(st.scratch(sizeof(uint32_t) * nf, &o.fe));
+  if (o.mer && !o.fm) OFDM_TRY(st.scratch(sizeof(double) * 2 * nf, &o.fm));
+  return OFDM_OK;
+}
+
+// every point of a sweep, chunk by chunk of at most CH frames: the chunk generated into the workspace (imp: with the Task-4
+// impairments, the draws of the sweep's frame k at imp->sto[k] / imp->cfo[k]), then decode(b, nf, o) with o the sweep index
+// of the chunk's first frame
+template <typename Decode>
+static int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const double* snr_db, const uint64_t* seeds,
+                            int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15, int64_t CH,
+                            const TxfImp* imp, Decode&& decode) {
+  OFDM_TRY(tx_dict_device(pl));
+  TxfBuffers b;
+  OFDM_TRY(txf_workspace(pl, CH, scr_reg15 != nullptr, true, b, imp != nullptr));
+  TxfImp ci;
+  if (imp) ci = *imp;
+  for (int64_t p = 0; p < n_points; ++p) {
+    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
+    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
+    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
+      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
+      const int64_t o = p * frames_per_point + c0;
+      if (imp) { ci.sto = imp->sto + o; ci.cfo = imp->cfo + o; }
+      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr,
+                            imp ? &ci : nullptr));
+      OFDM_TRY(decode(b, nf, o));
+    }
+  }
+  return OFDM_OK;
+}
+
+// the per-point MER sums of a sweep with MER: the fixed-order reduction of the per-frame sums
+static int txf_point_mer(const TxfSweepOut& o, int64_t n_points, int64_t frames_per_point) {
+  if (!o.mer) return OFDM_OK;
+  hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)o.fm,
+                     frames_per_point, (double*)o.mer);
+  return check_launch("t4_point_mer_kernel");
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_tx_frames_fused(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
+                                    int64_t n_frames, const uint8_t* scr_reg15, void* rx_out, uint8_t* ref_bits_out,
+                                    uint8_t* sc_ref_bits_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused: sc_ref_bits_out needs the Scrambler register");
+  return txf_frames(pl, h, h_len, snr_db, seed, frame0, n_frames, scr_reg15, nullptr, rx_out, ref_bits_out, sc_ref_bits_out,
+                    nullptr, nullptr, flags);
+}
+
+extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed,
+                                       int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, int sto_mode,
+                                       int64_t sto_value, int cfo_mode, double cfo_value, void* rx_out, uint8_t* ref_bits_out,
+                                       uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused_ex: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused_ex"));
+  OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "tx_frames_fused_ex"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused_ex: sc_ref_bits_out needs the Scrambler register");
+  TxfImp imp;
+  imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
+  return txf_frames(pl, h, h_len, snr_db, seed, frame0, n_frames, scr_reg15, &imp, rx_out, ref_bits_out, sc_ref_bits_out,
+                    sto_out, cfo_out, flags);
+}
+
+extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                                       int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                       int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
+                                       double* mer_sums_out, double* frame_mer_sums_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && max_frames_per_chunk >= 0 && errors_out,
+           "ber_sweep_task5: bad arguments");
+  OFDM_TRY(txf_check_sweep(pl, snr_db, seeds, n_points, frames_per_point, frame0, flags, "ber_sweep_task5"));
+  OFDM_ARG(!pl->d_wt || n_points <= 1, "ber_sweep_task5: an MMSE-mode plan is built for one SNR (n_points must be 1)");
+  OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task5"));
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  if (n_points == 0) return OFDM_OK;
+  Stage st(flags);
+  TxfSweepOut o;
+  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
+                             o));
+  if (frames_per_point == 0) return st.finish();
+  const int64_t CH = txf_chunk(pl, scr_reg15 != nullptr, true, frames_per_point, max_frames_per_chunk);
+  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
+  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, nullptr,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
+                              return ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
+                                                            (uint32_t*)o.fe + k, nullptr, nullptr,
+                                                            o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags);
+                            }));
+  hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)o.fe,
+                     frames_per_point, (unsigned long long*)o.err);
+  OFDM_TRY(check_launch("ber_point_reduce_kernel"));
+  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
+  return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
+                                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, int flags) {
+  return ofdm_ber_sweep_task5_ex(pl, h, h_len, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15,
+                                 max_frames_per_chunk, errors_out, frame_errors_out, nullptr, nullptr, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
@@ -691,9 +706,7 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4: bad arguments");
   OFDM_ARG(max_frames_per_chunk >= 0 && max_frames_per_chunk <= 65535,
            "ber_sweep_task4: max_frames_per_chunk must be 0..65535 (the limit of rx_chain_task4)");
-  OFDM_ARG(n_points == 0 || (snr_db && seeds), "ber_sweep_task4: snr_db / seeds missing");
-  OFDM_ARG(n_points < ((int64_t)1 << 31), "ber_sweep_task4: too many points");
-  OFDM_TRY(txf_check_plan(pl, flags, frame0, frames_per_point, "ber_sweep_task4"));
+  OFDM_TRY(txf_check_sweep(pl, snr_db, seeds, n_points, frames_per_point, frame0, flags, "ber_sweep_task4"));
   OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "ber_sweep_task4"));
   OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task4"));
   OFDM_ARG(mer_skip >= 0 && mer_skip < (int64_t)pl->nd * pl->n_symb,
@@ -703,25 +716,19 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   if (n_points == 0) return OFDM_OK;
   Stage st(flags);
   const int64_t NF = n_points * frames_per_point;
-  void *derr, *dsc, *dabs, *dfe, *dmer, *dfm;
-  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * (size_t)n_points, &derr));
+  TxfSweepOut o;
+  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
+                             o));
+  void *dsc, *dabs;
   OFDM_TRY(st.out(status_counts_out, sizeof(uint64_t) * 4 * (size_t)n_points, &dsc));
   OFDM_TRY(st.out(cfo_abs_err_out, sizeof(double) * (size_t)n_points, &dabs));
-  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * (size_t)NF, &dfe));
-  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_points, &dmer));
-  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * (size_t)NF, &dfm));
-  const bool mer = dmer || dfm;
   hipStream_t s = ctx().stream;
   if (frames_per_point == 0) {
-    OFDM_HIP(hipMemsetAsync(derr, 0, sizeof(uint64_t) * (size_t)n_points, s));
     if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, s));
     if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, s));
-    if (dmer) OFDM_HIP(hipMemsetAsync(dmer, 0, sizeof(double) * 2 * (size_t)n_points, s));
     return st.finish();
   }
   // the per-frame values of every point, reduced once after the last chunk
-  if (!dfe) OFDM_TRY(st.scratch(sizeof(uint32_t) * (size_t)NF, &dfe));
-  if (mer && !dfm) OFDM_TRY(st.scratch(sizeof(double) * 2 * (size_t)NF, &dfm));
   void *dtg, *dfo, *difo, *dstat, *dsto, *dcfo;
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dtg));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dfo));
@@ -729,42 +736,31 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)NF, &dstat));
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dsto));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dcfo));
-  OFDM_TRY(tx_dict_device(pl));
   const bool scr = scr_reg15 != nullptr;
   // default chunk: the generator workspace and the Task-4 arena (shared with ofdm_task5_part2_tile) budgeted together
   int64_t CH = max_frames_per_chunk;
   if (CH == 0)                                                  // (+ the per-frame MER sums when they are wanted)
     CH = std::max<int64_t>(1, (int64_t)(2 * TXF_WS_BUDGET /
-                                        (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl) + (mer ? 16 : 0))));
+                                        (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl) + (o.fm ? 16 : 0))));
   CH = std::max<int64_t>(1, std::min<int64_t>({CH, frames_per_point, 65535}));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr, true, b, true));
   const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
   TxfImp imp;
   imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      const int64_t o = p * frames_per_point + c0;
-      imp.sto = (int64_t*)dsto + o;
-      imp.cfo = (double*)dcfo + o;
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr, &imp));
-      OFDM_TRY(ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr, (const uint8_t*)b.ref,
-                                      (uint32_t*)dfe + o, (int64_t*)dtg + o, (double*)dfo + o, (int32_t*)difo + o,
-                                      (int32_t*)dstat + o, nullptr, mer_skip, mer ? (double*)dfm + 2 * o : nullptr, rxflags));
-    }
-  }
-  hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const uint32_t*)dfe,
+  imp.sto = (int64_t*)dsto;
+  imp.cfo = (double*)dcfo;
+  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, &imp,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
+                              return ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr,
+                                                            (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
+                                                            (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
+                                                            nullptr, mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
+                                                            rxflags);
+                            }));
+  hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const uint32_t*)o.fe,
                      (const int32_t*)dstat, (const double*)dfo, (const int32_t*)difo, (const double*)dcfo, frames_per_point,
-                     freq_desync ? 1 : 0, (unsigned long long*)derr, (unsigned long long*)dsc, (double*)dabs);
+                     freq_desync ? 1 : 0, (unsigned long long*)o.err, (unsigned long long*)dsc, (double*)dabs);
   OFDM_TRY(check_launch("t4_point_reduce_kernel"));
-  if (dmer) {
-    hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const double*)dfm, frames_per_point,
-                       (double*)dmer);
-    OFDM_TRY(check_launch("t4_point_mer_kernel"));
-  }
+  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
   return st.finish();
 }
 

@@ -6,11 +6,12 @@ T3/Main_model_Task_3.m:237-268).  Here every (snr_idx, batch_idx) tile is one un
 to the ranks (`sweep.tiles_for_rank`), each tile generates its frames on its own GPU (`ofdm_tx_frames`: payload -> TX ->
 multipath -> Noise, Philox streams keyed by the tile, so the table does not depend on the GPU count; nothing is drawn
 or packed on the host), runs `rx_chain_task5`, and adds
-its error / bit counts.  One SUM all-reduce of the int64 counters ends the sweep -- no samples are exchanged.
+its error / bit counts to a device table that is read once.  One SUM all-reduce of the int64 counters (and one of the
+float64 sums, when there are any) ends the sweep -- no samples are exchanged.
 
 --fused (opt-in): the reference's order, Noise -> conv(h) (T5/Task5_part2.m:134,:152), through `RxPlan.ber_sweep`
 (ofdm_ber_sweep_task5: the three-pass generator + the chain + a device reduction, one call for the points a rank holds of a
-batch, the same tile keys); the counters stay in a device tensor and are read once, before the all-reduce.
+batch, the same tile keys).
 
 --config C3: the Task-4 receiver (coarse sync, IFO, fine sync, spline equaliser; T4/Main_model_Task_4.m:99-134,:278-347) on
 frames with a random STO / CFO per frame, through `RxPlan.ber_sweep_task4` (ofdm_ber_sweep_task4), with the same tile keys
@@ -38,7 +39,10 @@ import numpy as np
 
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
         rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False):
-    """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}."""
+    """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}.
+    Per batch of the tiles this rank holds, one call decodes one tile (rx_chain_task5 on make_frames_device frames, or
+    ber_sweep for an MMSE plan, which is built for one SNR) or all of the batch's points (ber_sweep with --fused,
+    ber_sweep_task4 at C3)."""
     import torch
     import ofdm_course_amd as ofdm
     from ofdm_course_amd import frames as fr
@@ -49,119 +53,75 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     cfg = {"C5": fr.config_C5, "M": fr.config_M, "C3": fr.config_C3}[config]()
     snrs = np.arange(0.0, 30.0, 1.5) if snrs is None else np.asarray(snrs, dtype=float)      # 20 points
     plan = fr.make_plan(cfg, ofdm, precision=precision, device=device_index)
+    task4 = config == "C3"
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
     if estimator == "mmse":
-        h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
         hh = np.zeros(cfg.N_carrier, dtype=np.complex128)
         hh[: len(h)] = h
-    if config == "C3":
-        return _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer)
-    counters = sweep.Counters(len(snrs))
-    msum = torch.zeros((len(snrs), 2), dtype=torch.float64, device=dev) if mer else None      # MER_func sums s1, s2
-    t0 = time.perf_counter()
-    n_tiles = 0
-    if fused:
-        h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
-        err = torch.zeros(len(snrs), dtype=torch.int64, device=dev)
-        by_batch = {}
-        for si, bi in sweep.tiles_for_rank(len(snrs), batches, rank, world):
-            by_batch.setdefault(bi, []).append(si)
-        for bi, sis in by_batch.items():
-            keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
-            groups = [[i] for i in range(len(sis))] if estimator == "mmse" else [list(range(len(sis)))]
-            for g in groups:                                   # an MMSE plan is built for one SNR: one point per call
-                if estimator == "mmse":
-                    plan.set_mmse(hh, float(snrs[sis[g[0]]]))
-                out = plan.ber_sweep(snrs[[sis[i] for i in g]], frames_per_tile, h=h, seeds=[keys[i][0] for i in g],
-                                     frame0=keys[g[0]][1], device=dev, want_mer=mer)
-                err[[sis[i] for i in g]] += out["errors"]
-                if mer:
-                    msum[[sis[i] for i in g]] += out["mer_sums"]
-            n_tiles += len(sis)
-            for si in sis:
-                counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
-        counters.errors[:, 0] += err.cpu().numpy()            # the one read of the device counters
-    for si, bi in [] if fused else sweep.tiles_for_rank(len(snrs), batches, rank, world):
-        cfg.SNR_dB = float(snrs[si])
-        key, stream0 = sweep.tile_seed_stream(seed, si, bi, frames_per_tile)
-        data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=key, device=dev, frame0=stream0)
-        if estimator == "mmse":
-            plan.set_mmse(hh, cfg.SNR_dB)
-        out = ofdm.rx_chain_task5(plan, data["rx"], ref_bits_packed=data["packed"], want_mer=mer)
-        counters.add(si, 0, int(out["errors"].sum().item()), frames_per_tile * plan.frame_bits)
-        if mer:
-            msum[si] += out["mer_sums"].sum(dim=0)
-        n_tiles += 1
-    torch.cuda.synchronize()
-    local_s = time.perf_counter() - t0
-    total = sweep.all_reduce_counters(counters, device=dev if backend == "nccl" else None)
-    res = {"config": config, "estimator": estimator, "SNRs": snrs.tolist(), "errors": total.errors[:, 0].tolist(),
-           "bits": total.bits[:, 0].tolist(), "BER": (total.errors[:, 0] / np.maximum(total.bits[:, 0], 1)).tolist(),
-           "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world, "tiles_this_rank": n_tiles,
-           "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
-           **({"order": "noise_first", "fused": True} if fused else {})}
-    if mer:
-        import torch.distributed as dist
-        m = msum.cpu()
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            t = m.to(dev) if backend == "nccl" else m
-            dist.all_reduce(t, op=dist.ReduceOp.SUM)
-            m = t.cpu()
-        m = m.numpy()
-        res["mer_sums"] = m.tolist()
-        res["MER_dB"] = (10.0 * np.log10(m[:, 0] / m[:, 1])).tolist()
-    return res
-
-
-def _run_task4(cfg, plan, snrs, batches, frames_per_tile, precision, seed, rank, world, dev, backend, mer=False):
-    """--config C3: every tile of a batch in one ber_sweep_task4 call, random STO / CFO, all three desync stages on.
-    mer: the MER_func sums {s1, s2} per point (mer_skip = Nfft + T_guard) as two more float64 columns beside the CFO sum."""
-    import torch
-    import torch.distributed as dist
-    import ofdm_course_amd as ofdm
-    from ofdm_course_amd import sweep
-
-    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
-    # columns: bit errors, then frames with status 0, 1, -1, -2 -- one int64 table for the existing all-reduce
-    cnt = torch.zeros((len(snrs), 5), dtype=torch.int64, device=dev)
-    cae = torch.zeros((len(snrs), 3 if mer else 1), dtype=torch.float64, device=dev)     # CFO sum (+ MER s1, s2)
-    counters = sweep.Counters(len(snrs), 5)
+    n = len(snrs)
+    # int64 columns: bit errors (+ C3: frames with receiver status 0, 1, -1, -2); float64 columns: (C3: the sum of
+    # |FreqOffset + IFO - Freq_Shift|) (+ mer: the MER_func sums s1, s2) -- one device table each, read once
+    cnt = torch.zeros((n, 5 if task4 else 1), dtype=torch.int64, device=dev)
+    flt = torch.zeros((n, int(task4) + (2 if mer else 0)), dtype=torch.float64, device=dev)
+    counters = sweep.Counters(n, cnt.shape[1])
     t0 = time.perf_counter()
     n_tiles = 0
     by_batch = {}
-    for si, bi in sweep.tiles_for_rank(len(snrs), batches, rank, world):
+    for si, bi in sweep.tiles_for_rank(n, batches, rank, world):
         by_batch.setdefault(bi, []).append(si)
     for bi, sis in by_batch.items():
         keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
-        out = plan.ber_sweep_task4(snrs[sis], frames_per_tile, h=h, Time_Delay="random", Freq_Shift="random",
-                                   seeds=[k[0] for k in keys], frame0=keys[0][1], device=dev, want_mer=mer,
-                                   mer_skip=cfg.Nfft + cfg.T_guard)
-        cnt[sis, 0] += out["errors"]
-        cnt[sis, 1:] += out["status_counts"]
-        cae[sis, 0] += out["cfo_abs_err"]
-        if mer:
-            cae[sis, 1:] += out["mer_sums"]
+        whole = task4 or (fused and estimator != "mmse")
+        for g in [list(range(len(sis)))] if whole else [[i] for i in range(len(sis))]:
+            pts = [sis[i] for i in g]
+            seeds, stream0 = [keys[i][0] for i in g], keys[g[0]][1]
+            if task4:                                          # random STO / CFO, all three desync stages on
+                out = plan.ber_sweep_task4(snrs[pts], frames_per_tile, h=h, Time_Delay="random", Freq_Shift="random",
+                                           seeds=seeds, frame0=stream0, device=dev, want_mer=mer,
+                                           mer_skip=cfg.Nfft + cfg.T_guard)
+                cnt[pts, 1:] += out["status_counts"]
+                flt[pts, 0] += out["cfo_abs_err"]
+                errors, mer_sums = out["errors"], out.get("mer_sums")
+            elif fused:
+                if estimator == "mmse":
+                    plan.set_mmse(hh, float(snrs[pts[0]]))
+                out = plan.ber_sweep(snrs[pts], frames_per_tile, h=h, seeds=seeds, frame0=stream0, device=dev, want_mer=mer)
+                errors, mer_sums = out["errors"], out.get("mer_sums")
+            else:
+                cfg.SNR_dB = float(snrs[pts[0]])
+                data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=seeds[0], device=dev, frame0=stream0)
+                if estimator == "mmse":
+                    plan.set_mmse(hh, cfg.SNR_dB)
+                out = ofdm.rx_chain_task5(plan, data["rx"], ref_bits_packed=data["packed"], want_mer=mer)
+                errors, mer_sums = out["errors"].sum(), out["mer_sums"].sum(dim=0) if mer else None
+            cnt[pts, 0] += errors
+            if mer:
+                flt[pts, -2:] += mer_sums
         n_tiles += len(sis)
         for si in sis:
             counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
-    counters.errors += cnt.cpu().numpy()                      # the one read of the device counters
-    cfo = cae.cpu()
+    counters.errors += cnt.cpu().numpy()
+    sums = flt.cpu().numpy()
     torch.cuda.synchronize()
     local_s = time.perf_counter() - t0
-    total = sweep.all_reduce_counters(counters, device=dev if backend == "nccl" else None)
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        t = cfo.to(dev) if backend == "nccl" else cfo
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        cfo = t.cpu()
+    on = dev if backend == "nccl" else None
+    total = sweep.all_reduce_counters(counters, device=on)
+    sums = sweep.all_reduce_sums(sums, device=on)
     errors, bits = total.errors[:, 0], total.bits[:, 0]
-    flt = cfo.numpy()
-    res = {"config": "C3", "estimator": "task4", "SNRs": snrs.tolist(), "errors": errors.tolist(), "bits": bits.tolist(),
-           "BER": (errors / np.maximum(bits, 1)).tolist(), "status_counts": total.errors[:, 1:].tolist(),
-           "cfo_abs_err": flt[:, 0].tolist(), "batches": batches, "frames_per_tile": frames_per_tile, "n_gpus": world,
-           "tiles_this_rank": n_tiles, "seconds_this_rank": local_s, "dtype": "f32" if precision == "fp32" else "f64",
-           "order": "noise_first", "impairments": {"Time_Delay": "random", "Freq_Shift": "random"}}
+    res = {"config": config, "estimator": "task4" if task4 else estimator, "SNRs": snrs.tolist(), "errors": errors.tolist(),
+           "bits": bits.tolist(), "BER": (errors / np.maximum(bits, 1)).tolist()}
+    if task4:
+        res.update(status_counts=total.errors[:, 1:].tolist(), cfo_abs_err=sums[:, 0].tolist())
+    res.update(batches=batches, frames_per_tile=frames_per_tile, n_gpus=world, tiles_this_rank=n_tiles,
+               seconds_this_rank=local_s, dtype="f32" if precision == "fp32" else "f64")
+    if task4:
+        res.update(order="noise_first", impairments={"Time_Delay": "random", "Freq_Shift": "random"})
+    elif fused:
+        res.update(order="noise_first", fused=True)
     if mer:
-        res["mer_sums"] = flt[:, 1:].tolist()
-        res["MER_dB"] = (10.0 * np.log10(flt[:, 1] / flt[:, 2])).tolist()
+        m = sums[:, -2:]
+        res["mer_sums"] = m.tolist()
+        res["MER_dB"] = (10.0 * np.log10(m[:, 0] / m[:, 1])).tolist()
     return res
 
 

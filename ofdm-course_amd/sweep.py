@@ -74,3 +74,17 @@ def all_reduce_counters(counters: Counters, device=None) -> Counters:
     out.errors[:] = t[0]
     out.bits[:] = t[1]
     return out
+
+
+def all_reduce_sums(sums: np.ndarray, device=None) -> np.ndarray:
+    """SUM all-reduce of float64 sums (a sweep's MER and CFO sums) over the default process group (no-op when it is not
+    initialised or there is nothing to reduce).  Unlike the integer counters, the last bits can depend on the order."""
+    import torch
+    import torch.distributed as dist
+    if sums.size == 0 or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return sums
+    t = torch.tensor(sums, dtype=torch.float64)
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.cpu().numpy()

@@ -30,11 +30,13 @@ def _worker(rank, world, port, n_snr, n_batches, q):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     c = sweep.Counters(n_snr)
+    f = np.zeros((n_snr, 2))
     for s, b in sweep.tiles_for_rank(n_snr, n_batches, rank, world):
         e, n = _tile_result(s, b)
         c.add(s, 0, e, n)
+        f[s] += (e / 4, b)                  # float sums exact in any order
     tot = sweep.all_reduce_counters(c)
-    q.put((rank, tot.errors.copy(), tot.bits.copy()))
+    q.put((rank, tot.errors.copy(), tot.bits.copy(), sweep.all_reduce_sums(f)))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -53,13 +55,15 @@ def test_two_rank_sweep_matches_single_process():
         assert p.exitcode == 0
     want_e = np.zeros((n_snr, 1), np.int64)
     want_n = np.zeros((n_snr, 1), np.int64)
+    want_f = np.zeros((n_snr, 2))
     for s in range(n_snr):
         for b in range(n_batches):
             e, n = _tile_result(s, b)
             want_e[s, 0] += e
             want_n[s, 0] += n
-    for _, e, n in res:                 # every rank holds the global totals, bit-identical
-        assert np.array_equal(e, want_e) and np.array_equal(n, want_n)
+            want_f[s] += (e / 4, b)
+    for _, e, n, f in res:              # every rank holds the global totals, bit-identical
+        assert np.array_equal(e, want_e) and np.array_equal(n, want_n) and np.array_equal(f, want_f)
 
 
 def test_bench_parent_reports_a_failed_rank_instead_of_hanging():
