@@ -1,0 +1,227 @@
+"""Every dispatch route of the Task-5 receiver (ofdm_rx_chain_task5_ex) against the oracle: one test per row of
+routes.CASES.  The frames are the plan's own Philox frames in the reference's channel order (oracle.tx_frame restates them,
+test_gpu_txgen.py); the `want` side is oracle.rx_chain_task5, or in MMSE mode the function-by-function composition
+OFDM_demodulator -> MMSE_CE -> equalize_signal -> get_payload -> demapping [-> DeScrambler].
+
+Rules (the suite's existing ones): fp64 -- picks, bits and error counts equal, rel_l2(H) < 1e-9; fp32 -- rel_l2(H) < 2e-4, every
+differing decision a boundary point (flip_audit.py), every pick the arg-max or a near-tie (pick_audit.py), at most 2 * n_frames
+flipped decisions, at most `set_aside` frames (0 in every case: routes.GAPS) set aside for a near-tied pick; always -- the error
+counter is the popcount of the call's own bits against the reference and the padding bits are zero; MER sums with the tolerances
+of test_gpu_mer_task5.py.  Switch-only cases are also compared with the route without the switch: fp64 bit for bit (H too, except where the
+switch changes the arithmetic: the bound stands at the case), fp32 within the bounds of test_chain_one_pass_8192_any_layout."""
+import numpy as np
+import pytest
+
+import routes
+from conftest import rel_l2
+from flip_audit import decision_flip_audit
+from pick_audit import omp_pick_audit
+from routes import CASES, REFUSALS, REG
+
+pytestmark = pytest.mark.gpu
+
+
+def _set_env(monkeypatch, env):
+    for v in sorted(routes.dispatch_switches(excluded=True) | set(routes.EXTRA_SWITCHES)):
+        monkeypatch.delenv(v, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _h_for_mmse(ofdm, cfg):
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    hh = np.zeros(cfg.N_carrier, dtype=np.complex128)
+    hh[: len(h)] = h
+    return hh
+
+
+def _frames(ofdm, oracle, case, cfg):
+    from ofdm_course_amd import frames as fr
+    if np.any(case.pilot_carriers() > case.nc):
+        # the plan's generator refuses pilots outside 1..N_carrier: the same frames from the oracle's TX chain (routes.py)
+        rx, bits, _ = routes.oracle_frames(case, oracle)
+        return rx.astype(np.complex128 if case.precision == "fp64" else np.complex64), bits, fr.pack_bits(bits)
+    plan = fr.make_plan(cfg, ofdm, precision=case.precision)
+    h, _ = oracle.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    gen = plan.tx_frames(case.n_frames, h=h, SNR=case.snr, seed=case.seed, frame0=0, want_bits=True,
+                         Register=REG if case.descr else None, noise_first=True)
+    plan.close()
+    return np.asarray(gen["rx"]), np.asarray(gen["bits"]), np.asarray(gen["packed"])
+
+
+def _call(ofdm, monkeypatch, case, cfg, env, rx, packed):
+    """One rx_chain_task5 call of the case under `env`, on a plan of its own (the MMSE switches are read when the operator is
+    built)."""
+    from ofdm_course_amd import frames as fr
+    _set_env(monkeypatch, env)
+    plan = fr.make_plan(cfg, ofdm, precision=case.precision)
+    if case.mode == "mmse":
+        plan.set_mmse(_h_for_mmse(ofdm, cfg), cfg.SNR_dB)
+    if case.descr:
+        plan.set_descrambler(REG)
+    out = ofdm.rx_chain_task5(plan, rx, ref_bits_packed=packed, want_h=True, want_index=case.mode == "omp", want_mer=case.mer)
+    nb, nbytes = plan.frame_bits, plan.frame_bytes
+    plan.close()
+    res = dict(bits=fr.unpack_bits(np.asarray(out["bits"]), nb), pad=fr.unpack_bits(np.asarray(out["bits"]), nbytes * 8)[:, nb:],
+               errors=np.asarray(out["errors"]).astype(np.int64), H=np.asarray(out["H"]).T.copy(),
+               index=np.asarray(out["index"]).T.copy() if case.mode == "omp" else None,
+               mer=np.asarray(out["mer_sums"]).copy() if case.mer else None, packed=np.asarray(out["bits"]).copy())
+    return res
+
+
+def _mer_sums(oracle, iq, raw_bits01, const):
+    """MER_func.m:19-23 over the oracle's RX_IQ with ideal = the point of the decision the kernel made (test_gpu_mer_task5.py)."""
+    D, bps = oracle.constellation_func(const)
+    b = np.asarray(raw_bits01, dtype=np.int64)[: iq.size * bps].reshape(iq.size, bps)
+    ideal = D[b @ (1 << np.arange(bps - 1, -1, -1))]
+    return np.array([np.sum(ideal.real ** 2 + ideal.imag ** 2), np.sum((ideal - iq).real ** 2 + (ideal - iq).imag ** 2)])
+
+
+def _check_mer(got, want, n, precision, what):
+    got = np.asarray(got, dtype=np.float64)
+    print(f"{what}: MER sums {got} (oracle {want})")
+    if precision == "fp64":
+        assert np.allclose(got, want, rtol=1e-9, atol=0), (what, got, want)
+    else:
+        assert np.all(np.abs(got - want) <= 1e-4 * np.abs(want) + 1e-6 * n), (what, got, want)
+
+
+@pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)
+def test_route_matches_oracle(ofdm, oracle, monkeypatch, case):
+    from ofdm_course_amd import frames as fr
+    cfg = case.cfg()
+    nfr, f64, const = case.n_frames, case.precision == "fp64", case.const
+    _set_env(monkeypatch, {})
+    rx, tx_bits, packed = _frames(ofdm, oracle, case, cfg)
+    got = _call(ofdm, monkeypatch, case, cfg, case.env, rx, packed)
+    rx64 = rx.astype(np.complex128)
+    pv_col = np.asarray(fr.pilot_column(cfg, ofdm))
+    n_iq = len(cfg.dataCarriers) * cfg.N_symb
+
+    # ---- always: the counter is the popcount of this call's own bits, the padding is zero
+    assert np.array_equal(got["errors"], np.count_nonzero(got["bits"] != tx_bits, axis=1))
+    assert not got["pad"].any()
+
+    # the raw decisions of the call (a descrambling plan: Scrambler inverts DeScrambler exactly, register reset per frame)
+    raw_got = np.stack([oracle.Scrambler_fast(REG, got["bits"][f])[0] for f in range(nfr)]) if case.descr else got["bits"]
+
+    keep = list(range(nfr))                                   # frames compared with the oracle's decisions
+    if case.mode == "omp":
+        ref = oracle.rx_chain_task5(rx64, cfg.Nfft, cfg.T_guard, cfg.N_carrier, cfg.pilotCarriers, cfg.dataCarriers, pv_col,
+                                    cfg.K, cfg.dominant_taps, const, want_iq=True)
+        raw_want, iq, H_want = ref["bits"], ref["iq"], ref["H"]
+        idx = got["index"]
+        if f64:
+            for f in range(nfr):
+                want = list(ref["index"][f])
+                assert list(idx[f][: len(want)]) == want and not idx[f][len(want):].any(), f
+        else:
+            Smat = oracle.sensing_matrix(cfg.pilotCarriers, cfg.Nfft, cfg.K)
+            pc = np.asarray(cfg.pilotCarriers, int) - 1
+            L = cfg.Nfft + cfg.T_guard
+            keep = []
+            for f in range(nfr):
+                picks = [int(k) for k in idx[f] if k > 0]
+                X1 = oracle.OFDM_demodulator(rx64[:L, f][:, None], cfg.T_guard)
+                near, H_refit = omp_pick_audit(oracle, X1[pc, 0] / pv_col, Smat, picks, cfg.Nfft)
+                assert rel_l2(got["H"][f], H_refit[:cfg.N_carrier]) < 2e-4, f
+                if near == 0:
+                    want = list(ref["index"][f])
+                    assert picks == want and not idx[f][len(want):].any(), (f, picks, want)
+                    keep.append(f)
+            print(f"{case.name}: {nfr - len(keep)} frames with a near-tied pick")
+            assert nfr - len(keep) <= case.set_aside
+    else:
+        pv = np.repeat(pv_col[:, None], cfg.N_symb, axis=1)
+        hh = _h_for_mmse(ofdm, cfg)
+        raw_want = np.zeros_like(got["bits"])
+        iq = np.zeros((nfr, n_iq), dtype=np.complex128)
+        H_want = np.zeros((nfr, cfg.N_carrier), dtype=np.complex128)
+        for f in range(nfr):
+            X = oracle.OFDM_demodulator(rx64[:, f].reshape((cfg.Nfft + cfg.T_guard, cfg.N_symb), order="F"), cfg.T_guard)
+            Hm = oracle.MMSE_CE(X, pv, cfg.pilotCarriers, cfg.Nfft, cfg.N_carrier, hh, cfg.SNR_dB)
+            H_want[f] = Hm[0] if isinstance(Hm, tuple) else Hm
+            iq[f] = oracle.get_payload(oracle.equalize_signal(X, H_want[f], cfg.N_carrier), cfg.dataCarriers).ravel(order="F")
+            raw_want[f] = np.asarray(oracle.demapping(0, iq[f], const)).ravel()
+
+    err_H = rel_l2(got["H"][keep], H_want[keep])
+    print(f"{case.name}: rel_l2(H) {err_H:.3g}")
+    assert err_H < (1e-9 if f64 else 2e-4)
+    if f64:
+        want_bits = np.stack([oracle.DeScrambler_fast(REG, raw_want[f])[0] for f in range(nfr)]) if case.descr else raw_want
+        assert np.array_equal(got["bits"], want_bits)
+        assert np.array_equal(got["errors"], np.count_nonzero(want_bits != tx_bits, axis=1))
+    else:
+        flips = 0
+        for f in keep:
+            flips += decision_flip_audit(oracle, raw_got[f], raw_want[f], iq[f], const, what=f"{case.name} frame {f}")[0]
+        print(f"{case.name}: {flips} boundary decisions differ from the oracle's")
+        assert flips <= 2 * nfr
+    if case.mer:
+        for f in keep:
+            if case.mode == "mmse" and not f64:
+                # RX_IQ of the estimate the call returned (test_gpu_mer_task5.py: _run_and_check), itself checked above
+                X = oracle.OFDM_demodulator(rx64[:, f].reshape((cfg.Nfft + cfg.T_guard, cfg.N_symb), order="F"), cfg.T_guard)
+                z = oracle.get_payload(oracle.equalize_signal(X, got["H"][f].astype(np.complex128), cfg.N_carrier),
+                                       cfg.dataCarriers).ravel(order="F")
+            else:
+                z = iq[f]
+            _check_mer(got["mer"][f], _mer_sums(oracle, z, raw_got[f], const), n_iq, case.precision, f"{case.name} frame {f}")
+
+    # ---- a switch-only route against the route without the switch, on the same frames
+    if case.base_env is not None:
+        base = _call(ofdm, monkeypatch, case, cfg, case.base_env, rx, packed)
+        if f64:
+            assert got["packed"].tobytes() == base["packed"].tobytes() and np.array_equal(got["errors"], base["errors"])
+            d = rel_l2(got["H"], base["H"])
+            print(f"{case.name}: against the base route rel_l2(H) {d:.3g}")
+            if case.h_tol64 is None:                              # the switch keeps the arithmetic: H bit for bit
+                assert got["H"].tobytes() == base["H"].tobytes()
+            else:                                                 # another transform / correlation: the bound written at the case
+                assert d < case.h_tol64
+            if case.mode == "omp":
+                assert np.array_equal(got["index"], base["index"])
+        else:
+            d = rel_l2(got["H"], base["H"])
+            nflip = np.count_nonzero(got["bits"] != base["bits"])
+            print(f"{case.name}: against the base route rel_l2(H) {d:.3g}, {nflip} bits differ")
+            assert d < 2e-5
+            assert nflip <= 2 * nfr
+            if case.mode == "omp":
+                assert np.array_equal(got["index"], base["index"])
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=lambda c: c.name)
+def test_route_refusals(ofdm, oracle, monkeypatch, case):
+    """Host-side argument errors: the message is the one of the cited line, the stage whose LDS need is over its limit is not
+    launched, and the plan (and the library) keep working afterwards.  (refuse-omp-lds: launch_fast has already launched
+    rx_pilot_kernel when omp_batch_run refuses, ofdm_chain_fast.hip:498-511 -- the call ends with a half-run front end, whose
+    workspace the next call overwrites.)"""
+    from ofdm_course_amd import frames as fr
+    with pytest.raises(routes.Refused) as model:
+        case.route()
+    assert model.value.where == routes.REFUSAL_LINES[case.name]
+    cfg = case.cfg()
+    _set_env(monkeypatch, {})
+    plan = fr.make_plan(cfg, ofdm, precision=case.precision)
+    rx, tx_bits, packed = _frames(ofdm, oracle, case, cfg)
+    _set_env(monkeypatch, case.env)
+    if case.mode == "mmse":
+        plan.set_mmse(_h_for_mmse(ofdm, cfg), cfg.SNR_dB)
+    for _ in range(2):                                            # refused every time, with the same message
+        with pytest.raises(ofdm.OfdmError) as e:
+            ofdm.rx_chain_task5(plan, rx, ref_bits_packed=packed, want_h=True)
+        assert model.value.fragment in str(e.value), str(e.value)
+    # afterwards: the same plan on a route that accepts it
+    if case.name == "refuse-mmse-oob":
+        plan.set_mmse(None)                                       # OMP mode: the generic kernel
+    elif case.name == "refuse-generic-lds":
+        _set_env(monkeypatch, {})                                 # without the switch: the split form
+    else:
+        _set_env(monkeypatch, {"OFDM_CHAIN_GENERIC": "1"})        # the generic kernel has its pursuit inside: no OMP stage
+    out = ofdm.rx_chain_task5(plan, rx, ref_bits_packed=packed, want_h=True)
+    bits = fr.unpack_bits(np.asarray(out["bits"]), plan.frame_bits)
+    errs = np.asarray(out["errors"]).astype(np.int64)
+    assert np.array_equal(errs, np.count_nonzero(bits != tx_bits, axis=1))
+    assert errs.sum() < 0.05 * tx_bits.size and np.isfinite(np.asarray(out["H"])).all()
+    plan.close()
