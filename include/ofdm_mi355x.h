@@ -307,6 +307,40 @@ int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* plan, const void* h, int h_len, const 
                             int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
                             double* mer_sums_out /* [n_points][2] */,
                             double* frame_mer_sums_out /* [n_points][frames_per_point][2] */, int flags);
+/* ofdm_tx_frames_fused with a channel drawn per frame on one tap-delay line -- the Monte-Carlo realisations of
+ * T5/Task5_part2.m:148-155, static taps with random initial phases and unit power standing in for lteFadingChannel:
+ *   tap_delay[n_taps] (HOST int32): 0-based sample delays, distinct, each 0 .. 4096;
+ *   tap_power[n_taps] (HOST double): linear powers, > 0;  n_taps: 1 .. 64.
+ * Draw convention: tap t of frame f uses Philox4x32-10 with counter (t, 0, frame0 + f, 3) and key = seed (counter word 3 is
+ * 0 for the noise, 1 for the payload, 2 for STO / CFO); u = (word0 + 0.5) 2^-32;
+ *   a_{f,t} = g_t (cospi(2u) + i sinpi(2u)) in double,  g_t = sqrt(tap_power[t] / sum tap_power) (host, double);
+ *   rx_f[n] = sum_t a_{f,t} w_f[n - tap_delay[t]], the amplitudes cast to the precision of `flags` as h is.
+ * taps_out (optional): [n_frames][n_taps] interleaved complex double, the amplitudes a_{f,t}, where `flags` says.
+ * Everything else -- the order payload -> [Scrambler] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(snr_db) ->
+ * conv(h_f) truncated, the payload and noise draws, the outputs -- is ofdm_tx_frames_fused's.  No STO / CFO.  Results depend
+ * on (seed, frame0 + f, t) only, never on the batching. */
+int ofdm_tx_frames_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps, double snr_db,
+                          uint64_t seed, int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, void* rx_out,
+                          uint8_t* ref_bits_out, uint8_t* sc_ref_bits_out, double* taps_out /* [n_frames][n_taps][2] */,
+                          int flags);
+/* ofdm_ber_sweep_task5_ex over channel realisations: the frames of point p are those of ofdm_tx_frames_fading(tap_delay,
+ * tap_power, n_taps, snr_db[p], seeds[p], ...), each with its own channel, and the error of the receiver's channel estimate is
+ * summed beside the bit errors (T5/Task5_part2.m:202-205, :309-318).  Per frame
+ *   frame_nmse_out[n_points][frames_per_point] (double, optional) = sum_{k=0}^{N_carrier-1} |H_f(k) - Hest_f(k)|^2 with
+ *   H_f(k) = sum_t a_{f,t} exp(-2 pi i tap_delay[t] k / Nfft) (= fft(h_f, Nfft) of get_MP_channel_resp, in double) and Hest_f
+ *   the h_out of ofdm_rx_chain_task5;
+ *   nmse_sums_out[n_points] (double, optional) = the point's sum; its NMSE is nmse_sums / (frames_per_point * N_carrier).
+ * Both are summed in a fixed order without atomics (per frame: thread i of 256 takes carriers i, i + 256, ..., a butterfly
+ * over each wavefront, the four partials as (p0 + p1) + (p2 + p3); per point the same over the frames, after the last chunk):
+ * bitwise independent of max_frames_per_chunk.  An MMSE-mode plan is refused (its operator is built for one h).  The other
+ * arguments, outputs and rules are those of ofdm_ber_sweep_task5_ex; with both NMSE outputs NULL no estimate is stored. */
+int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,
+                                int64_t frame0, const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                                uint32_t* frame_errors_out, double* mer_sums_out /* [n_points][2] */,
+                                double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
+                                double* nmse_sums_out /* [n_points] */,
+                                double* frame_nmse_out /* [n_points][frames_per_point] */, int flags);
 /* ofdm_tx_frames_fused with the Task-4 impairments, in the reference order (T4/Main_model_Task_4.m:94-110,:257-267,
  * T5/Noise.m:3-10, T5/add_STO.m, T5/add_CFO.m): per frame f of length len = (Nfft + T_guard) * N_symb
  *   w[j] = x[j] + sigma_f n(j)            the noise of Noise.m, Philox counter (j, 0, frame0 + f, 0) of the SOURCE index j

@@ -86,6 +86,8 @@ SIGNATURES = {
     "ofdm_tx_frames_fused": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task5": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i],
     "ofdm_ber_sweep_task5_ex": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i],
+    "ofdm_tx_frames_fading": [_vp, _vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_ber_sweep_task5_fading": [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_tx_frames_fused_ex": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task4": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
                              _vp, _i],

@@ -747,6 +747,24 @@ class RxPlan:
         pr = reg.ctypes.data_as(C.c_void_p) if reg is not None else None
         return (hh, reg), ph, 0 if hh is None else hh.size, pr
 
+    @staticmethod
+    def _fading_args(h, fading, what):
+        """fading=(delays, powers) of a tap-delay line -> (kept arrays, delay pointer, power pointer, n_taps)."""
+        if h is not None:
+            raise OfdmError(f"{what}: give h= (one channel for every frame) or fading= (a channel per frame), not both")
+        try:
+            delays, powers = fading
+        except (TypeError, ValueError):
+            raise OfdmError(f"{what}: fading must be (delays, powers)") from None
+        dl = np.asarray(delays).ravel()
+        if dl.size and not np.all(dl == np.rint(dl)):
+            raise OfdmError(f"{what}: fading delays must be whole samples")
+        dl = np.ascontiguousarray(dl.astype(np.int32))
+        pw = np.ascontiguousarray(np.asarray(powers, dtype=np.float64).ravel())
+        if pw.size != dl.size:
+            raise OfdmError(f"{what}: fading needs one power per delay")
+        return (dl, pw), dl.ctypes.data_as(C.c_void_p), pw.ctypes.data_as(C.c_void_p), int(dl.size)
+
     def _outputs(self, device, *specs):
         """Row-major outputs of one plan call, one per (shape, numpy dtype) spec, None for an output not wanted: torch
         tensors on `device` (the call runs on its current stream) when it is given, numpy arrays on the default stream
@@ -772,7 +790,7 @@ class RxPlan:
         return snr, sd
 
     def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None, Time_Delay=None,
-                        Freq_Shift=None, want_draws=False):
+                        Freq_Shift=None, want_draws=False, fading=None, want_taps=False):
         """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
         frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(SNR) -> conv(h) truncated
         (T5/Main_model_Task_5.m:50-127, T5/Task5_part2.m:134,:152).  The draws of tx_frames(noise_first=True): the same
@@ -782,8 +800,19 @@ class RxPlan:
         (ofdm_tx_frames_fused_ex, T4:94-110); want_draws returns the per-frame values.
         Returns dict(rx=[frame_samples, n_frames], packed=[n_frames, frame_bytes] (the payload bits)
         (+ sc_packed = the scrambled bits when Register is given) (+ Time_Delay [n_frames] int64, Freq_Shift [n_frames]
-        float64 with want_draws)); torch CUDA tensors when `device` is given."""
+        float64 with want_draws)); torch CUDA tensors when `device` is given.
+        fading=(delays, powers) (ofdm_tx_frames_fading; not with h, Time_Delay or Freq_Shift): a channel per frame on one
+        tap-delay line -- 0-based distinct sample delays and linear powers (drivers.common.fading_profile gives the 3GPP
+        ones) -- the stand-in for lteFadingChannel of T5/Task5_part2.m:148-155: tap t of frame f is sqrt(powers[t] /
+        sum(powers)) e^{2 pi i u} with u from Philox counter (t, 0, frame0 + f, 3), key `seed`.  want_taps adds
+        taps=[n_frames, n_taps] complex128, those amplitudes."""
         n_frames = int(n_frames)
+        if fading is not None:
+            if Time_Delay is not None or Freq_Shift is not None or want_draws:
+                raise OfdmError("tx_frames_fused: fading does not combine with Time_Delay / Freq_Shift")
+            return self._tx_frames_fading(n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps)
+        if want_taps:
+            raise OfdmError("tx_frames_fused: want_taps needs fading")
         ex = Time_Delay is not None or Freq_Shift is not None or want_draws
         scr = Register is not None
         (rx, packed, scp, sto, cfo), ptrs, flags = self._outputs(
@@ -806,8 +835,26 @@ class RxPlan:
             out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
+    def _tx_frames_fading(self, n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps):
+        keep_f, pdl, ppw, nt = self._fading_args(h, fading, "tx_frames_fused")
+        scr = Register is not None
+        (rx, packed, scp, taps), ptrs, flags = self._outputs(
+            device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
+            ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bytes), np.uint8) if scr else None,
+            ((n_frames, nt), np.complex128) if want_taps else None)
+        keep, _, _, pr = self._fused_args(None, Register, "tx_frames_fused")
+        L.check(self.lib.ofdm_tx_frames_fading(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames, pr,
+                                               *ptrs, flags), "tx_frames_fading")
+        out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
+        if scr:
+            out["sc_packed"] = scp
+        if want_taps:
+            out["taps"] = taps
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
-                  want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False):
+                  want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
+                  want_nmse=False, want_frame_nmse=False):
         """One device-resident tile of a BER(SNR) sweep (ofdm_ber_sweep_task5): for every SNR of `SNRs` the frames
         frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p]) decoded by rx_chain_task5 on this plan
         (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152).  seeds: one Philox key per point (default: `seed`
@@ -818,20 +865,39 @@ class RxPlan:
         numpy arrays otherwise.
         want_mer (ofdm_ber_sweep_task5_ex): also mer_sums=[n, 2], the MER_func sums of each point's frames (the whole RX_IQ,
         frames concatenated; T5/Main_model_Task_5.m:282), and MER_dB=[n] (computed on `device` when it is given); with
-        want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2]."""
+        want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2].
+        fading=(delays, powers) (ofdm_ber_sweep_task5_fading; not with h): the frames of tx_frames_fused(fading=...), a channel
+        realisation per frame (T5/Task5_part2.m:148-155).  want_nmse then adds nmse_sums=[n], per point the sum over its frames
+        of sum_k |fft(h_f, Nfft)(k) - H_est_f(k)|^2 on carriers 1..N_carrier, and NMSE=[n] = nmse_sums / (frames_per_point *
+        N_carrier) (T5/Task5_part2.m:202-205,:318); want_frame_nmse the per-frame sums frame_nmse=[n, frames_per_point]."""
         if want_frame_mer and not want_mer:
             raise OfdmError("ber_sweep: want_frame_mer needs want_mer")
+        if (want_nmse or want_frame_nmse) and fading is None:
+            raise OfdmError("ber_sweep: want_nmse / want_frame_nmse need fading")
         snr, sd = self._points(SNRs, seeds, seed, "ber_sweep")
         n, fpp = snr.size, int(frames_per_point)
-        (err, fe, ms, fm), ptrs, flags = self._outputs(
+        (err, fe, ms, fm, ns, fn), ptrs, flags = self._outputs(
             device, ((n,), np.uint64), ((n, fpp), np.uint32) if want_frame_errors else None,
-            ((n, 2), np.float64) if want_mer else None, ((n, fpp, 2), np.float64) if want_frame_mer else None)
-        keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
-        L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
-                                                 sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                 int(max_frames_per_chunk), *ptrs, flags),
-                "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
+            ((n, 2), np.float64) if want_mer else None, ((n, fpp, 2), np.float64) if want_frame_mer else None,
+            ((n,), np.float64) if want_nmse else None, ((n, fpp), np.float64) if want_frame_nmse else None)
+        if fading is not None:
+            keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep")
+            keep, _, _, pr = self._fused_args(None, Register, "ber_sweep")
+            L.check(self.lib.ofdm_ber_sweep_task5_fading(self.handle, pdl, ppw, nt, snr.ctypes.data_as(C.c_void_p),
+                                                         sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                         int(max_frames_per_chunk), *ptrs, flags), "ber_sweep_task5_fading")
+        else:
+            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
+            L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
+                                                     sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                     int(max_frames_per_chunk), *ptrs[:4], flags),
+                    "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
         out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
+        if want_nmse:
+            out["nmse_sums"] = ns
+            out["NMSE"] = ns / float(max(fpp, 1) * self.N_carrier)
+        if want_frame_nmse:
+            out["frame_nmse"] = fn
         if want_frame_errors:
             out["frame_errors"] = fe
         if want_mer:

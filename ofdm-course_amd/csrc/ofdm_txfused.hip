@@ -27,12 +27,24 @@
 //   t4_point_mer_kernel             per-frame MER_func sums -> per-point sums in the same fixed order (both sweeps with MER).
 // The per-frame draws are tx_draw_kernel's (ofdm_txgen.hip), the draws of ofdm_tx_frames_ex.
 //
+// ofdm_tx_frames_fading / ofdm_ber_sweep_task5_fading draw a channel per frame (the Monte-Carlo realisations of
+// T5/Task5_part2.m:148-155) on one tap-delay line, still in three sample passes:
+//   tx_fade_draw_kernel             tap t of frame f: a = g_t e^{2 pi i u}, u from Philox counter (t, 0, frame0 + f, 3), double
+//   tx_channel_fade_kernel<T>       tx_channel_body with FADE on: the delays and the halo stay in the kernel arguments (uniform
+//                                   over the launch), the amplitudes of frame blockIdx.y are read once per workgroup into the
+//                                   tail of the dynamic LDS, cast to T as the static path casts h
+//   t5_frame_nmse_kernel<T>         one workgroup per frame: H_f(k) = sum_t a_t e^{-2 pi i d_t k / Nfft} in double (the phase
+//                                   d_t k mod Nfft reduced in integers), sum_k |H_f(k) - Hest_f(k)|^2 over 1..N_carrier in a
+//                                   fixed order (T5/Task5_part2.m:202-205); the points through t4_point_mer_kernel<1>
+//
 // Host side: both generator entries forward to one body (txf_frames); given impairments it launches the draw kernel and
 // tx_channel_imp_kernel, else tx_channel_fused_kernel.  The two sweeps share their common checks and outputs
 // (txf_check_sweep, txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points, the receiver
 // passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
-// per-point reduction.
+// per-point reduction.  The fading entries share those bodies: txf_frames / txf_sweep_points given a TxfFade launch
+// tx_fade_draw_kernel and tx_channel_fade_kernel, and both Task-5 sweep entries forward to t5_sweep.
 #include <algorithm>
+#include <cmath>
 #include <type_traits>
 
 #include "fft_core.hpp"
@@ -166,11 +178,14 @@ __device__ __forceinline__ cx<T> txf_noisy(cx<T> v, int64_t i, double sg, uint32
 //   w[j] = x[j] + sigma n(j)   s[m] = w[m + sto] (0 outside the frame, add_STO.m, either sign)
 //   z[m] = s[m] exp(2 pi i cfo m / Nfft)   (add_CFO.m on the shifted stream; the arithmetic of sto_cfo_frames_kernel)
 // ---------------------------------------------------------------------------------------------
-template <typename T, bool IMP>
+// FADE: the taps' amplitudes are those of the frame, famp[f][taps.n] (complex double, tx_fade_draw_kernel), staged behind the
+// segment in LDS; taps.amp is not read.
+template <typename T, bool IMP, bool FADE = false>
 __device__ __forceinline__ void tx_channel_body(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
                                                 const double* __restrict__ partial, int n_symb, int64_t len, double snr_lin,
                                                 uint32_t k0, uint32_t k1, uint32_t stream0, const int64_t* __restrict__ sto,
-                                                const double* __restrict__ cfo, double inv_nfft, const TxfTaps<T>& taps) {
+                                                const double* __restrict__ cfo, double inv_nfft, const TxfTaps<T>& taps,
+                                                const c64* __restrict__ famp = nullptr) {
   extern __shared__ __attribute__((aligned(16))) unsigned char txf_smem[];
   cx<T>* buf = (cx<T>*)txf_smem;
   const int64_t f = blockIdx.y;
@@ -205,12 +220,23 @@ __device__ __forceinline__ void tx_channel_body(const cx<T>* __restrict__ tx, cx
     }
     buf[i] = v;
   }
+  cx<T>* fa = buf + TXF_SEG + H;                                 // FADE: the frame's amplitudes, read once per workgroup
+  if constexpr (FADE) {
+    if ((int)threadIdx.x < taps.n) {
+      const c64 a = famp[f * taps.n + threadIdx.x];
+      fa[threadIdx.x] = mk<T>((T)a.x, (T)a.y);
+    }
+  }
   __syncthreads();
   cx<T>* y = rx + f * len;
   for (int o = threadIdx.x; o < TXF_SEG; o += 256) {
     if (n0 + o >= len) break;
     cx<T> acc = mk<T>(0, 0);
-    for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
+    if constexpr (FADE) {
+      for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * fa[t];
+    } else {
+      for (int t = 0; t < taps.n; ++t) acc = acc + buf[H + o - taps.delay[t]] * taps.amp[t];
+    }
     nt_store(y + n0 + o, acc);
   }
 }
@@ -230,6 +256,77 @@ __global__ __launch_bounds__(256) void tx_channel_imp_kernel(const cx<T>* __rest
                                                              const int64_t* __restrict__ sto, const double* __restrict__ cfo,
                                                              double inv_nfft, TxfTaps<T> taps) {
   tx_channel_body<T, true>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, sto, cfo, inv_nfft, taps);
+}
+
+// dynamic LDS = (TXF_SEG + halo + taps.n) samples
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_fade_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                              const double* __restrict__ partial, int n_symb, int64_t len,
+                                                              double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                              const c64* __restrict__ famp, TxfTaps<T> taps) {
+  tx_channel_body<T, false, true>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, nullptr, nullptr, 0.0, taps, famp);
+}
+
+// per-frame channel draw, the sibling of tx_draw_kernel: tap t of frame f is gain[t] (cospi(2u) + i sinpi(2u)) with
+// u = (word0 + 0.5) 2^-32 of Philox counter (t, 0, stream0 + f, 3) -- static taps with random initial phases, the stand-in
+// for lteFadingChannel of drivers/common.py:fading_taps drawn on the device.  amp / taps_out: [n_frames][n_taps].
+struct TxfGains {
+  double g[TXF_MAX_TAPS];
+};
+
+__global__ __launch_bounds__(256) void tx_fade_draw_kernel(c64* __restrict__ amp, c64* __restrict__ taps_out, TxfGains gains,
+                                                           int n_taps, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                           int64_t n_frames) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_frames * n_taps) return;
+  const int64_t f = i / n_taps;
+  const int t = (int)(i - f * n_taps);
+  uint32_t r[4];
+  philox_words((uint32_t)t, 0u, stream0 + (uint32_t)f, 3u, k0, k1, r);
+  const double u = ((double)r[0] + 0.5) * 2.3283064365386963e-10;
+  double sn, cs;
+  sincospi(2.0 * u, &sn, &cs);
+  const c64 a{gains.g[t] * cs, gains.g[t] * sn};
+  amp[i] = a;
+  if (taps_out) taps_out[i] = a;
+}
+
+// per frame f of a fading sweep: sum_{k < n_carrier} |H_f(k) - hest[f][k]|^2 with H_f(k) = sum_t a_{f,t} e^{-2 pi i d_t k / Nfft}
+// = fft(h_f, Nfft)(k) of get_MP_channel_resp (T5/Task5_part2.m:160-166,:202-205), in double.  One workgroup per frame: each
+// thread a fixed stride of carriers, a fixed butterfly, the four wave partials paired -- no atomics.
+struct TxfDelays {
+  int32_t d[TXF_MAX_TAPS];
+  int n;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void t5_frame_nmse_kernel(const c64* __restrict__ amp, const cx<T>* __restrict__ hest,
+                                                            TxfDelays dl, int nfft, int n_carrier,
+                                                            double* __restrict__ frame_nmse) {
+  __shared__ c64 a[TXF_MAX_TAPS];
+  __shared__ double part[4];
+  const int64_t f = blockIdx.x;
+  if ((int)threadIdx.x < dl.n) a[threadIdx.x] = amp[f * dl.n + threadIdx.x];
+  __syncthreads();
+  const double inv = 2.0 / (double)nfft;
+  double s = 0;
+  for (int k = threadIdx.x; k < n_carrier; k += 256) {
+    double hr = 0, hi = 0;
+    for (int t = 0; t < dl.n; ++t) {
+      const int m = (int)(((int64_t)dl.d[t] * k) % nfft);       // the phase reduced in integers: the argument stays in [0, 2)
+      double sn, cs;
+      sincospi((double)m * inv, &sn, &cs);
+      hr += a[t].x * cs + a[t].y * sn;                           // a (cs - i sn)
+      hi += a[t].y * cs - a[t].x * sn;
+    }
+    const cx<T> e = hest[f * n_carrier + k];
+    const double dr = hr - (double)e.x, di = hi - (double)e.y;
+    s += dr * dr + di * di;
+  }
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) frame_nmse[f] = (part[0] + part[1]) + (part[2] + part[3]);
 }
 
 __global__ __launch_bounds__(256) void ber_point_reduce_kernel(const uint32_t* __restrict__ frame_errors,
@@ -289,28 +386,27 @@ __global__ __launch_bounds__(256) void t4_point_reduce_kernel(const uint32_t* __
 
 // per point p of a Task-4 / Task-5 sweep with MER: the per-frame MER_func sums {s1, s2} of the symbol stages' MER variants -> the
 // point's {sum s1, sum s2} (MER_func of the point's RX_IQ concatenated) -- the fixed order of t4_point_reduce_kernel:
-// each thread a fixed stride, a fixed butterfly, the four wave partials paired; bitwise independent of the chunking
+// each thread a fixed stride, a fixed butterfly, the four wave partials paired; bitwise independent of the chunking.
+// W = values per frame: 2 for the MER sums, 1 for the channel-estimate error of a fading sweep (t5_frame_nmse_kernel).
+template <int W>
 __global__ __launch_bounds__(256) void t4_point_mer_kernel(const double* __restrict__ frame_mer, int64_t frames_per_point,
                                                            double* __restrict__ mer_sums) {
   const int64_t p = blockIdx.x;
-  double a = 0, b = 0;
+  double a[W];
+  for (int q = 0; q < W; ++q) a[q] = 0;
   for (int64_t i = threadIdx.x; i < frames_per_point; i += 256) {
     const int64_t k = p * frames_per_point + i;
-    a += frame_mer[2 * k];
-    b += frame_mer[2 * k + 1];
+    for (int q = 0; q < W; ++q) a[q] += frame_mer[W * k + q];
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    a += __shfl_xor(a, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
-  __shared__ double pa[4], pb[4];
+  for (int off = 32; off > 0; off >>= 1)
+    for (int q = 0; q < W; ++q) a[q] += __shfl_xor(a[q], off, 64);
+  __shared__ double pa[4][W];
   const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { pa[w] = a; pb[w] = b; }
+  if ((threadIdx.x & 63) == 0)
+    for (int q = 0; q < W; ++q) pa[w][q] = a[q];
   __syncthreads();
-  if (threadIdx.x == 0) {
-    mer_sums[2 * p] = (pa[0] + pa[1]) + (pa[2] + pa[3]);
-    mer_sums[2 * p + 1] = (pb[0] + pb[1]) + (pb[2] + pb[3]);
-  }
+  if (threadIdx.x == 0)
+    for (int q = 0; q < W; ++q) mer_sums[W * p + q] = (pa[0][q] + pa[1][q]) + (pa[2][q] + pa[3][q]);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -341,6 +437,36 @@ static int txf_channel(const void* h, int h_len, bool f64, TxfChannel& ch) {
   }
   OFDM_ARG((int)ch.delay.size() <= TXF_MAX_TAPS, "tx_frames_fused: %d nonzero channel taps (at most %d)",
            (int)ch.delay.size(), TXF_MAX_TAPS);
+  return OFDM_OK;
+}
+
+// a per-frame channel on one tap-delay line: ch.delay / ch.halo as for a static h, the amplitudes drawn per chunk
+struct TxfFade {
+  TxfGains gains;                                    // g_t = sqrt(tap_power[t] / sum tap_power), double
+  c64* amp = nullptr;                                // the chunk's amplitudes [nf][n_taps] (tx_fade_draw_kernel)
+  c64* taps_out = nullptr;                           // generator: where the caller wants them (optional)
+};
+
+static int txf_fading(const int32_t* tap_delay, const double* tap_power, int n_taps, const char* what, TxfChannel& ch,
+                      TxfFade& fd) {
+  OFDM_ARG(n_taps >= 1 && n_taps <= TXF_MAX_TAPS, "%s: n_taps must be 1 .. %d", what, TXF_MAX_TAPS);
+  OFDM_ARG(tap_delay && tap_power, "%s: tap_delay / tap_power missing", what);
+  double total = 0;
+  for (int t = 0; t < n_taps; ++t) {
+    OFDM_ARG(tap_delay[t] >= 0 && tap_delay[t] <= TXF_MAX_DELAY, "%s: tap delay %d outside 0 .. %d", what, tap_delay[t],
+             TXF_MAX_DELAY);
+    for (int q = 0; q < t; ++q) OFDM_ARG(tap_delay[q] != tap_delay[t], "%s: tap delay %d given twice", what, tap_delay[t]);
+    OFDM_ARG(tap_power[t] > 0.0 && std::isfinite(tap_power[t]), "%s: tap powers must be positive and finite", what);
+    total += tap_power[t];
+  }
+  OFDM_ARG(std::isfinite(total), "%s: tap powers must be positive and finite", what);
+  fd.gains = TxfGains{};
+  for (int t = 0; t < n_taps; ++t) {
+    fd.gains.g[t] = std::sqrt(tap_power[t] / total);
+    ch.delay.push_back(tap_delay[t]);
+    ch.amp.push_back(c64{fd.gains.g[t], 0.0});
+    ch.halo = std::max(ch.halo, (int)tap_delay[t]);
+  }
   return OFDM_OK;
 }
 
@@ -379,16 +505,24 @@ struct TxfImp {
   double* cfo = nullptr;
 };
 
-// imp (optional): tx_channel_imp_kernel with the chunk's draws imp->sto / imp->cfo, else tx_channel_fused_kernel
+// fade (optional, no entry combines it with imp): tx_channel_fade_kernel with the chunk's amplitudes fade->amp;
+// imp (optional): tx_channel_imp_kernel with the chunk's draws imp->sto / imp->cfo; else tx_channel_fused_kernel
 template <typename T>
 static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
-                          double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const TxfImp* imp, int64_t nf) {
+                          double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const TxfImp* imp, const TxfFade* fade,
+                          int64_t nf) {
   const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
-  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo);
+  const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo + (fade ? ch.delay.size() : 0));
   const dim3 grid(cdiv_u(len, TXF_SEG), (unsigned)nf);
-  const void* kernel = imp ? (const void*)tx_channel_imp_kernel<T> : (const void*)tx_channel_fused_kernel<T>;
+  const void* kernel = fade ? (const void*)tx_channel_fade_kernel<T>
+                            : imp ? (const void*)tx_channel_imp_kernel<T> : (const void*)tx_channel_fused_kernel<T>;
   // > 64 KB for long channels: the attribute is per device, so it is set on every launch (not cached per process)
   OFDM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (fade) {
+    hipLaunchKernelGGL(tx_channel_fade_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
+                       pl->n_symb, len, snr_lin, k0, k1, stream0, (const c64*)fade->amp, txf_taps<T>(ch));
+    return check_launch("tx_channel_fade_kernel");
+  }
   if (imp)
     hipLaunchKernelGGL(tx_channel_imp_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
                        pl->n_symb, len, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, 1.0 / (double)pl->nfft, txf_taps<T>(ch));
@@ -408,27 +542,40 @@ struct TxfBuffers {
   uint32_t* ref = nullptr;                           // sweep: their packed reference bits
   int64_t* sto = nullptr;                            // impairments on: the chunk's draws
   double* cfo = nullptr;
+  c64* amp = nullptr;                                // fading: the chunk's tap amplitudes [ch][n_taps]
+  void* hest = nullptr;                              // fading sweep with NMSE: the chunk's channel estimates [N_carrier x ch]
+};
+
+// what a call adds to the plain generator workspace
+struct TxfExtras {
+  bool imp = false;                                  // the Task-4 impairment draws
+  int fade_taps = 0;                                 // > 0: a per-frame channel of that many taps
+  bool hest = false;                                 // the receiver's channel estimates (sweep)
 };
 
 static size_t a256(size_t b) { return (b + 255) & ~size_t(255); }
 
-static size_t txf_frame_bytes(const ofdm_rx_plan* pl, bool scr, bool sweep, bool imp = false) {
+static size_t txf_frame_bytes(const ofdm_rx_plan* pl, bool scr, bool sweep, const TxfExtras& x = TxfExtras()) {
   const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
   const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
   return cs * fs * (sweep ? 2 : 1) + 8 * (size_t)pl->n_symb + (scr ? 2 * frame_bits : 0) +
-         (sweep ? (size_t)pl->frame_words * 4 : 0) + (imp ? 16 : 0);
+         (sweep ? (size_t)pl->frame_words * 4 : 0) + (x.imp ? 16 : 0) + sizeof(c64) * (size_t)x.fade_taps +
+         (x.hest ? cs * (size_t)pl->n_carrier : 0);
 }
 
-static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, TxfBuffers& b, bool imp = false) {
+static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, TxfBuffers& b,
+                         const TxfExtras& x = TxfExtras()) {
   const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
   const size_t fs = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t frame_bits = (size_t)pl->nd * pl->n_symb * pl->bps;
   const size_t t_bytes = a256(cs * fs * ch), p_bytes = a256(8 * (size_t)pl->n_symb * ch);
   const size_t b_bytes = scr ? a256(frame_bits * ch) : 0;
   const size_t r_bytes = sweep ? t_bytes : 0, f_bytes = sweep ? a256((size_t)pl->frame_words * 4 * ch) : 0;
-  const size_t d_bytes = imp ? a256(8 * (size_t)ch) : 0;
-  const size_t need = t_bytes + p_bytes + 2 * b_bytes + r_bytes + f_bytes + 2 * d_bytes;
+  const size_t d_bytes = x.imp ? a256(8 * (size_t)ch) : 0;
+  const size_t a_bytes = a256(sizeof(c64) * (size_t)x.fade_taps * ch);
+  const size_t h_bytes = x.hest ? a256(cs * (size_t)pl->n_carrier * ch) : 0;
+  const size_t need = t_bytes + p_bytes + 2 * b_bytes + r_bytes + f_bytes + 2 * d_bytes + a_bytes + h_bytes;
   if (pl->ws_txf_bytes < need) {
     OFDM_HIP(hipStreamSynchronize(ctx().stream));
     if (pl->ws_txf) { (void)hipFree(pl->ws_txf); pl->ws_txf = nullptr; pl->ws_txf_bytes = 0; }
@@ -441,20 +588,25 @@ static int txf_workspace(ofdm_rx_plan* pl, int64_t ch, bool scr, bool sweep, Txf
   unsigned char* q = base + t_bytes + p_bytes;
   if (scr) { b.b0 = q; b.b1 = q + b_bytes; q += 2 * b_bytes; }
   if (sweep) { b.rx = q; b.ref = (uint32_t*)(q + r_bytes); q += r_bytes + f_bytes; }
-  if (imp) { b.sto = (int64_t*)q; b.cfo = (double*)(q + d_bytes); }
+  if (x.imp) { b.sto = (int64_t*)q; b.cfo = (double*)(q + d_bytes); q += 2 * d_bytes; }
+  if (x.fade_taps) { b.amp = (c64*)q; q += a_bytes; }
+  if (x.hest) b.hest = q;
   return OFDM_OK;
 }
 
-static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n_frames, int64_t user_cap, bool imp = false) {
-  int64_t ch = user_cap > 0 ? user_cap : std::max<int64_t>(1, (int64_t)(TXF_WS_BUDGET / txf_frame_bytes(pl, scr, sweep, imp)));
+static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n_frames, int64_t user_cap,
+                         const TxfExtras& x = TxfExtras()) {
+  int64_t ch = user_cap > 0 ? user_cap : std::max<int64_t>(1, (int64_t)(TXF_WS_BUDGET / txf_frame_bytes(pl, scr, sweep, x)));
   return std::max<int64_t>(1, std::min<int64_t>({ch, n_frames, 65535}));
 }
 
 // one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
 // imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
+// fade (optional): a channel per frame -- the draws into fade->amp (and fade->taps_out), the channel pass of
+// tx_channel_fade_kernel
 static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
                         int64_t nf, const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
-                        const TxfImp* imp = nullptr) {
+                        const TxfImp* imp = nullptr, const TxfFade* fade = nullptr) {
   const int64_t frame_bits = (int64_t)pl->nd * pl->n_symb * pl->bps;
   OFDM_TRY(tx_bits_device(pl, ref, scr_reg15 ? b.b0 : nullptr, k0, k1, stream0, nf));
   if (scr_reg15) {                                              // Scrambler.m per frame, register reset (T5:58-69)
@@ -472,8 +624,14 @@ static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, 
   if (imp)
     OFDM_TRY(tx_draw_device(pl, imp->sto, imp->cfo, imp->sto_mode, imp->sto_value, imp->cfo_mode, imp->cfo_value, k0, k1,
                             stream0, nf));
-  if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, nf));
-  else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, nf));
+  if (fade) {
+    const int n_taps = (int)ch.delay.size();
+    hipLaunchKernelGGL(tx_fade_draw_kernel, dim3(cdiv_u(nf * n_taps, 256)), dim3(256), 0, ctx().stream, fade->amp,
+                       fade->taps_out, fade->gains, n_taps, k0, k1, stream0, nf);
+    OFDM_TRY(check_launch("tx_fade_draw_kernel"));
+  }
+  if (pl->f64) OFDM_TRY(launch_channel<double>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, fade, nf));
+  else OFDM_TRY(launch_channel<float>(pl, ch, b.tx, rx, b.partial, snr_lin, k0, k1, stream0, imp, fade, nf));
   return OFDM_OK;
 }
 
@@ -519,41 +677,51 @@ static int txf_check_plan(ofdm_rx_plan* pl, int flags, int64_t frame0, int64_t n
   return OFDM_OK;
 }
 
-// the body of both generator entries: n_frames frames from frame0 on in chunks of the plan-owned workspace.
+// the body of the generator entries: n_frames frames from frame0 on in chunks of the plan-owned workspace.
 // imp (optional): the Task-4 impairments -- the draws go to sto_out / cfo_out when they are given, else to the workspace
-static int txf_frames(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed, int64_t frame0,
-                      int64_t n_frames, const uint8_t* scr_reg15, const TxfImp* imp, void* rx_out, uint8_t* ref_bits_out,
-                      uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, int flags) {
-  TxfChannel ch;
-  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+// fade (optional): a channel per frame on ch's delays -- the amplitudes go to the workspace and to taps_out when it is given
+static int txf_frames(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_db, uint64_t seed, int64_t frame0,
+                      int64_t n_frames, const uint8_t* scr_reg15, const TxfImp* imp, const TxfFade* fade, void* rx_out,
+                      uint8_t* ref_bits_out, uint8_t* sc_ref_bits_out, int64_t* sto_out, double* cfo_out, double* taps_out,
+                      int flags) {
   if (n_frames == 0) return OFDM_OK;
   OFDM_TRY(tx_dict_device(pl));
   const size_t cs = csize(flags);
   const int64_t frame_samples = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t fb = (size_t)pl->frame_words * 4;
   Stage st(flags);
-  void *drx, *dref, *dscref, *dsto, *dcfo;
+  const int n_taps = fade ? (int)ch.delay.size() : 0;
+  void *drx, *dref, *dscref, *dsto, *dcfo, *dtaps;
   OFDM_TRY(st.out(rx_out, cs * (size_t)frame_samples * n_frames, &drx));
   OFDM_TRY(st.out(ref_bits_out, fb * n_frames, &dref));
   OFDM_TRY(st.out(sc_ref_bits_out, fb * n_frames, &dscref));
   OFDM_TRY(st.out(sto_out, sizeof(int64_t) * (size_t)n_frames, &dsto));
   OFDM_TRY(st.out(cfo_out, sizeof(double) * (size_t)n_frames, &dcfo));
+  OFDM_TRY(st.out(taps_out, sizeof(c64) * (size_t)n_taps * n_frames, &dtaps));
   const bool scr = scr_reg15 != nullptr;
-  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0, imp != nullptr);
+  TxfExtras x;
+  x.imp = imp != nullptr;
+  x.fade_taps = n_taps;
+  const int64_t CH = txf_chunk(pl, scr, false, n_frames, 0, x);
   TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr, false, b, imp != nullptr));
+  OFDM_TRY(txf_workspace(pl, CH, scr, false, b, x));
   const double snr_lin = std::pow(10.0, snr_db / 10.0);
   const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
   TxfImp ci;
   if (imp) ci = *imp;
+  TxfFade cf;
+  if (fade) cf = *fade;
+  cf.amp = b.amp;
   for (int64_t c0 = 0; c0 < n_frames; c0 += CH) {
     const int64_t nf = std::min<int64_t>(CH, n_frames - c0);
     ci.sto = dsto ? (int64_t*)dsto + c0 : b.sto;
     ci.cfo = dcfo ? (double*)dcfo + c0 : b.cfo;
+    cf.taps_out = dtaps ? (c64*)dtaps + c0 * n_taps : nullptr;
     OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b,
                           (unsigned char*)drx + cs * (size_t)frame_samples * c0,
                           dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
-                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, imp ? &ci : nullptr));
+                          dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, imp ? &ci : nullptr,
+                          fade ? &cf : nullptr));
   }
   return st.finish();
 }
@@ -591,17 +759,20 @@ static int txf_sweep_outputs(Stage& st, int64_t n_points, int64_t frames_per_poi
 }
 
 // every point of a sweep, chunk by chunk of at most CH frames: the chunk generated into the workspace (imp: with the Task-4
-// impairments, the draws of the sweep's frame k at imp->sto[k] / imp->cfo[k]), then decode(b, nf, o) with o the sweep index
-// of the chunk's first frame
+// impairments, the draws of the sweep's frame k at imp->sto[k] / imp->cfo[k]; fade: with a channel per frame, the chunk's
+// amplitudes at b.amp), then decode(b, nf, o) with o the sweep index of the chunk's first frame.  x: the workspace's extras.
 template <typename Decode>
 static int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const double* snr_db, const uint64_t* seeds,
                             int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15, int64_t CH,
-                            const TxfImp* imp, Decode&& decode) {
+                            const TxfImp* imp, const TxfFade* fade, const TxfExtras& x, Decode&& decode) {
   OFDM_TRY(tx_dict_device(pl));
   TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, scr_reg15 != nullptr, true, b, imp != nullptr));
+  OFDM_TRY(txf_workspace(pl, CH, scr_reg15 != nullptr, true, b, x));
   TxfImp ci;
   if (imp) ci = *imp;
+  TxfFade cf;
+  if (fade) cf = *fade;
+  cf.amp = b.amp;
   for (int64_t p = 0; p < n_points; ++p) {
     const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
     const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
@@ -610,7 +781,7 @@ static int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const double
       const int64_t o = p * frames_per_point + c0;
       if (imp) { ci.sto = imp->sto + o; ci.cfo = imp->cfo + o; }
       OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr,
-                            imp ? &ci : nullptr));
+                            imp ? &ci : nullptr, fade ? &cf : nullptr));
       OFDM_TRY(decode(b, nf, o));
     }
   }
@@ -620,7 +791,7 @@ static int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const double
 // the per-point MER sums of a sweep with MER: the fixed-order reduction of the per-frame sums
 static int txf_point_mer(const TxfSweepOut& o, int64_t n_points, int64_t frames_per_point) {
   if (!o.mer) return OFDM_OK;
-  hipLaunchKernelGGL(t4_point_mer_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)o.fm,
+  hipLaunchKernelGGL(t4_point_mer_kernel<2>, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)o.fm,
                      frames_per_point, (double*)o.mer);
   return check_launch("t4_point_mer_kernel");
 }
@@ -636,8 +807,25 @@ extern "C" int ofdm_tx_frames_fused(ofdm_rx_plan* pl, const void* h, int h_len, 
   OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fused: bad arguments");
   OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fused"));
   OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused: sc_ref_bits_out needs the Scrambler register");
-  return txf_frames(pl, h, h_len, snr_db, seed, frame0, n_frames, scr_reg15, nullptr, rx_out, ref_bits_out, sc_ref_bits_out,
-                    nullptr, nullptr, flags);
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  return txf_frames(pl, ch, snr_db, seed, frame0, n_frames, scr_reg15, nullptr, nullptr, rx_out, ref_bits_out,
+                    sc_ref_bits_out, nullptr, nullptr, nullptr, flags);
+}
+
+extern "C" int ofdm_tx_frames_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                     double snr_db, uint64_t seed, int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15,
+                                     void* rx_out, uint8_t* ref_bits_out, uint8_t* sc_ref_bits_out, double* taps_out,
+                                     int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fading: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fading"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fading: sc_ref_bits_out needs the Scrambler register");
+  TxfChannel ch;
+  TxfFade fade;
+  OFDM_TRY(txf_fading(tap_delay, tap_power, n_taps, "tx_frames_fading", ch, fade));
+  return txf_frames(pl, ch, snr_db, seed, frame0, n_frames, scr_reg15, nullptr, &fade, rx_out, ref_bits_out, sc_ref_bits_out,
+                    nullptr, nullptr, taps_out, flags);
 }
 
 extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_len, double snr_db, uint64_t seed,
@@ -651,8 +839,65 @@ extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fused_ex: sc_ref_bits_out needs the Scrambler register");
   TxfImp imp;
   imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
-  return txf_frames(pl, h, h_len, snr_db, seed, frame0, n_frames, scr_reg15, &imp, rx_out, ref_bits_out, sc_ref_bits_out,
-                    sto_out, cfo_out, flags);
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  return txf_frames(pl, ch, snr_db, seed, frame0, n_frames, scr_reg15, &imp, nullptr, rx_out, ref_bits_out, sc_ref_bits_out,
+                    sto_out, cfo_out, nullptr, flags);
+}
+
+// the body of both Task-5 sweep entries, after their argument checks: ch the static channel, or with fade the delay line of a
+// channel per frame; nmse_sums_out / frame_nmse_out (fading only): the channel-estimate error sums
+static int t5_sweep(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfFade* fade, const double* snr_db, const uint64_t* seeds,
+                    int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                    int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out, double* mer_sums_out,
+                    double* frame_mer_sums_out, double* nmse_sums_out, double* frame_nmse_out, int flags) {
+  if (n_points == 0) return OFDM_OK;
+  Stage st(flags);
+  TxfSweepOut o;
+  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
+                             o));
+  void *dns, *dfn;
+  OFDM_TRY(st.out(nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
+  OFDM_TRY(st.out(frame_nmse_out, sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
+  if (frames_per_point == 0) {
+    if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, ctx().stream));
+    return st.finish();
+  }
+  if (dns && !dfn) OFDM_TRY(st.scratch(sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
+  TxfExtras x;
+  x.fade_taps = fade ? (int)ch.delay.size() : 0;
+  x.hest = dfn != nullptr;
+  const int64_t CH = txf_chunk(pl, scr_reg15 != nullptr, true, frames_per_point, max_frames_per_chunk, x);
+  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
+  TxfDelays dl{};
+  dl.n = x.fade_taps;
+  for (int t = 0; t < dl.n; ++t) dl.d[t] = ch.delay[t];
+  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, nullptr, fade, x,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
+                              OFDM_TRY(ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
+                                                              (uint32_t*)o.fe + k, b.hest, nullptr,
+                                                              o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags));
+                              if (!dfn) return (int)OFDM_OK;
+                              if (pl->f64)
+                                hipLaunchKernelGGL(t5_frame_nmse_kernel<double>, dim3((unsigned)nf), dim3(256), 0, ctx().stream,
+                                                   (const c64*)b.amp, (const c64*)b.hest, dl, pl->nfft, pl->n_carrier,
+                                                   (double*)dfn + k);
+                              else
+                                hipLaunchKernelGGL(t5_frame_nmse_kernel<float>, dim3((unsigned)nf), dim3(256), 0, ctx().stream,
+                                                   (const c64*)b.amp, (const c32*)b.hest, dl, pl->nfft, pl->n_carrier,
+                                                   (double*)dfn + k);
+                              return check_launch("t5_frame_nmse_kernel");
+                            }));
+  hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)o.fe,
+                     frames_per_point, (unsigned long long*)o.err);
+  OFDM_TRY(check_launch("ber_point_reduce_kernel"));
+  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
+  if (dns) {
+    hipLaunchKernelGGL(t4_point_mer_kernel<1>, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const double*)dfn,
+                       frames_per_point, (double*)dns);
+    OFDM_TRY(check_launch("t4_point_mer_kernel"));
+  }
+  return st.finish();
 }
 
 extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
@@ -667,25 +912,27 @@ extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task5"));
   TxfChannel ch;
   OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
-  if (n_points == 0) return OFDM_OK;
-  Stage st(flags);
-  TxfSweepOut o;
-  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
-                             o));
-  if (frames_per_point == 0) return st.finish();
-  const int64_t CH = txf_chunk(pl, scr_reg15 != nullptr, true, frames_per_point, max_frames_per_chunk);
-  const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
-  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, nullptr,
-                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
-                              return ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
-                                                            (uint32_t*)o.fe + k, nullptr, nullptr,
-                                                            o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags);
-                            }));
-  hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)o.fe,
-                     frames_per_point, (unsigned long long*)o.err);
-  OFDM_TRY(check_launch("ber_point_reduce_kernel"));
-  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
-  return st.finish();
+  return t5_sweep(pl, ch, nullptr, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk,
+                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nullptr, nullptr, flags);
+}
+
+extern "C" int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                           const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                           int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                           int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
+                                           double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
+                                           double* frame_nmse_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && max_frames_per_chunk >= 0 && errors_out,
+           "ber_sweep_task5_fading: bad arguments");
+  OFDM_TRY(txf_check_sweep(pl, snr_db, seeds, n_points, frames_per_point, frame0, flags, "ber_sweep_task5_fading"));
+  OFDM_ARG(!pl->d_wt, "ber_sweep_task5_fading: an MMSE-mode plan is built for one channel h (ofdm_rx_plan_set_mmse)");
+  OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task5_fading"));
+  TxfChannel ch;
+  TxfFade fade;
+  OFDM_TRY(txf_fading(tap_delay, tap_power, n_taps, "ber_sweep_task5_fading", ch, fade));
+  return t5_sweep(pl, ch, &fade, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk,
+                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
@@ -737,18 +984,20 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dsto));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dcfo));
   const bool scr = scr_reg15 != nullptr;
+  TxfExtras x;
+  x.imp = true;
   // default chunk: the generator workspace and the Task-4 arena (shared with ofdm_task5_part2_tile) budgeted together
   int64_t CH = max_frames_per_chunk;
   if (CH == 0)                                                  // (+ the per-frame MER sums when they are wanted)
     CH = std::max<int64_t>(1, (int64_t)(2 * TXF_WS_BUDGET /
-                                        (txf_frame_bytes(pl, scr, true, true) + t4_frame_bytes(pl) + (o.fm ? 16 : 0))));
+                                        (txf_frame_bytes(pl, scr, true, x) + t4_frame_bytes(pl) + (o.fm ? 16 : 0))));
   CH = std::max<int64_t>(1, std::min<int64_t>({CH, frames_per_point, 65535}));
   const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
   TxfImp imp;
   imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
   imp.sto = (int64_t*)dsto;
   imp.cfo = (double*)dcfo;
-  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, &imp,
+  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, &imp, nullptr, x,
                             [&](const TxfBuffers& b, int64_t nf, int64_t k) {
                               return ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr,
                                                             (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,

@@ -1,5 +1,6 @@
 // Counter-based draws of the device frame generators (ofdm_txgen.hip, ofdm_txfused.hip): Philox4x32-10 with the payload
-// counter (j_lo, j_hi, stream, 1) and the raw word form the impairment (counter word 3 = 2) and noise (= 0) draws use.
+// counter (j_lo, j_hi, stream, 1) and the raw word form the impairment (counter word 3 = 2), noise (= 0) and per-frame
+// channel (= 3, counter (tap, 0, stream, 3): ofdm_tx_frames_fading) draws use.
 // Restated in oracle/ofdm_oracle.py (payload_codes_philox, sto_cfo_draw_philox, awgn_philox).
 #pragma once
 

@@ -117,6 +117,24 @@ def fading_taps(DelayProfile, SamplingRate, Seed):
     return np.stack([ds.astype(complex), a], axis=1)
 
 
+def fading_profile(DelayProfile, SamplingRate):
+    """The tap-delay line of a 3GPP delay profile for the per-frame channel draw of the fused generator
+    (RxPlan.tx_frames_fused / ber_sweep with fading=): table delays rounded to samples by the rule of fading_taps, power-
+    normalised.  Equal delays are merged by summing their POWERS, and the generator draws one phase per merged tap;
+    fading_taps draws a phase per table tap and merges the complex AMPLITUDES instead, so a merged tap there has a random
+    power where here it has a fixed one (and the realisations differ anyway: Philox on the device, PCG64 there).
+    Returns (delays [n] int, sorted and distinct; powers [n] float64, linear, summing to 1)."""
+    d_ns, p_db = DELAY_PROFILES[DelayProfile]
+    delay = np.floor(np.asarray(d_ns) * 1e-9 * SamplingRate + 0.5).astype(int)
+    power = 10.0 ** (np.asarray(p_db) / 10.0)
+    merged = {}
+    for d, p in zip(delay, power):
+        merged[int(d)] = merged.get(int(d), 0.0) + float(p)
+    ds = np.array(sorted(merged), dtype=np.int64)
+    pw = np.array([merged[int(d)] for d in ds], dtype=np.float64)
+    return ds, pw / np.sum(pw)
+
+
 def to_jsonable(o):
     if isinstance(o, dict):
         return {k: to_jsonable(v) for k, v in o.items() if not k.startswith("_")}

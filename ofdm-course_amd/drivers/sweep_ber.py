@@ -22,6 +22,14 @@ frames: at C3 MER_func of RX_IQ(Nfft+T_Guard+1:end) per frame, concatenated (ofd
 at C5 / M MER_func of each frame's whole RX_IQ (T5/Main_model_Task_5.m:282; ofdm_ber_sweep_task5_ex with --fused,
 rx_chain_task5(want_mer) per tile otherwise).  The two MER_func sums travel in a float64 all-reduce.
 
+--fused --fading {EPA,EVA,ETU} (C5 / M): a channel realisation per frame instead of the one channel cfg.taps -- the Monte-Carlo
+runs of T5/Task5_part2.m:148-155 at sweep rate, through `RxPlan.ber_sweep(fading=common.fading_profile(...))`
+(ofdm_ber_sweep_task5_fading), with the same tile keys and dealing.  The profile's delays are taken at FADING_SAMPLING_RATE; the
+estimator sees a delay only below the plan's K dictionary columns (ETU's last taps lie beyond M's 128: an error floor, as
+for any echo the dictionary cannot hold).  --nmse adds per point `nmse_sums` and `NMSE`, the channel-estimate error against
+fft(h_f) on carriers 1..N_carrier averaged over the point's frames (T5/Task5_part2.m:202-205,:318); the sums are doubles and
+travel in the float64 all-reduce.  The JSON line names the profile under "fading".
+
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -36,9 +44,26 @@ import time
 
 import numpy as np
 
+FADING_SAMPLING_RATE = 30.72e6          # samples/s the delay profiles are rounded at: LTE 20 MHz, the rate of Nfft 2048
+
+
+def check_fading(config, estimator, fused, fading, nmse):
+    """What --fading / --nmse need; the text of the refusal, or None."""
+    if nmse and fading is None:
+        return "--nmse needs --fading"
+    if fading is None:
+        return None
+    if not fused:
+        return "--fading needs --fused"
+    if config not in ("C5", "M"):
+        return "--fading is for the Task-5 receiver (configs C5 and M)"
+    if estimator != "omp":
+        return "--fading needs the OMP estimator (an MMSE plan is built for one channel)"
+    return None
+
 
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
-        rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False):
+        rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False, fading=None, nmse=False):
     """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}.
     Per batch of the tiles this rank holds, one call decodes one tile (rx_chain_task5 on make_frames_device frames, or
     ber_sweep for an MMSE plan, which is built for one SNR) or all of the batch's points (ber_sweep with --fused,
@@ -47,7 +72,11 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     import ofdm_course_amd as ofdm
     from ofdm_course_amd import frames as fr
     from ofdm_course_amd import sweep
+    from ofdm_course_amd.drivers.common import fading_profile
 
+    bad = check_fading(config, estimator, fused, fading, nmse)
+    if bad:
+        raise ValueError(bad)
     ofdm.init(device_index)
     dev = torch.device("cuda", device_index)
     cfg = {"C5": fr.config_C5, "M": fr.config_M, "C3": fr.config_C3}[config]()
@@ -60,9 +89,13 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         hh[: len(h)] = h
     n = len(snrs)
     # int64 columns: bit errors (+ C3: frames with receiver status 0, 1, -1, -2); float64 columns: (C3: the sum of
-    # |FreqOffset + IFO - Freq_Shift|) (+ mer: the MER_func sums s1, s2) -- one device table each, read once
+    # |FreqOffset + IFO - Freq_Shift|) (+ mer: the MER_func sums s1, s2) (+ nmse: the channel-estimate error sums) -- one
+    # device table each, read once
     cnt = torch.zeros((n, 5 if task4 else 1), dtype=torch.int64, device=dev)
-    flt = torch.zeros((n, int(task4) + (2 if mer else 0)), dtype=torch.float64, device=dev)
+    c_mer = int(task4)
+    c_nmse = c_mer + (2 if mer else 0)
+    flt = torch.zeros((n, c_nmse + int(nmse)), dtype=torch.float64, device=dev)
+    profile = fading_profile(fading, FADING_SAMPLING_RATE) if fading else None
     counters = sweep.Counters(n, cnt.shape[1])
     t0 = time.perf_counter()
     n_tiles = 0
@@ -85,8 +118,11 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
             elif fused:
                 if estimator == "mmse":
                     plan.set_mmse(hh, float(snrs[pts[0]]))
-                out = plan.ber_sweep(snrs[pts], frames_per_tile, h=h, seeds=seeds, frame0=stream0, device=dev, want_mer=mer)
+                chan = dict(fading=profile, want_nmse=nmse) if fading else dict(h=h)
+                out = plan.ber_sweep(snrs[pts], frames_per_tile, seeds=seeds, frame0=stream0, device=dev, want_mer=mer, **chan)
                 errors, mer_sums = out["errors"], out.get("mer_sums")
+                if nmse:
+                    flt[pts, c_nmse] += out["nmse_sums"]
             else:
                 cfg.SNR_dB = float(snrs[pts[0]])
                 data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=seeds[0], device=dev, frame0=stream0)
@@ -96,7 +132,7 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
                 errors, mer_sums = out["errors"].sum(), out["mer_sums"].sum(dim=0) if mer else None
             cnt[pts, 0] += errors
             if mer:
-                flt[pts, -2:] += mer_sums
+                flt[pts, c_mer:c_mer + 2] += mer_sums
         n_tiles += len(sis)
         for si in sis:
             counters.add(si, 0, 0, frames_per_tile * plan.frame_bits)
@@ -118,14 +154,20 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         res.update(order="noise_first", impairments={"Time_Delay": "random", "Freq_Shift": "random"})
     elif fused:
         res.update(order="noise_first", fused=True)
+    if fading:
+        res["fading"] = {"profile": fading, "sampling_rate": FADING_SAMPLING_RATE, "delays": profile[0].tolist(),
+                         "powers": profile[1].tolist()}
+    if nmse:
+        res["nmse_sums"] = sums[:, c_nmse].tolist()
+        res["NMSE"] = (sums[:, c_nmse] / (batches * frames_per_tile * cfg.N_carrier)).tolist()
     if mer:
-        m = sums[:, -2:]
+        m = sums[:, c_mer:c_mer + 2]
         res["mer_sums"] = m.tolist()
         res["MER_dB"] = (10.0 * np.log10(m[:, 0] / m[:, 1])).tolist()
     return res
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", choices=["C5", "M", "C3"], default="C5")
     ap.add_argument("--batches", type=int, default=2, help="tiles per SNR point")
@@ -137,8 +179,25 @@ def main():
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank on this GPU")
     ap.add_argument("--fused", action="store_true", help="reference order (Noise -> conv) through RxPlan.ber_sweep")
     ap.add_argument("--mer", action="store_true", help="per-point MER_dB (MER_func sums of the receiver)")
+    ap.add_argument("--fading", choices=["EPA", "EVA", "ETU"], default=None,
+                    help="with --fused at C5 / M: a channel realisation of this delay profile per frame")
+    ap.add_argument("--nmse", action="store_true", help="with --fading: per-point NMSE of the channel estimate")
     ap.add_argument("--json", default=None)
-    a = ap.parse_args()
+    return ap
+
+
+def parse_args(argv=None):
+    """The command line; a --fading / --nmse combination the sweep cannot run is a usage error."""
+    ap = parser()
+    a = ap.parse_args(argv)
+    bad = check_fading(a.config, a.estimator, a.fused, a.fading, a.nmse)
+    if bad:
+        ap.error(bad)
+    return a
+
+
+def main():
+    a = parse_args()
     import torch
     import torch.distributed as dist
     from ofdm_course_amd import sweep
@@ -152,7 +211,7 @@ def main():
         else:
             dist.init_process_group(a.backend)
     res = run(a.config, a.snrs, a.batches, a.frames_per_tile, a.precision, estimator=a.estimator, rank=rank, world=world,
-              device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer)
+              device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer, fading=a.fading, nmse=a.nmse)
     if rank == 0:
         text = json.dumps(res)
         if a.json:

@@ -12,7 +12,13 @@ ber_sweep_task4 call of the same size.  With --mer the C3 entry adds the same sw
 (ber_sweep_task4(want_mer=True, mer_skip=Nfft+T_guard), ofdm_ber_sweep_task4_ex) and rx_chain_task4 with want_mer, each timed
 in alternation with its MER-off form (rounds of `reps` calls each) so that the two medians see the same clocks.
 
-    python tools/sweep_rate.py [--mer] [M C4 C5 C3]
+--fading (M, C5): the cost of a channel per frame.  The generator with the config's static channel (tx_frames_fused(h=...),
+the yardstick) against the generator drawing a channel per frame on the same delays with the taps' powers
+(tx_frames_fused(fading=...), ofdm_tx_frames_fading), three rounds of `reps` calls each in alternation, every round's median
+and the spread (max - min) of each side; then the one-point fading sweep without and with the NMSE outputs in the same
+alternation (their difference is t5_frame_nmse_kernel + the stored estimates) beside the RX time of the tile.
+
+    python tools/sweep_rate.py [--mer] [--fading] [M C4 C5 C3]
 """
 from __future__ import annotations
 
@@ -100,6 +106,44 @@ def ab_timed(fa, fb, reps=5, rounds=3):
     return float(np.median(a)), float(np.median(b))
 
 
+def ab_rounds(fa, fb, reps=5, rounds=3):
+    """every round's median of fa and fb, timed in alternating rounds"""
+    a, b = [], []
+    for _ in range(rounds):
+        a.append(timed(fa, reps))
+        b.append(timed(fb, reps))
+    return a, b
+
+
+def measure_fading(name, reps=5):
+    cfg, F, _ = config(name)
+    dev = torch.device("cuda:0")
+    plan = fr.make_plan(cfg, ofdm, precision="fp32", device=0)
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    snr = cfg.SNR_dB
+    nz = np.flatnonzero(h)                                   # the same delay line for both: equal tap count and halo
+    fad = (nz, np.abs(h[nz]) ** 2)
+    st, fa = ab_rounds(lambda: plan.tx_frames_fused(F, h=h, SNR=snr, seed=3, device=dev),
+                       lambda: plan.tx_frames_fused(F, fading=fad, SNR=snr, seed=3, device=dev), reps)
+    torch.cuda.empty_cache()
+    gen = plan.tx_frames_fused(F, fading=fad, SNR=snr, seed=3, device=dev)
+    ms_rx = timed(lambda: ofdm.rx_chain_task5(plan, gen["rx"], ref_bits_packed=gen["packed"]), reps)
+    del gen
+    torch.cuda.empty_cache()
+    off, on = ab_rounds(lambda: plan.ber_sweep([snr], F, fading=fad, seed=3, device=dev),
+                        lambda: plan.ber_sweep([snr], F, fading=fad, seed=3, device=dev, want_nmse=True), reps)
+    res = plan.ber_sweep([snr], F, fading=fad, seed=3, device=dev, want_nmse=True)
+    r = {"config": name, "mode": "fading", "frames": F, "snr_db": snr, "n_taps": int(nz.size), "halo": int(nz[-1]),
+         "gen_static_ms": st, "gen_fading_ms": fa, "gen_static_spread_ms": max(st) - min(st),
+         "gen_fading_spread_ms": max(fa) - min(fa), "gen_fading_over_static": float(np.median(fa) / np.median(st)),
+         "rx_ms": ms_rx, "sweep_fading_ms": off, "sweep_fading_nmse_ms": on,
+         "nmse_ms_per_tile": float(np.median(on) - np.median(off)),
+         "ber": int(res["errors"][0].item()) / (F * plan.frame_bits), "NMSE": float(res["NMSE"][0].item())}
+    plan.close()
+    torch.cuda.empty_cache()
+    return r
+
+
 def measure_c3(reps=5, mer=False):
     cfg, F = fr.config_C3(), 4096
     dev = torch.device("cuda:0")
@@ -161,9 +205,14 @@ def measure_c3(reps=5, mer=False):
 def main():
     args = sys.argv[1:]
     mer = "--mer" in args
-    names = [a for a in args if a != "--mer"] or ["M", "C4", "C5"]
+    fading = "--fading" in args
+    names = [a for a in args if a not in ("--mer", "--fading")] or (["M", "C5"] if fading else ["M", "C4", "C5"])
     ofdm.init(0)
-    out = {"tool": "sweep_rate", "dtype": "f32", "configs": [measure_c3(mer=mer) if n == "C3" else measure(n) for n in names]}
+    if fading:
+        configs = [measure_fading(n) for n in names]
+    else:
+        configs = [measure_c3(mer=mer) if n == "C3" else measure(n) for n in names]
+    out = {"tool": "sweep_rate", "dtype": "f32", "configs": configs}
     print(json.dumps(out), flush=True)
 
 
