@@ -211,6 +211,15 @@ int ofdm_rx_plan_destroy(ofdm_rx_plan* plan);
  * values in the precision of `flags` (OFDM_F32 / OFDM_F64); h = NULL returns the plan to OMP mode.
  * Needs 2..512 pilots; the chain call needs the fast-path geometry (Nfft 512..4096). */
 int ofdm_rx_plan_set_mmse(ofdm_rx_plan* plan, const void* h, int64_t n_h, double snr_db, int flags);
+/* MMSE mode without a supplied channel: per frame H_LS = LS_CE(Y, Xp, pilot_loc, N_carrier), h = ifft(H_LS) (N_carrier points),
+ * H = MMSE_CE(Y, Xp, pilot_loc, Nfft, N_carrier, h, snr_db)   -- T5/Main_model_Task_5.m:178-180, :317-319.
+ * snr_db is what ofdm_rx_chain_task5(_ex) uses; the BER sweeps use snr_db[p] of the point instead.
+ * enable = 0 returns the plan to OMP mode (as ofdm_rx_plan_set_mmse(h = NULL) does). Pilot limits: those of ofdm_rx_plan_set_mmse.
+ * The two MMSE modes exclude each other: setting one clears the other.  index_out is not written.  The rms delay spread of
+ * MMSE_CE.m:19-24 is formed per frame from three Hermitian forms on the pilot LS values (built once per plan, summed in double
+ * in both precisions, r2 - r^2 clamped at 0), the Np x Np system of :33-36 is solved per frame (Levinson), :38 is the plan's
+ * spline operator.  The generic single-kernel entry refuses the mode as it refuses the fixed-h mode. */
+int ofdm_rx_plan_set_mmse_ls(ofdm_rx_plan* plan, int enable, double snr_db);
 /* Task-4 receiver over a batch of frames, each frame one stream of N_symb guarded symbols (T4/Main_model_Task_4.m:278-347
  * per frame, the plan supplying Nfft, T_guard, N_symb, the carrier sets, the pilot column and the constellation):
  *   if time_desync || freq_desync:  AutoCorrFunction(Rx, T_guard, Nfft)                              (:278)
@@ -287,7 +296,8 @@ int ofdm_tx_frames_fused(ofdm_rx_plan* plan, const void* h, int h_len, double sn
  * errors_out[n_points] (uint64): bit errors per point; frame_errors_out (optional): [n_points][frames_per_point] uint32;
  * both live where `flags` says.  With scr_reg15 (HOST uint8[15]) the plan must carry a DeScrambler with the same register
  * and the errors count against the payload bits (T3/Main_model_Task_3.m:237-265); without it the plan must not descramble.
- * An MMSE-mode plan is accepted only with n_points == 1 (its operator is built for one SNR).
+ * An MMSE-mode plan is accepted only with n_points == 1 (its operator is built for one SNR); a plan in the
+ * ofdm_rx_plan_set_mmse_ls mode with any n_points, point p estimated at snr_db[p].
  * max_frames_per_chunk: 0 = the library's choice (a workspace of about 2 GB); results do not depend on it.
  * With OFDM_DEVICE nothing synchronises the host (apart from a first-call workspace growth) and nothing is reduced on it. */
 int ofdm_ber_sweep_task5(ofdm_rx_plan* plan, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
@@ -332,7 +342,8 @@ int ofdm_tx_frames_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, const do
  *   nmse_sums_out[n_points] (double, optional) = the point's sum; its NMSE is nmse_sums / (frames_per_point * N_carrier).
  * Both are summed in a fixed order without atomics (per frame: thread i of 256 takes carriers i, i + 256, ..., a butterfly
  * over each wavefront, the four partials as (p0 + p1) + (p2 + p3); per point the same over the frames, after the last chunk):
- * bitwise independent of max_frames_per_chunk.  An MMSE-mode plan is refused (its operator is built for one h).  The other
+ * bitwise independent of max_frames_per_chunk.  A fixed-h MMSE plan is refused (its operator is built for one h); a plan
+ * in the ofdm_rx_plan_set_mmse_ls mode is accepted (Hest_f is then that estimator's output).  The other
  * arguments, outputs and rules are those of ofdm_ber_sweep_task5_ex; with both NMSE outputs NULL no estimate is stored. */
 int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps,
                                 const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,

@@ -688,6 +688,14 @@ class RxPlan:
         L.check(self.lib.ofdm_rx_plan_set_mmse(self.handle, hh.ctypes.data_as(C.c_void_p), hh.size, float(SNR),
                                                L.OFDM_F64 | L.OFDM_HOST), "rx_plan_set_mmse")
 
+    def set_mmse_ls(self, SNR=None):
+        """Switch the plan's estimator to the MMSE_CE call of T5/Main_model_Task_5.m:178-180 (ofdm_rx_plan_set_mmse_ls): per
+        frame H_LS = LS_CE(...), h = ifft(H_LS), H = MMSE_CE(Y, Xp, pilot_loc, Nfft, N_carrier, h, SNR) -- no channel is
+        supplied.  rx_chain_task5 uses `SNR`; ber_sweep uses each point's own SNR.  `SNR=None` returns to OMP_estimate.
+        set_mmse and set_mmse_ls exclude each other: setting one clears the other."""
+        L.check(self.lib.ofdm_rx_plan_set_mmse_ls(self.handle, 0 if SNR is None else 1, 0.0 if SNR is None else float(SNR)),
+                "rx_plan_set_mmse_ls")
+
     def set_descrambler(self, Register=None):
         """Per-frame DeScrambler(Register, .) inside rx_chain_task5 / rx_chain_task4 (T5/Main_model_Task_5.m:257-274): the
         demapped bits of every frame are descrambled in the pack stage before they are written / compared.  None = off."""

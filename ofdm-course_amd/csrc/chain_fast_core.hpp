@@ -665,6 +665,18 @@ struct FastPlanView {
   int64_t* ws_x_elems;
   int data_mod4;           // bit r: a data carrier with 0-based index = r (mod 4) exists (the wave symbol kernel skips the other residues)
   uint32_t descr;          // per-frame DeScrambler of the pack stage: 0 or DESCR_ON | register bits (ofdm_rx_plan_set_descrambler)
+  // MMSE mode with h = ifft(H_LS) per frame (ofdm_rx_plan_set_mmse_ls): the stage of ofdm_chain_mmse_ls.hip fills ws_h
+  int mmse_ls = 0;
+  double ls_inv_snr = 0.0, ls_cscale = 0.0;   // 1 / snr of this call; 2 pi df Nps
+  const void* d_ls_aq = nullptr;              // moment forms A_q [3][np][np] c64
+  const void* d_ls_wt = nullptr;              // fp64: spline operator W^T [np][ls_m_pad] c64
+  int ls_m_pad = 0;
+  const float* d_ls_bw = nullptr;             // fp32: banded spline operator (w [bw][nq][4], c0 [nq])
+  const int32_t* d_ls_bc0 = nullptr;
+  int ls_bw = 0, ls_span = 0;
+  void** ws_lsv = nullptr;                    // [n_frames][np] MMSE estimate at the pilots
+  size_t* ws_lsv_bytes = nullptr;
+  bool mmse() const { return d_wt != nullptr || mmse_ls != 0; }   // the symbol stages take H from ws_h
 };
 
 template <typename T>
@@ -691,10 +703,16 @@ int mmse_factored_run(const void* mt, int np_pad, const float* sb_w, const int32
 template <typename T>
 int mmse_apply_run(const void* wt, const void* y, void* hout, int np, int m_pad, int n_carrier, int64_t n_frames);
 
+// ofdm_chain_mmse_ls.hip: the same for a plan in the h = ifft(H_LS) mode (delay spread and Toeplitz solve per frame, then the spline)
+template <typename T>
+int mmse_ls_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_t n_frames);
+size_t spline_band_lds_bytes(int bw, int span);   // ofdm_chain_mmse.hip: dynamic LDS of spline_band_kernel
+
 // The MMSE estimate of every frame of a batch from its pilot LS values (P.ypil -> *pv.ws_h): fp32 plans with the factors
 // take H = Sop_banded * (M * Y), everything else the dense operator.  v [n_frames][np] lives in a plan-owned workspace.
 template <typename T>
 inline int mmse_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_t n_frames) {
+  if (pv.mmse_ls) return mmse_ls_stage_run<T>(pv, P, n_frames);
   if constexpr (std::is_same<T, float>::value) {
     if (pv.d_mt && mmse_factored_usable(pv.np, pv.np_pad)) {
       int64_t& cap = *pv.ws_v_frames;

@@ -561,7 +561,7 @@ int ofdm_rx_plan_destroy(ofdm_rx_plan* pl) {
   void* ptrs[] = {pl->d_prole, pl->d_drole, pl->d_pilots, pl->d_sct, pl->d_gram, pl->d_pc0,
                   pl->ws_stash, pl->ws_ypil, pl->ws_tapidx, pl->ws_tapx, pl->ws_h, pl->d_wt, pl->ws_x,
                   pl->ws_gen, pl->d_dict, pl->ws_t4, pl->d_t4_tx, pl->d_t4_w, pl->d_p2_sop, pl->ws_raw,
-                  pl->d_mt, pl->d_sb_w, pl->d_sb_c0, pl->ws_v, pl->d_t4_bw, pl->d_t4_bc0, pl->ws_txf};
+                  pl->d_mt, pl->d_sb_w, pl->d_sb_c0, pl->ws_v, pl->d_t4_bw, pl->d_t4_bc0, pl->ws_txf, pl->d_ls_aq, pl->d_ls_wt, pl->d_ls_bw, pl->d_ls_bc0, pl->ws_lsv};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& e : pl->ev) if (e) (void)hipEventDestroy(e);
   for (auto& e : pl->ev_t4) if (e) (void)hipEventDestroy(e);
@@ -590,7 +590,7 @@ int ofdm_rx_plan_set_descrambler(ofdm_rx_plan* pl, const uint8_t* reg15) {
 int ofdm_rx_plan_set_mmse(ofdm_rx_plan* pl, const void* h, int64_t n_h, double snr_db, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl, "rx_plan_set_mmse: null plan");
-  auto drop_factors = [&]() {
+  auto drop_factors = [&]() { pl->mmse_ls = 0;            // (the two MMSE modes exclude each other: every path here clears the other)
     for (void** q : {&pl->d_mt, &pl->d_sb_w, &pl->d_sb_c0}) if (*q) { (void)hipFree(*q); *q = nullptr; }
   };
   if (!h || n_h <= 0) {                                   // back to OMP mode
@@ -680,8 +680,8 @@ int ofdm_rx_plan_last_task4_ms(ofdm_rx_plan* pl, float* ms5) {
 
 int64_t ofdm_rx_plan_frame_bytes(const ofdm_rx_plan* pl) { return pl ? (int64_t)pl->frame_words * 4 : 0; }
 
-int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
-                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags) {
+extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && rx && n_frames >= 0, "rx_chain_task5: bad arguments");
   OFDM_PLAN_DEVICE(pl);
@@ -711,7 +711,7 @@ int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, u
   bool split = false;
   if (!fast && pl->pilots_in_band &&
       chain_split_supported(pl->nfft, pl->n_carrier, pl->taps, pl->bps, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0))
-    split = pl->nfft > 4096 || pl->d_wt != nullptr || generic_lds_bytes(pl) > GENERIC_LDS_LIMIT;
+    split = pl->nfft > 4096 || pl->d_wt != nullptr || pl->mmse_ls || generic_lds_bytes(pl) > GENERIC_LDS_LIMIT;
   // DeScrambler of the plan: fused into the pack stage of the wave-per-frame symbol kernel; every other path -- and the wave
   // kernel's MER variant -- hands its raw decisions to descr_pass_kernel (the stages themselves then neither compare nor count)
   void* craw = nullptr;
@@ -719,7 +719,7 @@ int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, u
   double* mer = (double*)dmer;
   if (fast || split) {
     FastPlanView pv;
-    make_plan_view(pl, pv);
+    make_plan_view(pl, pv, ls_inv_snr);
     pl->last_fast = 1;
     descr_pass = (pl->descr & DESCR_ON) && (mer || !(fast && chain_wave_supported(pv)));
     if (descr_pass) {
@@ -736,7 +736,7 @@ int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, u
   }
   descr_pass = (pl->descr & DESCR_ON) != 0;
   if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
-  OFDM_ARG(!pl->d_wt, "rx_chain_task5: the MMSE mode of a plan needs pilots inside 1..N_carrier, at most 32 taps and a frame "
+  OFDM_ARG(!pl->d_wt && !pl->mmse_ls, "rx_chain_task5: the MMSE mode of a plan needs pilots inside 1..N_carrier, at most 32 taps and a frame "
                       "whose decisions fit the workgroup's LDS (ofdm_MMSE_CE covers every other case)");
   pl->last_fast = 0;
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[0], ctx().stream));
@@ -753,6 +753,11 @@ int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, u
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[3], ctx().stream));
   return st.finish();
+}
+
+int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags) {
+  return rx_chain_task5_run(pl, rx, n_frames, bits_out, ref_bits, errors_out, h_out, index_out, mer_sums_out, flags, -1.0);
 }
 
 int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out,

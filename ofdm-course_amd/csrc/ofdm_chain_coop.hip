@@ -331,7 +331,7 @@ int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   const unsigned lds = CP_OFF_CODES + 2 * codes_bytes;
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 256, lds);
     if (const char* e = getenv("OFDM_COOP_WG_PER_CU")) per_cu = std::max(1, atoi(e));

@@ -433,12 +433,12 @@ int fast_params_prepare(const FastPlanView& pv, const void* tw, int64_t n_frames
     OFDM_HIP(hipMalloc(pv.ws_ypil, sizeof(cx<T>) * (size_t)pv.np * n_frames));
     OFDM_HIP(hipMalloc(pv.ws_tapidx, sizeof(int32_t) * (size_t)pv.taps * n_frames));
     OFDM_HIP(hipMalloc(pv.ws_tapx, sizeof(c64) * (size_t)pv.taps * n_frames));
-    if (pv.d_wt) OFDM_HIP(hipMalloc(pv.ws_h, sizeof(cx<T>) * (size_t)pv.n_carrier * n_frames));
+    if (pv.mmse()) OFDM_HIP(hipMalloc(pv.ws_h, sizeof(cx<T>) * (size_t)pv.n_carrier * n_frames));
     *pv.ws_frames = n_frames;
   }
   P.stash = (cx<T>*)*pv.ws_stash; P.ypil = (cx<T>*)*pv.ws_ypil;
   P.tap_idx = (int32_t*)*pv.ws_tapidx; P.tap_x = (c64*)*pv.ws_tapx;
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   if (mmse && !*pv.ws_h) {                       // the plan switched to MMSE mode after the workspace was made
     OFDM_HIP(hipStreamSynchronize(ctx().stream));
     OFDM_HIP(hipMalloc(pv.ws_h, sizeof(cx<T>) * (size_t)pv.n_carrier * *pv.ws_frames));
@@ -483,7 +483,7 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   FastParams<T> P;
   OFDM_TRY(fast_params_prepare<T>(pv, tw, n_frames, P));
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   DemapTable<T> tab;
   fill_demap_table<T>(*pv.dict, *pv.cinfo, tab);
   const int ncu = ctx().num_cu;

@@ -518,4 +518,7 @@ int mmse_apply_run(const void* wt, const void* y, void* hout, int np, int m_pad,
 template int mmse_apply_run<float>(const void*, const void*, void*, int, int, int, int64_t);
 template int mmse_apply_run<double>(const void*, const void*, void*, int, int, int, int64_t);
 
+// what spline_band_run asks for (a plan can refuse a band that does not fit when it is built)
+size_t spline_band_lds_bytes(int bw, int span) { return sizeof(cx<float>) * (size_t)span * SB_VS + sizeof(float4) * (size_t)bw * SB_QUADS; }
+
 }  // namespace ofdm

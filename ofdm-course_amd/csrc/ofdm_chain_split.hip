@@ -591,7 +591,7 @@ static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>&
   const void *tw4 = nullptr, *tw8 = nullptr;
   OFDM_TRY(get_twiddles(4096, false, &tw4));
   OFDM_TRY(get_twiddles(8192, false, &tw8));
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 512, lds);
     if (const char* e = getenv("OFDM_R2_WG_PER_CU")) per_cu = std::max(1, atoi(e));
@@ -694,7 +694,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
                      const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0, double* mer) {
   FastParams<T> P;
   OFDM_TRY(fast_params_prepare<T>(pv, tw, n_frames, P));
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   if constexpr (std::is_same<T, float>::value) {
     const bool coop = chain_coop_supported(pv);                        // (the faster one where its layout conditions hold)
     const bool r2 = !coop && chain_r2_supported(pv);

@@ -419,7 +419,7 @@ static bool wave_layout(int nd, int n_symb, int wpb, WaveLayout& lay) {
 
 bool chain_wave_supported(const FastPlanView& pv) {
   if (getenv("OFDM_FAST_NO_WAVE")) return false;
-  if ((pv.descr & DESCR_ON) && pv.d_wt != nullptr) return false;      // DeScrambler + MMSE mode: the four-wavefront symbol stage
+  if ((pv.descr & DESCR_ON) && pv.mmse()) return false;      // DeScrambler + MMSE mode: the four-wavefront symbol stage
   if (pv.f64 || pv.nfft != WV_N || pv.n_carrier > WV_N / 4 || pv.taps > FAST_MAXT) return false;
   WaveLayout lay;
   return wave_layout(pv.nd, pv.n_symb, 4, lay) && wave_layout(pv.nd, pv.n_symb, 8, lay);
@@ -435,7 +435,7 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   OFDM_ARG(wave_layout(pv.nd, pv.n_symb, wpb, lay), "rx_chain_task5(wave): frame does not fit the wave-per-frame stage");
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
-  const bool mmse = pv.d_wt != nullptr;
+  const bool mmse = pv.mmse();
   auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
     int per_cu = resident_blocks_per_cu((const void*)kern, 64 * wpb, lay.total);
     if (const char* e = getenv("OFDM_WAVE_WG_PER_CU")) per_cu = std::max(1, atoi(e));

@@ -13,6 +13,7 @@
 // Nothing returns to the host but 4 x n NMSE values and 4 x n error counts.
 #include <algorithm>
 
+#include "mmse_levinson.hpp"
 #include "rx_plan.hpp"
 #include "spline_op.hpp"
 
@@ -96,15 +97,8 @@ __global__ __launch_bounds__(128) void p2_apply_operator_kernel(const double* __
     if (f0 + f < n_frames) out[(f0 + f) * n_out + m] = mk<T>((T)ar[f], (T)ai[f]);
 }
 
-// ---- MMSE_CE.m:25-36 for one realisation per WAVEFRONT: Rpp = rf2 + I/snr is Hermitian Toeplitz with first column
-// 1/(1 + j c k), c = 2 pi tau_rms df Nps (tau_rms of the realisation's CIR comes with it); z = Rpp \ H_tilde by the Levinson
-// recursion in double, all state in wave-private LDS, no workgroup barrier; out = rf2 * z (the first Np rows of Rhp/Rpp*H_tilde,
-// which is all MMSE_CE.m:38 keeps).
-__device__ __forceinline__ double p2_wave_sum(double v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
+// ---- MMSE_CE.m:25-36 for one realisation per WAVEFRONT: mmse_toeplitz_wave (mmse_levinson.hpp), tau_rms of the realisation's CIR
+// comes with it as c = 2 pi tau_rms df Nps
 template <typename T>
 __global__ __launch_bounds__(256) void mmse_wave_kernel(const cx<T>* __restrict__ ypil, const double* __restrict__ cvals,
                                                         double inv_snr, int np, cx<T>* __restrict__ vout, int64_t n_frames,
@@ -117,68 +111,7 @@ __global__ __launch_bounds__(256) void mmse_wave_kernel(const cx<T>* __restrict_
   if (f >= n_frames) return;                                       // no workgroup barrier below
   if (inv_snr_v) inv_snr = inv_snr_v[f];
   c64* tcol = (c64*)p2_smem + (size_t)wave * 4 * np;               // [np] each: tcol, fv, bv, xv
-  c64 *fv = tcol + np, *bv = fv + np, *xv = bv + np;
-  const cx<T>* y = ypil + f * np;
-  const double c = cvals[f];
-  for (int k = lane; k < np; k += 64) {
-    const double d = 1.0 + (c * k) * (c * k);
-    tcol[k] = c64{1.0 / d, -(c * k) / d};
-  }
-  wave_sync();
-  const double t0 = tcol[0].x + inv_snr;
-  if (lane == 0) {
-    fv[0] = c64{1.0 / t0, 0};
-    bv[0] = c64{1.0 / t0, 0};
-    xv[0] = c64{(double)y[0].x / t0, (double)y[0].y / t0};
-  }
-  wave_sync();
-  for (int n = 1; n < np; ++n) {
-    // eps_f = sum_i T[n][i] f[i], eps_x = sum_i T[n][i] x[i], eps_b = sum_i T[0][i+1] b[i],  i < n   (T[i][j] = t(i - j))
-    c64 ef{0, 0}, ex{0, 0}, eb{0, 0};
-    for (int i = lane; i < n; i += 64) {
-      const c64 tn = tcol[n - i];
-      ef = ef + tn * fv[i];
-      ex = ex + tn * xv[i];
-      eb = eb + conj(tcol[i + 1]) * bv[i];
-    }
-    ef = c64{p2_wave_sum(ef.x), p2_wave_sum(ef.y)};
-    ex = c64{p2_wave_sum(ex.x), p2_wave_sum(ex.y)};
-    eb = c64{p2_wave_sum(eb.x), p2_wave_sum(eb.y)};
-    const c64 one{1, 0};
-    const c64 inv = cdiv(one, one - eb * ef);
-    const c64 dx = c64{(double)y[n].x, (double)y[n].y} - ex;
-    // new f = inv [f; 0] - ef inv [0; b] ; new b = inv [0; b] - eb inv [f; 0] ; x += dx * new b.  Entry i reads the old f[i]
-    // and b[i - 1] and writes index i: 64-entry chunks from the top down, each chunk reading before it writes, never
-    // overwrite an input of a chunk still to come.
-    for (int i0 = (n / 64) * 64; i0 >= 0; i0 -= 64) {
-      const int i = i0 + lane;
-      c64 nf{0, 0}, nb{0, 0}, nx{0, 0};
-      if (i <= n) {
-        const c64 fe = (i < n) ? fv[i] : c64{0, 0};
-        const c64 be = (i > 0) ? bv[i - 1] : c64{0, 0};
-        nf = inv * fe - (ef * inv) * be;
-        nb = inv * be - (eb * inv) * fe;
-        nx = ((i < n) ? xv[i] : c64{0, 0}) + dx * nb;
-      }
-      wave_sync();
-      if (i <= n) {
-        fv[i] = nf;
-        bv[i] = nb;
-        xv[i] = nx;
-      }
-      wave_sync();
-    }
-  }
-  // ---- out = rf2 * z (no 1/snr on this diagonal)
-  for (int i = lane; i < np; i += 64) {
-    c64 acc{0, 0};
-    for (int j = 0; j < np; ++j) {
-      const int k = i - j;
-      const c64 t = k >= 0 ? tcol[k] : conj(tcol[-k]);
-      acc = acc + t * xv[j];
-    }
-    vout[f * np + i] = mk<T>((T)acc.x, (T)acc.y);
-  }
+  mmse_toeplitz_wave<T>(ypil + f * np, cvals[f], inv_snr, np, tcol, vout + f * np, lane);
 }
 
 // ---- MP_estimate.m:8-24 for a tile of realisations.  A workgroup of four wavefronts owns FB = 4 * fpw realisations:
@@ -359,6 +292,7 @@ static int part2_tile_run(ofdm_rx_plan* pl, const void* dtx, const int32_t* ddel
   make_plan_view(pl, pv);
   pv.ev = nullptr;
   pv.d_wt = nullptr;
+  pv.mmse_ls = 0;
   FastParams<T> P;
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(N, f64, &tw));
@@ -463,7 +397,7 @@ __global__ __launch_bounds__(256) void mse_tau_kernel(const cx<T>* __restrict__ 
   if (threadIdx.x == 0) {
     const double H = red[0][0] + red[0][1] + red[0][2] + red[0][3];
     const double r = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / H, r2 = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) / H;
-    cvals[f] = 2.0 * M_PI * sqrt(r2 - r * r) * (1.0 / (double)nc) * nps;      // :23-26, df = 1 / N_carrier
+    cvals[f] = 2.0 * M_PI * sqrt(fmax(r2 - r * r, 0.0)) * (1.0 / (double)nc) * nps;      // :23-26, df = 1 / N_carrier
   }
 }
 
@@ -532,6 +466,7 @@ static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, 
   make_plan_view(pl, pv);
   pv.ev = nullptr;
   pv.d_wt = nullptr;
+  pv.mmse_ls = 0;
   FastParams<T> P;
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(N, f64, &tw));

@@ -872,11 +872,13 @@ static int t5_sweep(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfFade* fade,
   TxfDelays dl{};
   dl.n = x.fade_taps;
   for (int t = 0; t < dl.n; ++t) dl.d[t] = ch.delay[t];
+  // a plan in the h = ifft(H_LS) MMSE mode estimates every point at the point's own SNR (a host scalar of the stage's launch)
   OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, nullptr, fade, x,
                             [&](const TxfBuffers& b, int64_t nf, int64_t k) {
-                              OFDM_TRY(ofdm_rx_chain_task5_ex(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
-                                                              (uint32_t*)o.fe + k, b.hest, nullptr,
-                                                              o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags));
+                              const double inv_snr = 1.0 / std::pow(10.0, snr_db[k / frames_per_point] * 0.1);
+                              OFDM_TRY(rx_chain_task5_run(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
+                                                          (uint32_t*)o.fe + k, b.hest, nullptr,
+                                                          o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags, inv_snr));
                               if (!dfn) return (int)OFDM_OK;
                               if (pl->f64)
                                 hipLaunchKernelGGL(t5_frame_nmse_kernel<double>, dim3((unsigned)nf), dim3(256), 0, ctx().stream,

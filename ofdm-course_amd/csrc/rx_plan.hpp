@@ -21,6 +21,18 @@ struct ofdm_rx_plan {
   void *d_mt = nullptr, *d_sb_w = nullptr, *d_sb_c0 = nullptr, *ws_v = nullptr;   // fp32 MMSE mode, factored: M^T, banded spline, v workspace
   int np_pad = 0, sb_bw = 0, sb_span = 0;
   int64_t ws_v_frames = 0;
+  // MMSE mode with h = ifft(H_LS) per frame (ofdm_rx_plan_set_mmse_ls, ofdm_chain_mmse_ls.hip)
+  int mmse_ls = 0;
+  double ls_snr_db = 0.0;    // what a chain call uses
+  double ls_inv_snr = 0.0;   // 1 / snr of a chain call (a BER sweep passes its point's own instead: rx_chain_task5_run)
+  double ls_cscale = 0.0;    // 2 pi df Nps (MMSE_CE.m:15,:25-26)
+  void* d_ls_aq = nullptr;   // the moment forms A_q [3][np][np] c64 (mmse_ls_forms.hpp)
+  void* d_ls_wt = nullptr;   // fp64: the spline operator as W^T [np][ls_m_pad] c64
+  int ls_m_pad = 0;
+  void *d_ls_bw = nullptr, *d_ls_bc0 = nullptr;   // fp32: the spline operator cut to its band (spline_band_kernel)
+  int ls_bw = 0, ls_span = 0;
+  void* ws_lsv = nullptr;    // [n_frames][np] MMSE estimate at the pilots
+  size_t ws_lsv_bytes = 0;
   std::vector<int32_t> pilot_loc;      // 1-based, as given
   int data_mod4 = 15;                  // bit r set: some data carrier has (0-based) index = r mod 4
   int64_t ws_frames = 0;
@@ -60,12 +72,16 @@ struct ofdm_rx_plan {
 
 // ofdm_chain.hip: DeScrambler as a pass over the packed decisions (every path but the wave-per-frame symbol kernel)
 namespace ofdm {
+// ofdm_chain.hip: the body of ofdm_rx_chain_task5_ex; ls_inv_snr as in make_plan_view (the BER sweeps: the point's SNR)
+int rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                       uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
 }
 
 // view of a plan for the fast / split stages
-inline void make_plan_view(ofdm_rx_plan* pl, ofdm::FastPlanView& pv) {
+// ls_inv_snr >= 0: the 1 / snr of this call in the h = ifft(H_LS) MMSE mode instead of the plan's
+inline void make_plan_view(ofdm_rx_plan* pl, ofdm::FastPlanView& pv, double ls_inv_snr = -1.0) {
   pv.nfft = pl->nfft; pv.t_guard = pl->t_guard; pv.n_symb = pl->n_symb; pv.n_carrier = pl->n_carrier;
   pv.np = pl->np; pv.nd = pl->nd; pv.k_atoms = pl->k_atoms; pv.taps = pl->taps; pv.bps = pl->bps;
   pv.f64 = pl->f64; pv.frame_words = pl->frame_words;
@@ -81,6 +97,10 @@ inline void make_plan_view(ofdm_rx_plan* pl, ofdm::FastPlanView& pv) {
   pv.d_mt = pl->d_mt; pv.np_pad = pl->np_pad; pv.sb_bw = pl->sb_bw; pv.sb_span = pl->sb_span; pv.d_sb_w = (const float*)pl->d_sb_w;
   pv.d_sb_c0 = (const int32_t*)pl->d_sb_c0; pv.ws_v = &pl->ws_v; pv.ws_v_frames = &pl->ws_v_frames;
   pv.ws_x = &pl->ws_x; pv.ws_x_elems = &pl->ws_x_elems;
+  pv.mmse_ls = pl->mmse_ls; pv.ls_inv_snr = ls_inv_snr >= 0.0 ? ls_inv_snr : pl->ls_inv_snr; pv.ls_cscale = pl->ls_cscale; pv.d_ls_aq = pl->d_ls_aq;
+  pv.d_ls_wt = pl->d_ls_wt; pv.ls_m_pad = pl->ls_m_pad; pv.d_ls_bw = (const float*)pl->d_ls_bw;
+  pv.d_ls_bc0 = (const int32_t*)pl->d_ls_bc0; pv.ls_bw = pl->ls_bw; pv.ls_span = pl->ls_span;
+  pv.ws_lsv = &pl->ws_lsv; pv.ws_lsv_bytes = &pl->ws_lsv_bytes;
   pv.data_mod4 = pl->data_mod4;
   pv.descr = pl->descr;
 }

@@ -25,10 +25,15 @@ rx_chain_task5(want_mer) per tile otherwise).  The two MER_func sums travel in a
 --fused --fading {EPA,EVA,ETU} (C5 / M): a channel realisation per frame instead of the one channel cfg.taps -- the Monte-Carlo
 runs of T5/Task5_part2.m:148-155 at sweep rate, through `RxPlan.ber_sweep(fading=common.fading_profile(...))`
 (ofdm_ber_sweep_task5_fading), with the same tile keys and dealing.  The profile's delays are taken at FADING_SAMPLING_RATE; the
-estimator sees a delay only below the plan's K dictionary columns (ETU's last taps lie beyond M's 128: an error floor, as
+OMP estimator sees a delay only below the plan's K dictionary columns (ETU's last taps lie beyond M's 128: an error floor, as
 for any echo the dictionary cannot hold).  --nmse adds per point `nmse_sums` and `NMSE`, the channel-estimate error against
 fft(h_f) on carriers 1..N_carrier averaged over the point's frames (T5/Task5_part2.m:202-205,:318); the sums are doubles and
 travel in the float64 all-reduce.  The JSON line names the profile under "fading".
+
+--estimator mmse-ls (C5 / M): MMSE_CE with h = ifft(H_est_LS) per frame, the call of T5/Main_model_Task_5.m:178-180 and
+:317-319 (`RxPlan.set_mmse_ls`): no channel is handed to the receiver, every point is estimated at its own SNR, and the plan
+decodes all points of a batch in one call with --fused, with --fading, --mer and --nmse as for omp.  (--estimator mmse is the
+fixed-h form of T5/Task5_part2.m:176-177: one point per call, no --fading.)  The JSON line names the estimator.
 
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
@@ -57,8 +62,8 @@ def check_fading(config, estimator, fused, fading, nmse):
         return "--fading needs --fused"
     if config not in ("C5", "M"):
         return "--fading is for the Task-5 receiver (configs C5 and M)"
-    if estimator != "omp":
-        return "--fading needs the OMP estimator (an MMSE plan is built for one channel)"
+    if estimator not in ("omp", "mmse-ls"):
+        return "--fading needs the OMP or the mmse-ls estimator (a fixed-h MMSE plan is built for one channel)"
     return None
 
 
@@ -105,6 +110,8 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     for bi, sis in by_batch.items():
         keys = [sweep.tile_seed_stream(seed, si, bi, frames_per_tile) for si in sis]
         whole = task4 or (fused and estimator != "mmse")
+        if estimator == "mmse-ls" and not task4 and whole:
+            plan.set_mmse_ls(cfg.SNR_dB)                       # (the sweep estimates every point at the point's own SNR)
         for g in [list(range(len(sis)))] if whole else [[i] for i in range(len(sis))]:
             pts = [sis[i] for i in g]
             seeds, stream0 = [keys[i][0] for i in g], keys[g[0]][1]
@@ -128,6 +135,8 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
                 data = fr.make_frames_device(cfg, ofdm, plan, frames_per_tile, seed=seeds[0], device=dev, frame0=stream0)
                 if estimator == "mmse":
                     plan.set_mmse(hh, cfg.SNR_dB)
+                elif estimator == "mmse-ls":
+                    plan.set_mmse_ls(cfg.SNR_dB)
                 out = ofdm.rx_chain_task5(plan, data["rx"], ref_bits_packed=data["packed"], want_mer=mer)
                 errors, mer_sums = out["errors"].sum(), out["mer_sums"].sum(dim=0) if mer else None
             cnt[pts, 0] += errors
@@ -174,7 +183,8 @@ def parser():
     ap.add_argument("--frames-per-tile", type=int, default=32)
     ap.add_argument("--snrs", type=float, nargs="*", default=None)
     ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp32")
-    ap.add_argument("--estimator", choices=["omp", "mmse"], default="omp")
+    ap.add_argument("--estimator", choices=["omp", "mmse", "mmse-ls"], default="omp",
+                    help="mmse: MMSE_CE with the true channel (one point per call); mmse-ls: MMSE_CE with h = ifft(H_LS) per frame")
     ap.add_argument("--backend", default="nccl", help="nccl = RCCL over xGMI; gloo for rehearsals")
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank on this GPU")
     ap.add_argument("--fused", action="store_true", help="reference order (Noise -> conv) through RxPlan.ber_sweep")
