@@ -405,6 +405,65 @@ int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* plan, const void* h, int h_len, int st
                             uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
                             int64_t mer_skip, double* mer_sums_out /* [n_points][2] */,
                             double* frame_mer_sums_out /* [n_points][frames_per_point][2] */, int flags);
+/* ofdm_tx_frames_fading with the Task-4 impairments: a channel drawn per frame (T5/Task5_part2.m:148-155) behind the
+ * STO / CFO of T4/Main_model_Task_4.m:94-110,:257-267, in the reference order, per frame f of length len:
+ *   w[j] = x[j] + sigma_f n(j)                  Noise.m, the noise of the SOURCE index j
+ *   s[m] = w[m + sto_f] (0 outside 0..len-1)    add_STO.m, either sign
+ *   z[m] = s[m] exp(2 pi i cfo_f m / Nfft)      add_CFO.m on the shifted stream
+ *   rx[n] = sum_t a_{f,t} z[n - tap_delay[t]]   conv with the frame's own taps, truncated
+ * still in three sample passes.  tap_delay / tap_power / n_taps, the draw of a_{f,t} (Philox counter (t, 0, frame0 + f, 3)) and
+ * taps_out are those of ofdm_tx_frames_fading; sto_mode / cfo_mode / the values, the draw of sto_f / cfo_f (counter
+ * (0, 0, frame0 + f, 2)) and sto_out / cfo_out those of ofdm_tx_frames_fused_ex: the two per-frame draws are independent.
+ * With both modes 0 the frames are bit-identical to ofdm_tx_frames_fading's.  The other arguments, outputs and limits are
+ * those of ofdm_tx_frames_fading.  Results depend on (seed, frame0 + f, t) only, never on the batching. */
+int ofdm_tx_frames_fading_ex(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps, double snr_db,
+                             uint64_t seed, int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, int sto_mode,
+                             int64_t sto_value, int cfo_mode, double cfo_value, void* rx_out, uint8_t* ref_bits_out,
+                             uint8_t* sc_ref_bits_out, double* taps_out /* [n_frames][n_taps][2] */, int64_t* sto_out,
+                             double* cfo_out, int flags);
+/* ofdm_ber_sweep_task4_ex with the error of estimate_channel summed beside the bit errors -- the NMSE(SNR) study of
+ * T4/Main_model_Task_4.m:205-239 (T5/Task5_part2.m:202-205 per realisation) over frames_per_point realisations.  Per frame
+ *   frame_nmse_out[n_points][frames_per_point] (double, optional) = sum_{k=0}^{N_carrier-1} |H(k) - Hest_f(k)|^2 with Hest_f
+ *   the h_out of ofdm_rx_chain_task4_ex for that frame and H(k) = sum_t h_t exp(-2 pi i d_t k / Nfft) in double over the
+ *   nonzero taps of h (= H_freq(1:N_carrier) of get_MP_channel_resp; 1 without h);
+ *   nmse_sums_out[n_points] (double, optional) = the point's sum; its NMSE is nmse_sums / (frames_per_point * N_carrier).
+ * Both are summed in the fixed order of ofdm_ber_sweep_task5_fading (no atomics), the points after the last chunk: bitwise
+ * independent of max_frames_per_chunk.  Rules:
+ *   the NMSE outputs need mp_desync != 0 (otherwise there is no estimate): OFDM_ERR_ARG, the plan stays usable;
+ *   frames with status 1, -1 or -2 are included as decoded; a non-finite estimate gives a NaN frame value and a NaN point
+ *   sum, as the Task-4 MER sums do;
+ *   the value is the reference's plain difference.  With time_desync / freq_desync on, fine_sync takes the channel's mean
+ *   group delay and common phase out of X before estimate_channel (T4:313-318), so the difference then contains that ramp
+ *   and does not fall to the noise floor: it is reported as it is, not corrected;
+ *   the default chunk budget counts the stored estimates.
+ * With both NMSE outputs NULL this is ofdm_ber_sweep_task4_ex: every output bit for bit, no estimate stored.  OFDM_DEVICE keeps
+ * the no-host-synchronisation rule of ofdm_ber_sweep_task4. */
+int ofdm_ber_sweep_task4_nmse(ofdm_rx_plan* plan, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                              double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                              const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                              const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                              uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                              int64_t mer_skip, double* mer_sums_out /* [n_points][2] */,
+                              double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
+                              double* nmse_sums_out /* [n_points] */,
+                              double* frame_nmse_out /* [n_points][frames_per_point] */, int flags);
+/* ofdm_ber_sweep_task4_nmse over channel realisations: the frames of point p are those of ofdm_tx_frames_fading_ex(tap_delay,
+ * tap_power, n_taps, snr_db[p], seeds[p], sto / cfo modes and values, ...), each with its own channel, decoded by
+ * ofdm_rx_chain_task4_ex -- the synchroniser (AutoCorrFunction -> remove_IFO -> fine_sync) and the spline equaliser swept over
+ * the echo profiles of T5/Task5_part2.m:148-155.  The NMSE outputs are against the frame's own channel,
+ *   H_f(k) = sum_t a_{f,t} exp(-2 pi i tap_delay[t] k / Nfft) in double, from the drawn amplitudes;
+ * every other argument, output and rule (mp_desync for the NMSE outputs, the statuses included, NaN, the fine_sync ramp, the
+ * chunk budget -- which also counts the amplitudes -- and OFDM_DEVICE) is that of ofdm_ber_sweep_task4_nmse. */
+int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value, int time_desync,
+                                int freq_desync, int mp_desync, const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                int64_t max_frames_per_chunk, uint64_t* errors_out, uint64_t* status_counts_out,
+                                double* cfo_abs_err_out, uint32_t* frame_errors_out, int64_t mer_skip,
+                                double* mer_sums_out /* [n_points][2] */,
+                                double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
+                                double* nmse_sums_out /* [n_points] */,
+                                double* frame_nmse_out /* [n_points][frames_per_point] */, int flags);
 /* Per-frame DeScrambler inside ofdm_rx_chain_task5 / ofdm_rx_chain_task4 (T5/DeScrambler.m:1-16 with
  * the register reset for every frame, T5/Main_model_Task_5.m:257-274, T4/Main_model_Task_4.m:354-364): the demapped bits
  * of a frame go through d[i] = s[i] ^ s[i-13] ^ s[i-14], s[-m] = reg15[m-1], before they are written to bits_out and

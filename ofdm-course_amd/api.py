@@ -809,16 +809,17 @@ class RxPlan:
         Returns dict(rx=[frame_samples, n_frames], packed=[n_frames, frame_bytes] (the payload bits)
         (+ sc_packed = the scrambled bits when Register is given) (+ Time_Delay [n_frames] int64, Freq_Shift [n_frames]
         float64 with want_draws)); torch CUDA tensors when `device` is given.
-        fading=(delays, powers) (ofdm_tx_frames_fading; not with h, Time_Delay or Freq_Shift): a channel per frame on one
+        fading=(delays, powers) (ofdm_tx_frames_fading; not with h): a channel per frame on one
         tap-delay line -- 0-based distinct sample delays and linear powers (drivers.common.fading_profile gives the 3GPP
         ones) -- the stand-in for lteFadingChannel of T5/Task5_part2.m:148-155: tap t of frame f is sqrt(powers[t] /
         sum(powers)) e^{2 pi i u} with u from Philox counter (t, 0, frame0 + f, 3), key `seed`.  want_taps adds
-        taps=[n_frames, n_taps] complex128, those amplitudes."""
+        taps=[n_frames, n_taps] complex128, those amplitudes.  With Time_Delay / Freq_Shift / want_draws too
+        (ofdm_tx_frames_fading_ex): Noise -> add_STO -> add_CFO -> conv with the frame's own taps, the two per-frame draws
+        independent of each other."""
         n_frames = int(n_frames)
         if fading is not None:
-            if Time_Delay is not None or Freq_Shift is not None or want_draws:
-                raise OfdmError("tx_frames_fused: fading does not combine with Time_Delay / Freq_Shift")
-            return self._tx_frames_fading(n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps)
+            return self._tx_frames_fading(n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps, Time_Delay,
+                                          Freq_Shift, want_draws)
         if want_taps:
             raise OfdmError("tx_frames_fused: want_taps needs fading")
         ex = Time_Delay is not None or Freq_Shift is not None or want_draws
@@ -843,21 +844,32 @@ class RxPlan:
             out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
-    def _tx_frames_fading(self, n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps):
+    def _tx_frames_fading(self, n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps, Time_Delay=None,
+                          Freq_Shift=None, want_draws=False):
         keep_f, pdl, ppw, nt = self._fading_args(h, fading, "tx_frames_fused")
+        ex = Time_Delay is not None or Freq_Shift is not None or want_draws
         scr = Register is not None
-        (rx, packed, scp, taps), ptrs, flags = self._outputs(
+        (rx, packed, scp, taps, sto, cfo), ptrs, flags = self._outputs(
             device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
             ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bytes), np.uint8) if scr else None,
-            ((n_frames, nt), np.complex128) if want_taps else None)
+            ((n_frames, nt), np.complex128) if want_taps else None, ((n_frames,), np.int64) if want_draws else None,
+            ((n_frames,), np.float64) if want_draws else None)
         keep, _, _, pr = self._fused_args(None, Register, "tx_frames_fused")
-        L.check(self.lib.ofdm_tx_frames_fading(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames, pr,
-                                               *ptrs, flags), "tx_frames_fading")
+        if ex:
+            sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
+            cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
+            L.check(self.lib.ofdm_tx_frames_fading_ex(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames,
+                                                      pr, sm, int(sv), cm, float(cv), *ptrs, flags), "tx_frames_fading_ex")
+        else:                           # without impairments: no STO / CFO draw kernel, the channel pass without them
+            L.check(self.lib.ofdm_tx_frames_fading(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames,
+                                                   pr, *ptrs[:4], flags), "tx_frames_fading")
         out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
         if scr:
             out["sc_packed"] = scp
         if want_taps:
             out["taps"] = taps
+        if want_draws:
+            out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
@@ -918,7 +930,7 @@ class RxPlan:
     def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
                         freq_desync=None, mp_desync=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                         want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, mer_skip=0,
-                        want_frame_mer=False):
+                        want_frame_mer=False, fading=None, want_nmse=False, want_frame_nmse=False):
         """One device-resident tile of a BER(SNR) sweep of the Task-4 receiver (ofdm_ber_sweep_task4): for every SNR of
         `SNRs` the frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p], Time_Delay,
         Freq_Shift) decoded by rx_chain_task4(time_desync, freq_desync, mp_desync) on this plan.  A desync flag left at None
@@ -932,27 +944,55 @@ class RxPlan:
         want_mer (ofdm_ber_sweep_task4_ex): also mer_sums=[n, 2], the MER_func sums of each point's frames (RX_IQ from
         0-based index mer_skip on, frames concatenated), and MER_dB=[n] (computed on `device` when it is given); with
         want_frame_mer the per-frame sums frame_mer_sums=[n, frames_per_point, 2].  Time_Delay=12, time_desync=1,
-        freq_desync=0, mp_desync=0, mer_skip=Nfft+T_guard is the MER(SNR) study of T4/Main_model_Task_4.m:136-200."""
+        freq_desync=0, mp_desync=0, mer_skip=Nfft+T_guard is the MER(SNR) study of T4/Main_model_Task_4.m:136-200.
+        fading=(delays, powers) (ofdm_ber_sweep_task4_fading; not with h): the frames of tx_frames_fused(fading=..., Time_Delay,
+        Freq_Shift), a channel realisation per frame (T5/Task5_part2.m:148-155); mp_desync left at None is then on.
+        want_nmse (ofdm_ber_sweep_task4_nmse / _fading; needs mp_desync): also nmse_sums=[n], per point the sum over its frames
+        of sum_k |H(k) - H_est_f(k)|^2 on carriers 1..N_carrier against fft(h, Nfft), or with fading against the frame's own
+        channel, and NMSE=[n] = nmse_sums / (frames_per_point * N_carrier) (T4/Main_model_Task_4.m:205-239); with
+        want_frame_nmse the per-frame sums frame_nmse=[n, frames_per_point].  The plain difference of the reference: with
+        time_desync / freq_desync on, fine_sync has taken the channel's mean delay and common phase out of what
+        estimate_channel sees, and the difference contains that ramp."""
+        if want_frame_nmse and not want_nmse:
+            raise OfdmError("ber_sweep_task4: want_frame_nmse needs want_nmse")
         snr, sd = self._points(SNRs, seeds, seed, "ber_sweep_task4")
         n, fpp = snr.size, int(frames_per_point)
         sm, sv = _imp_mode(Time_Delay, "ber_sweep_task4")
         cm, cv = _imp_mode(Freq_Shift, "ber_sweep_task4")
         td = Time_Delay is not None if time_desync is None else bool(time_desync)
         fd = Freq_Shift is not None if freq_desync is None else bool(freq_desync)
-        md = h is not None if mp_desync is None else bool(mp_desync)
-        (err, stc, cae, fe, ms, fm), ptrs, flags = self._outputs(
+        md = (h is not None or fading is not None) if mp_desync is None else bool(mp_desync)
+        (err, stc, cae, fe, ms, fm, ns, fn), ptrs, flags = self._outputs(
             device, ((n,), np.uint64), ((n, 4), np.uint64), ((n,), np.float64),
             ((n, fpp), np.uint32) if want_frame_errors else None, ((n, 2), np.float64) if want_mer else None,
-            ((n, fpp, 2), np.float64) if want_mer and want_frame_mer else None)
-        keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-        L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd), int(md),
-                                                 snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
-                                                 int(frame0), pr, int(max_frames_per_chunk), *ptrs[:4],
-                                                 int(mer_skip) if want_mer else 0, *ptrs[4:], flags),
-                "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
+            ((n, fpp, 2), np.float64) if want_mer and want_frame_mer else None, ((n,), np.float64) if want_nmse else None,
+            ((n, fpp), np.float64) if want_frame_nmse else None)
+        tail = (snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0))
+        mer = (int(mer_skip) if want_mer else 0, *ptrs[4:6])
+        if fading is not None:
+            keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep_task4")
+            keep, _, _, pr = self._fused_args(None, Register, "ber_sweep_task4")
+            L.check(self.lib.ofdm_ber_sweep_task4_fading(self.handle, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(td),
+                                                         int(fd), int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4],
+                                                         *mer, *ptrs[6:], flags), "ber_sweep_task4_fading")
+        elif want_nmse:
+            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
+            L.check(self.lib.ofdm_ber_sweep_task4_nmse(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
+                                                       int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer,
+                                                       *ptrs[6:], flags), "ber_sweep_task4_nmse")
+        else:
+            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
+            L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
+                                                     int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer, flags),
+                    "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
         host = device is None
         out = dict(errors=err.astype(np.int64) if host else err, bits=fpp * self.frame_bits,
                    status_counts=stc.astype(np.int64) if host else stc, cfo_abs_err=cae)
+        if want_nmse:
+            out["nmse_sums"] = ns
+            out["NMSE"] = ns / float(max(fpp, 1) * self.N_carrier)
+        if want_frame_nmse:
+            out["frame_nmse"] = fn
         if want_frame_errors:
             out["frame_errors"] = fe
         if want_mer:

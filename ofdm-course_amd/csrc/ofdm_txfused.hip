@@ -37,12 +37,21 @@
 //                                   d_t k mod Nfft reduced in integers), sum_k |H_f(k) - Hest_f(k)|^2 over 1..N_carrier in a
 //                                   fixed order (T5/Task5_part2.m:202-205); the points through t4_point_mer_kernel<1>
 //
+// ofdm_tx_frames_fading_ex / ofdm_ber_sweep_task4_fading / ofdm_ber_sweep_task4_nmse put both together for the Task-4 receiver
+// (T4/Main_model_Task_4.m:94-110,:257-267 over the realisations of T5/Task5_part2.m:148-155, NMSE of T4:205-239):
+//   tx_channel_imp_fade_kernel<T>   tx_channel_body with IMP and FADE on: the load stage is tx_channel_imp_kernel's (Noise ->
+//                                   add_STO -> add_CFO), the frame's amplitudes staged behind the segment as in
+//                                   tx_channel_fade_kernel; the two per-frame draws stay independent (counter word 3 = 2 / 3)
+//   tx_static_amp_kernel            the static channel's taps into device memory once per sweep, so that t5_frame_nmse_kernel
+//                                   reads them with a frame stride of 0
+//
 // Host side: both generator entries forward to one body (txf_frames); given impairments it launches the draw kernel and
 // tx_channel_imp_kernel, else tx_channel_fused_kernel.  The two sweeps share their common checks and outputs
 // (txf_check_sweep, txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points, the receiver
 // passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
 // per-point reduction.  The fading entries share those bodies: txf_frames / txf_sweep_points given a TxfFade launch
-// tx_fade_draw_kernel and tx_channel_fade_kernel, and both Task-5 sweep entries forward to t5_sweep.
+// tx_fade_draw_kernel and tx_channel_fade_kernel (tx_channel_imp_fade_kernel given impairments too), both Task-5 sweep entries
+// forward to t5_sweep and the Task-4 sweep entries to t4_sweep.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -267,6 +276,18 @@ __global__ __launch_bounds__(256) void tx_channel_fade_kernel(const cx<T>* __res
   tx_channel_body<T, false, true>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, nullptr, nullptr, 0.0, taps, famp);
 }
 
+// IMP and FADE: add_STO -> add_CFO of the frame's draws between Noise and the conv with the frame's own amplitudes
+// (T4/Main_model_Task_4.m:94-110,:257-267 per realisation of T5/Task5_part2.m:148-155); dynamic LDS as tx_channel_fade_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void tx_channel_imp_fade_kernel(const cx<T>* __restrict__ tx, cx<T>* __restrict__ rx,
+                                                                  const double* __restrict__ partial, int n_symb, int64_t len,
+                                                                  double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
+                                                                  const int64_t* __restrict__ sto,
+                                                                  const double* __restrict__ cfo, double inv_nfft,
+                                                                  const c64* __restrict__ famp, TxfTaps<T> taps) {
+  tx_channel_body<T, true, true>(tx, rx, partial, n_symb, len, snr_lin, k0, k1, stream0, sto, cfo, inv_nfft, taps, famp);
+}
+
 // per-frame channel draw, the sibling of tx_draw_kernel: tap t of frame f is gain[t] (cospi(2u) + i sinpi(2u)) with
 // u = (word0 + 0.5) 2^-32 of Philox counter (t, 0, stream0 + f, 3) -- static taps with random initial phases, the stand-in
 // for lteFadingChannel of drivers/common.py:fading_taps drawn on the device.  amp / taps_out: [n_frames][n_taps].
@@ -291,9 +312,19 @@ __global__ __launch_bounds__(256) void tx_fade_draw_kernel(c64* __restrict__ amp
   if (taps_out) taps_out[i] = a;
 }
 
+// the taps of a static channel (host doubles in the kernel arguments) -> device memory, for t5_frame_nmse_kernel
+struct TxfAmps {
+  c64 a[TXF_MAX_TAPS];
+};
+
+__global__ __launch_bounds__(64) void tx_static_amp_kernel(c64* __restrict__ amp, TxfAmps amps, int n_taps) {
+  if ((int)threadIdx.x < n_taps) amp[threadIdx.x] = amps.a[threadIdx.x];
+}
+
 // per frame f of a fading sweep: sum_{k < n_carrier} |H_f(k) - hest[f][k]|^2 with H_f(k) = sum_t a_{f,t} e^{-2 pi i d_t k / Nfft}
 // = fft(h_f, Nfft)(k) of get_MP_channel_resp (T5/Task5_part2.m:160-166,:202-205), in double.  One workgroup per frame: each
 // thread a fixed stride of carriers, a fixed butterfly, the four wave partials paired -- no atomics.
+// amp_stride: dl.n for the amplitudes of a channel per frame [frames][dl.n], 0 for one static channel [dl.n].
 struct TxfDelays {
   int32_t d[TXF_MAX_TAPS];
   int n;
@@ -301,12 +332,12 @@ struct TxfDelays {
 
 template <typename T>
 __global__ __launch_bounds__(256) void t5_frame_nmse_kernel(const c64* __restrict__ amp, const cx<T>* __restrict__ hest,
-                                                            TxfDelays dl, int nfft, int n_carrier,
+                                                            TxfDelays dl, int64_t amp_stride, int nfft, int n_carrier,
                                                             double* __restrict__ frame_nmse) {
   __shared__ c64 a[TXF_MAX_TAPS];
   __shared__ double part[4];
   const int64_t f = blockIdx.x;
-  if ((int)threadIdx.x < dl.n) a[threadIdx.x] = amp[f * dl.n + threadIdx.x];
+  if ((int)threadIdx.x < dl.n) a[threadIdx.x] = amp[f * amp_stride + threadIdx.x];
   __syncthreads();
   const double inv = 2.0 / (double)nfft;
   double s = 0;
@@ -505,8 +536,9 @@ struct TxfImp {
   double* cfo = nullptr;
 };
 
-// fade (optional, no entry combines it with imp): tx_channel_fade_kernel with the chunk's amplitudes fade->amp;
-// imp (optional): tx_channel_imp_kernel with the chunk's draws imp->sto / imp->cfo; else tx_channel_fused_kernel
+// fade (optional): tx_channel_fade_kernel with the chunk's amplitudes fade->amp;
+// imp (optional): tx_channel_imp_kernel with the chunk's draws imp->sto / imp->cfo; both: tx_channel_imp_fade_kernel;
+// neither: tx_channel_fused_kernel
 template <typename T>
 static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
                           double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, const TxfImp* imp, const TxfFade* fade,
@@ -514,10 +546,16 @@ static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const vo
   const int64_t len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t dyn = sizeof(cx<T>) * (size_t)(TXF_SEG + ch.halo + (fade ? ch.delay.size() : 0));
   const dim3 grid(cdiv_u(len, TXF_SEG), (unsigned)nf);
-  const void* kernel = fade ? (const void*)tx_channel_fade_kernel<T>
+  const void* kernel = fade ? (imp ? (const void*)tx_channel_imp_fade_kernel<T> : (const void*)tx_channel_fade_kernel<T>)
                             : imp ? (const void*)tx_channel_imp_kernel<T> : (const void*)tx_channel_fused_kernel<T>;
   // > 64 KB for long channels: the attribute is per device, so it is set on every launch (not cached per process)
   OFDM_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+  if (fade && imp) {
+    hipLaunchKernelGGL(tx_channel_imp_fade_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
+                       pl->n_symb, len, snr_lin, k0, k1, stream0, imp->sto, imp->cfo, 1.0 / (double)pl->nfft,
+                       (const c64*)fade->amp, txf_taps<T>(ch));
+    return check_launch("tx_channel_imp_fade_kernel");
+  }
   if (fade) {
     hipLaunchKernelGGL(tx_channel_fade_kernel<T>, grid, dim3(256), dyn, ctx().stream, (const cx<T>*)tx, (cx<T>*)rx, partial,
                        pl->n_symb, len, snr_lin, k0, k1, stream0, (const c64*)fade->amp, txf_taps<T>(ch));
@@ -543,7 +581,7 @@ struct TxfBuffers {
   int64_t* sto = nullptr;                            // impairments on: the chunk's draws
   double* cfo = nullptr;
   c64* amp = nullptr;                                // fading: the chunk's tap amplitudes [ch][n_taps]
-  void* hest = nullptr;                              // fading sweep with NMSE: the chunk's channel estimates [N_carrier x ch]
+  void* hest = nullptr;                              // sweep with NMSE: the chunk's channel estimates [N_carrier x ch]
 };
 
 // what a call adds to the plain generator workspace
@@ -603,7 +641,7 @@ static int64_t txf_chunk(const ofdm_rx_plan* pl, bool scr, bool sweep, int64_t n
 // one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
 // imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
 // fade (optional): a channel per frame -- the draws into fade->amp (and fade->taps_out), the channel pass of
-// tx_channel_fade_kernel
+// tx_channel_fade_kernel; with imp too, both draws and the channel pass of tx_channel_imp_fade_kernel
 static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0,
                         int64_t nf, const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
                         const TxfImp* imp = nullptr, const TxfFade* fade = nullptr) {
@@ -845,6 +883,25 @@ extern "C" int ofdm_tx_frames_fused_ex(ofdm_rx_plan* pl, const void* h, int h_le
                     sto_out, cfo_out, nullptr, flags);
 }
 
+extern "C" int ofdm_tx_frames_fading_ex(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                        double snr_db, uint64_t seed, int64_t frame0, int64_t n_frames,
+                                        const uint8_t* scr_reg15, int sto_mode, int64_t sto_value, int cfo_mode,
+                                        double cfo_value, void* rx_out, uint8_t* ref_bits_out, uint8_t* sc_ref_bits_out,
+                                        double* taps_out, int64_t* sto_out, double* cfo_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_frames >= 0 && rx_out, "tx_frames_fading_ex: bad arguments");
+  OFDM_TRY(txf_check_plan(pl, flags, frame0, n_frames, "tx_frames_fading_ex"));
+  OFDM_TRY(txf_check_modes(sto_mode, cfo_mode, "tx_frames_fading_ex"));
+  OFDM_ARG(scr_reg15 || !sc_ref_bits_out, "tx_frames_fading_ex: sc_ref_bits_out needs the Scrambler register");
+  TxfImp imp;
+  imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
+  TxfChannel ch;
+  TxfFade fade;
+  OFDM_TRY(txf_fading(tap_delay, tap_power, n_taps, "tx_frames_fading_ex", ch, fade));
+  return txf_frames(pl, ch, snr_db, seed, frame0, n_frames, scr_reg15, &imp, &fade, rx_out, ref_bits_out, sc_ref_bits_out,
+                    sto_out, cfo_out, taps_out, flags);
+}
+
 // the body of both Task-5 sweep entries, after their argument checks: ch the static channel, or with fade the delay line of a
 // channel per frame; nmse_sums_out / frame_nmse_out (fading only): the channel-estimate error sums
 static int t5_sweep(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfFade* fade, const double* snr_db, const uint64_t* seeds,
@@ -882,12 +939,12 @@ static int t5_sweep(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfFade* fade,
                               if (!dfn) return (int)OFDM_OK;
                               if (pl->f64)
                                 hipLaunchKernelGGL(t5_frame_nmse_kernel<double>, dim3((unsigned)nf), dim3(256), 0, ctx().stream,
-                                                   (const c64*)b.amp, (const c64*)b.hest, dl, pl->nfft, pl->n_carrier,
-                                                   (double*)dfn + k);
+                                                   (const c64*)b.amp, (const c64*)b.hest, dl, (int64_t)dl.n, pl->nfft,
+                                                   pl->n_carrier, (double*)dfn + k);
                               else
                                 hipLaunchKernelGGL(t5_frame_nmse_kernel<float>, dim3((unsigned)nf), dim3(256), 0, ctx().stream,
-                                                   (const c64*)b.amp, (const c32*)b.hest, dl, pl->nfft, pl->n_carrier,
-                                                   (double*)dfn + k);
+                                                   (const c64*)b.amp, (const c32*)b.hest, dl, (int64_t)dl.n, pl->nfft,
+                                                   pl->n_carrier, (double*)dfn + k);
                               return check_launch("t5_frame_nmse_kernel");
                             }));
   hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)o.fe,
@@ -944,15 +1001,15 @@ extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, 
                                  max_frames_per_chunk, errors_out, frame_errors_out, nullptr, nullptr, flags);
 }
 
-extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
-                                       int cfo_mode, double cfo_value, int time_desync, int freq_desync, int mp_desync,
-                                       const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,
-                                       int64_t frame0, const uint8_t* scr_reg15, int64_t max_frames_per_chunk,
-                                       uint64_t* errors_out, uint64_t* status_counts_out, double* cfo_abs_err_out,
-                                       uint32_t* frame_errors_out, int64_t mer_skip, double* mer_sums_out,
-                                       double* frame_mer_sums_out, int flags) {
-  OFDM_TRY(ensure_init());
-  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4: bad arguments");
+// the body of the Task-4 sweep entries: the argument checks they share, then ch the static channel, or with fade the delay line
+// of a channel per frame; nmse_sums_out / frame_nmse_out (optional): the channel-estimate error sums against ch's H (static:
+// one H for every frame) or the frame's own H_f (fade)
+static int t4_sweep(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfFade* fade, int sto_mode, int64_t sto_value, int cfo_mode,
+                    double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                    const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                    const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out, uint64_t* status_counts_out,
+                    double* cfo_abs_err_out, uint32_t* frame_errors_out, int64_t mer_skip, double* mer_sums_out,
+                    double* frame_mer_sums_out, double* nmse_sums_out, double* frame_nmse_out, int flags) {
   OFDM_ARG(max_frames_per_chunk >= 0 && max_frames_per_chunk <= 65535,
            "ber_sweep_task4: max_frames_per_chunk must be 0..65535 (the limit of rx_chain_task4)");
   OFDM_TRY(txf_check_sweep(pl, snr_db, seeds, n_points, frames_per_point, frame0, flags, "ber_sweep_task4"));
@@ -960,21 +1017,24 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(txf_check_descrambler(pl, scr_reg15, "ber_sweep_task4"));
   OFDM_ARG(mer_skip >= 0 && mer_skip < (int64_t)pl->nd * pl->n_symb,
            "ber_sweep_task4_ex: mer_skip must be 0 .. nd * N_symb - 1 (%lld)", (long long)mer_skip);
-  TxfChannel ch;
-  OFDM_TRY(txf_channel(h, h_len, pl->f64 != 0, ch));
+  OFDM_ARG(!(nmse_sums_out || frame_nmse_out) || mp_desync,
+           "ber_sweep_task4: the NMSE outputs need mp_desync (without estimate_channel there is no estimate)");
   if (n_points == 0) return OFDM_OK;
   Stage st(flags);
   const int64_t NF = n_points * frames_per_point;
   TxfSweepOut o;
   OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
                              o));
-  void *dsc, *dabs;
+  void *dsc, *dabs, *dns, *dfn;
   OFDM_TRY(st.out(status_counts_out, sizeof(uint64_t) * 4 * (size_t)n_points, &dsc));
   OFDM_TRY(st.out(cfo_abs_err_out, sizeof(double) * (size_t)n_points, &dabs));
+  OFDM_TRY(st.out(nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
+  OFDM_TRY(st.out(frame_nmse_out, sizeof(double) * (size_t)NF, &dfn));
   hipStream_t s = ctx().stream;
   if (frames_per_point == 0) {
     if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, s));
     if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, s));
+    if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, s));
     return st.finish();
   }
   // the per-frame values of every point, reduced once after the last chunk
@@ -985,9 +1045,13 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)NF, &dstat));
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dsto));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dcfo));
+  if (dns && !dfn) OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dfn));
   const bool scr = scr_reg15 != nullptr;
+  const int n_taps = (int)ch.delay.size();
   TxfExtras x;
   x.imp = true;
+  x.fade_taps = fade ? n_taps : 0;
+  x.hest = dfn != nullptr;
   // default chunk: the generator workspace and the Task-4 arena (shared with ofdm_task5_part2_tile) budgeted together
   int64_t CH = max_frames_per_chunk;
   if (CH == 0)                                                  // (+ the per-frame MER sums when they are wanted)
@@ -999,20 +1063,98 @@ extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_le
   imp.sto_mode = sto_mode; imp.sto_value = sto_value; imp.cfo_mode = cfo_mode; imp.cfo_value = cfo_value;
   imp.sto = (int64_t*)dsto;
   imp.cfo = (double*)dcfo;
-  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, &imp, nullptr, x,
+  TxfDelays dl{};
+  void* dstatic = nullptr;                                      // NMSE against a static channel: its taps, read with stride 0
+  if (dfn) {
+    dl.n = n_taps;
+    for (int t = 0; t < n_taps; ++t) dl.d[t] = ch.delay[t];
+    if (!fade) {
+      TxfAmps sa{};
+      for (int t = 0; t < n_taps; ++t) sa.a[t] = ch.amp[t];
+      OFDM_TRY(st.scratch(sizeof(c64) * (size_t)std::max(n_taps, 1), &dstatic));   // an all-zero h has no taps: H = 0
+      hipLaunchKernelGGL(tx_static_amp_kernel, dim3(1), dim3(64), 0, s, (c64*)dstatic, sa, n_taps);
+      OFDM_TRY(check_launch("tx_static_amp_kernel"));
+    }
+  }
+  OFDM_TRY(txf_sweep_points(pl, ch, snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, CH, &imp, fade, x,
                             [&](const TxfBuffers& b, int64_t nf, int64_t k) {
-                              return ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr,
-                                                            (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
-                                                            (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
-                                                            nullptr, mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
-                                                            rxflags);
+                              OFDM_TRY(ofdm_rx_chain_task4_ex(pl, b.rx, nf, time_desync, freq_desync, mp_desync, nullptr,
+                                                              (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
+                                                              (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
+                                                              b.hest, mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
+                                                              rxflags));
+                              if (!dfn) return (int)OFDM_OK;
+                              const c64* amp = fade ? (const c64*)b.amp : (const c64*)dstatic;
+                              const int64_t stride = fade ? n_taps : 0;
+                              if (pl->f64)
+                                hipLaunchKernelGGL(t5_frame_nmse_kernel<double>, dim3((unsigned)nf), dim3(256), 0, s, amp,
+                                                   (const c64*)b.hest, dl, stride, pl->nfft, pl->n_carrier, (double*)dfn + k);
+                              else
+                                hipLaunchKernelGGL(t5_frame_nmse_kernel<float>, dim3((unsigned)nf), dim3(256), 0, s, amp,
+                                                   (const c32*)b.hest, dl, stride, pl->nfft, pl->n_carrier, (double*)dfn + k);
+                              return check_launch("t5_frame_nmse_kernel");
                             }));
   hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, s, (const uint32_t*)o.fe,
                      (const int32_t*)dstat, (const double*)dfo, (const int32_t*)difo, (const double*)dcfo, frames_per_point,
                      freq_desync ? 1 : 0, (unsigned long long*)o.err, (unsigned long long*)dsc, (double*)dabs);
   OFDM_TRY(check_launch("t4_point_reduce_kernel"));
   OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
+  if (dns) {
+    hipLaunchKernelGGL(t4_point_mer_kernel<1>, dim3((unsigned)n_points), dim3(256), 0, s, (const double*)dfn,
+                       frames_per_point, (double*)dns);
+    OFDM_TRY(check_launch("t4_point_mer_kernel"));
+  }
   return st.finish();
+}
+
+extern "C" int ofdm_ber_sweep_task4_nmse(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
+                                         int cfo_mode, double cfo_value, int time_desync, int freq_desync, int mp_desync,
+                                         const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                         int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                         int64_t max_frames_per_chunk, uint64_t* errors_out, uint64_t* status_counts_out,
+                                         double* cfo_abs_err_out, uint32_t* frame_errors_out, int64_t mer_skip,
+                                         double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
+                                         double* frame_nmse_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4: bad arguments");
+  TxfChannel ch;
+  OFDM_TRY(txf_channel(h, h_len, is_f64(flags), ch));
+  return t4_sweep(pl, ch, nullptr, sto_mode, sto_value, cfo_mode, cfo_value, time_desync, freq_desync, mp_desync, snr_db, seeds,
+                  n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk, errors_out, status_counts_out,
+                  cfo_abs_err_out, frame_errors_out, mer_skip, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out,
+                  flags);
+}
+
+extern "C" int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                           int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value, int time_desync,
+                                           int freq_desync, int mp_desync, const double* snr_db, const uint64_t* seeds,
+                                           int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                                           const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                                           uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                                           int64_t mer_skip, double* mer_sums_out, double* frame_mer_sums_out,
+                                           double* nmse_sums_out, double* frame_nmse_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && n_points >= 0 && frames_per_point >= 0 && errors_out, "ber_sweep_task4_fading: bad arguments");
+  TxfChannel ch;
+  TxfFade fade;
+  OFDM_TRY(txf_fading(tap_delay, tap_power, n_taps, "ber_sweep_task4_fading", ch, fade));
+  return t4_sweep(pl, ch, &fade, sto_mode, sto_value, cfo_mode, cfo_value, time_desync, freq_desync, mp_desync, snr_db, seeds,
+                  n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk, errors_out, status_counts_out,
+                  cfo_abs_err_out, frame_errors_out, mer_skip, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out,
+                  flags);
+}
+
+extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
+                                       int cfo_mode, double cfo_value, int time_desync, int freq_desync, int mp_desync,
+                                       const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,
+                                       int64_t frame0, const uint8_t* scr_reg15, int64_t max_frames_per_chunk,
+                                       uint64_t* errors_out, uint64_t* status_counts_out, double* cfo_abs_err_out,
+                                       uint32_t* frame_errors_out, int64_t mer_skip, double* mer_sums_out,
+                                       double* frame_mer_sums_out, int flags) {
+  return ofdm_ber_sweep_task4_nmse(pl, h, h_len, sto_mode, sto_value, cfo_mode, cfo_value, time_desync, freq_desync, mp_desync,
+                                   snr_db, seeds, n_points, frames_per_point, frame0, scr_reg15, max_frames_per_chunk,
+                                   errors_out, status_counts_out, cfo_abs_err_out, frame_errors_out, mer_skip, mer_sums_out,
+                                   frame_mer_sums_out, nullptr, nullptr, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,

@@ -18,6 +18,11 @@ the yardstick) against the generator drawing a channel per frame on the same del
 and the spread (max - min) of each side; then the one-point fading sweep without and with the NMSE outputs in the same
 alternation (their difference is t5_frame_nmse_kernel + the stored estimates) beside the RX time of the tile.
 
+--fading C3: the Task-4 tile over channel realisations with the NMSE outputs (ber_sweep_task4(fading=, want_nmse=True),
+ofdm_ber_sweep_task4_fading) against the static-channel tile (ber_sweep_task4(h=), the parent's code) on the same delays, both
+with random STO / CFO, 4096 frames, one point, in the same alternation; and the static tile with the NMSE outputs on
+(ofdm_ber_sweep_task4_nmse).
+
     python tools/sweep_rate.py [--mer] [--fading] [M C4 C5 C3]
 """
 from __future__ import annotations
@@ -144,6 +149,33 @@ def measure_fading(name, reps=5):
     return r
 
 
+def measure_c3_fading(reps=5):
+    cfg, F = fr.config_C3(), 4096
+    dev = torch.device("cuda:0")
+    plan = fr.make_plan(cfg, ofdm, precision="fp32", device=0)
+    h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
+    snr = cfg.SNR_dB
+    imp = dict(Time_Delay="random", Freq_Shift="random")
+    nz = np.flatnonzero(h)                                   # the same delay line for both: equal tap count and halo
+    fad = (nz, np.abs(h[nz]) ** 2)
+    static = lambda **kw: plan.ber_sweep_task4([snr], F, h=h, seed=3, device=dev, **imp, **kw)
+    fading = lambda **kw: plan.ber_sweep_task4([snr], F, fading=fad, seed=3, device=dev, **imp, **kw)
+    st, fn = ab_rounds(static, lambda: fading(want_nmse=True), reps)
+    st2, sn = ab_rounds(static, lambda: static(want_nmse=True), reps)
+    rs, rf = static(want_nmse=True), fading(want_nmse=True)
+    r = {"config": "C3", "mode": "fading", "frames": F, "snr_db": snr, "impairments": "random STO / CFO",
+         "n_taps": int(nz.size), "halo": int(nz[-1]), "sweep_static_ms": st, "sweep_fading_nmse_ms": fn,
+         "fading_nmse_over_static": float(np.median(fn) / np.median(st)), "sweep_static_again_ms": st2,
+         "sweep_static_nmse_ms": sn, "static_nmse_over_static": float(np.median(sn) / np.median(st2)),
+         "static": {"ber": int(rs["errors"][0].item()) / (F * plan.frame_bits), "NMSE": float(rs["NMSE"][0].item()),
+                    "status_counts": rs["status_counts"][0].cpu().tolist()},
+         "fading": {"ber": int(rf["errors"][0].item()) / (F * plan.frame_bits), "NMSE": float(rf["NMSE"][0].item()),
+                    "status_counts": rf["status_counts"][0].cpu().tolist()}}
+    plan.close()
+    torch.cuda.empty_cache()
+    return r
+
+
 def measure_c3(reps=5, mer=False):
     cfg, F = fr.config_C3(), 4096
     dev = torch.device("cuda:0")
@@ -209,7 +241,7 @@ def main():
     names = [a for a in args if a not in ("--mer", "--fading")] or (["M", "C5"] if fading else ["M", "C4", "C5"])
     ofdm.init(0)
     if fading:
-        configs = [measure_fading(n) for n in names]
+        configs = [measure_c3_fading() if n == "C3" else measure_fading(n) for n in names]
     else:
         configs = [measure_c3(mer=mer) if n == "C3" else measure(n) for n in names]
     out = {"tool": "sweep_rate", "dtype": "f32", "configs": configs}
