@@ -500,6 +500,24 @@ int ofdm_task5_part2_tile(ofdm_rx_plan* plan, const void* tx_noised, const int32
  * device: the 61-point sweep of the script is one call.  At most 65535 points and 64 channel taps per call. */
 int ofdm_task5_mse_tile(ofdm_rx_plan* plan, const void* tx, const int32_t* tap_delay, const double* tap_amp, int n_ch_taps,
                         const double* snr_db, int64_t n_points, uint64_t seed, uint32_t stream0, double* mse_out, int flags);
+/* The OMP_estimate step of the two tiles above (T5/OMP_estimate.m:7-23, Task5_part2.m:193, Main_model_Task_5.m:331) in batch
+ * form: n pilot LS vectors y[n_pilots x n] (column per realisation, the plan's precision, DEVICE or HOST per flags like every
+ * other array here) against the plan's dictionary -- K consecutive delays of the Nfft-point DFT on the plan's pilot carriers.
+ *   index_out[taps x n] (int32): the picks in pick order, 1-based, 0 = not made (the relative-change stop, :20);
+ *   x_out[taps x n] (complex double): the coefficient of each pick after the last refit; a pick repeated later holds 0 and the
+ *   later one the value (est_fade_chan(index(i)) = x(i), :31-33);  h_out (optional, [n_carrier x n], the plan's precision):
+ *   H = fft(est_fade_chan) on carriers 1..N_carrier (:36).
+ * route: 0 = the library's choice -- omp_batch_kernel (csrc/ofdm_chain_fast.hip:138; 16 realisations per workgroup, c0 and the
+ * Gram table in LDS) for every shape whose state fits 150 KB of LDS, else omp_wide_kernel (csrc/ofdm_omp_wide.hip; one
+ * realisation per workgroup, c0 = S^H Y as a transform of Y scattered onto its carriers, scores in registers, dictionary never
+ * read): Nfft 512, 1024, 2048 or 4096, K <= Nfft, taps <= 32, any pilot set -- all Nfft delays on a random pilot mask
+ * (Task5_part2.m:58-64, :181-184).  1 / 2 force either kernel; a route that cannot serve the shape (omp_batch_kernel beyond its
+ * LDS, the wide kernel at Nfft 8192 or below 512) is OFDM_ERR_ARG, never a fallback.  Both kernels give the same picks and, in
+ * double, coefficients equal to rounding.  ofdm_rx_chain_task5 and the BER sweeps keep omp_batch_kernel alone.
+ * The plan's dense dictionary (n_pilots x K, built by ofdm_rx_plan_create) stays: MP_estimate of the tiles reads it.
+ * At most 65535 realisations per call. */
+int ofdm_OMP_estimate_batch(ofdm_rx_plan* plan, const void* y, int64_t n, int route, int32_t* index_out, void* x_out,
+                            void* h_out, int flags);
 /* Measurement aid: with timing enabled every ofdm_rx_chain_task5 call brackets its launches with HIP
  * events on the launch stream; ms3 = {symbol-1 kernel, OMP kernel, symbols kernel} of the last call
  * (comb pilot layouts run the first two as one launch and report {symbol-1 + OMP kernel, 0, symbols

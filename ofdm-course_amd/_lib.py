@@ -84,6 +84,7 @@ SIGNATURES = {
     "ofdm_rx_chain_task5_ex": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_task5_part2_tile": [_vp, _vp, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _i],
     "ofdm_task5_mse_tile": [_vp, _vp, _vp, _vp, _i, _vp, _i64, C.c_uint64, C.c_uint32, _vp, _i],
+    "ofdm_OMP_estimate_batch": [_vp, _vp, _i64, _i, _vp, _vp, _vp, _i],
     "ofdm_tx_frames_fused": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task5": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i],
     "ofdm_ber_sweep_task5_ex": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i],

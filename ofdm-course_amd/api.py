@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "task5_part2_tile", "task5_mse_tile", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -1171,3 +1171,27 @@ def task5_mse_tile(plan: RxPlan, Tx, channel_taps, SNRs, seed=0, stream0=0):
                                          delay.size, C.c_void_p(snr.ctypes.data), n, int(seed), int(stream0), pms, call.flags),
             "task5_mse_tile")
     return ms.T
+
+
+_OMP_ROUTES = {"auto": 0, "batch": 1, "wide": 2}
+
+
+def OMP_estimate_batch(plan: RxPlan, Y, route="auto", want_h=False):
+    """T5/OMP_estimate.m:7-23 for every column of Y [Np, n] against the plan's dictionary (ofdm_OMP_estimate_batch): the OMP
+    step of task5_part2_tile / task5_mse_tile on its own.  route: "auto" (omp_batch_kernel while its state fits the LDS, else
+    the wide kernel), "batch" or "wide" to force one; a route that cannot serve the shape raises OfdmError.
+    Returns (index [taps, n] int32, 1-based picks in pick order, 0 = not made; x [taps, n] complex128, the picks' coefficients;
+    H [N_carrier, n] in the plan's precision, or None without want_h)."""
+    if route not in _OMP_ROUTES:
+        raise OfdmError(f"OMP_estimate_batch: route must be one of {sorted(_OMP_ROUTES)}")
+    call = _Call(Y, f64=plan.f64)
+    npil, n = _shape2(Y)
+    if npil != plan.n_pilots:
+        raise OfdmError("OMP_estimate_batch: Y needs one row per pilot of the plan")
+    T = plan.taps
+    idx, pidx = call._out((T, n), np.int32, torch.int32 if call.dev else None)
+    x, px = call._out((T, n), np.complex128, torch.complex128 if call.dev else None)
+    H, pH = call.cout((plan.N_carrier, n)) if want_h else (None, None)
+    L.check(call.lib.ofdm_OMP_estimate_batch(plan.handle, call.cin(Y), n, _OMP_ROUTES[route], pidx, px, pH, call.flags),
+            "OMP_estimate_batch")
+    return idx, x, H

@@ -683,6 +683,10 @@ template <typename T>
 int fast_params_prepare(const FastPlanView& pv, const void* tw, int64_t n_frames, FastParams<T>& P);   // ofdm_chain_fast.hip
 template <typename T>
 int omp_batch_run(const FastParams<T>& P, int64_t n_frames);                                            // ofdm_chain_fast.hip
+template <typename T>
+unsigned omp_batch_lds_bytes(const FastParams<T>& P);     // ofdm_chain_fast.hip: the LDS omp_batch_run asks for (it refuses above 150 KB)
+template <typename T>
+int omp_wide_run(const FastParams<T>& P, int nfft, int64_t n_frames);                                   // ofdm_omp_wide.hip
 
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,

@@ -454,7 +454,7 @@ template int fast_params_prepare<double>(const FastPlanView&, const void*, int64
 template <typename T>
 int omp_batch_run(const FastParams<T>& P, int64_t n_frames) {
   hipStream_t st = ctx().stream;
-  const bool by_fft = P.comb_m == 2048 && P.np <= 2048 && P.k_atoms <= 2048 && !getenv("OFDM_OMP_NO_FFT");
+  const bool by_fft = P.comb_m == 2048 && P.np <= 2048 && P.k_atoms <= 2048 && !getenv("OFDM_OMP_NO_FFT");   // (= omp_batch_lds_bytes below)
   const OmpLayout lay = omp_layout<T>(P.np, P.k_atoms, P.taps, by_fft ? fft_lds_elems(2048) : 0);
   OFDM_ARG(lay.total <= 150 * 1024, "rx_chain_task5: OMP stage needs %u bytes of LDS", lay.total);
   const unsigned grid = cdiv_u(n_frames, 4 * lay.fpw);
@@ -593,5 +593,17 @@ int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64
   if (pv.f64) return dispatch_fast<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
   return dispatch_fast<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
 }
+
+// The dynamic LDS omp_batch_run asks for at the shape of P (its omp_layout): above 150 KB it refuses, and the Task-5 part-2 tiles
+// take omp_wide_kernel instead (ofdm_part2.hip, omp_stage_run).  The two lines are those of omp_batch_run (:457-458) and must
+// stay equal to them: the route choice and the refusal agree only then (omp_batch_run keeps its own copy so that its lines,
+// which tests/routes.py cites, do not move).
+template <typename T>
+unsigned omp_batch_lds_bytes(const FastParams<T>& P) {
+  const bool by_fft = P.comb_m == 2048 && P.np <= 2048 && P.k_atoms <= 2048 && !getenv("OFDM_OMP_NO_FFT");
+  return omp_layout<T>(P.np, P.k_atoms, P.taps, by_fft ? fft_lds_elems(2048) : 0).total;
+}
+template unsigned omp_batch_lds_bytes<float>(const FastParams<float>&);
+template unsigned omp_batch_lds_bytes<double>(const FastParams<double>&);
 
 }  // namespace ofdm

@@ -7,13 +7,15 @@
 //   MMSE_CE(h = true CIR, SNR)                     (:176-177)      mmse_wave_kernel: one wavefront per realisation (Levinson),
 //                                                                  then the same spline operator
 //   MP_estimate                                    (:192)          mp_batch_kernel: S^H residue on the matrix cores per iteration
-//   OMP_estimate                                   (:193)          omp_batch_kernel (ofdm_chain_fast.hip)
+//   OMP_estimate                                   (:193)          omp_batch_kernel (ofdm_chain_fast.hip) while its state fits the LDS,
+//                                                                  else omp_wide_kernel (ofdm_omp_wide.hip): omp_stage_run
 //   NMSE of the four estimates                     (:202-205)      p2_nmse_kernel against H = fft(h_jj)
 //   equalize_signal -> get_payload -> demapping -> BER_func, four times (:269-304)   eq_demap_kernel (ofdm_chain_split.hip)
 // Nothing returns to the host but 4 x n NMSE values and 4 x n error counts.
 #include <algorithm>
 
 #include "mmse_levinson.hpp"
+#include "omp_wide_host.hpp"
 #include "rx_plan.hpp"
 #include "spline_op.hpp"
 
@@ -214,6 +216,19 @@ __global__ __launch_bounds__(256) void mp_batch_kernel(FastParams<T> P, MpLayout
   }
 }
 
+// ---- OMP_estimate.m:7-23 of every realisation, P.ypil -> P.tap_idx / P.tap_x.  omp_batch_kernel for every shape it can run (its
+// results do not move); a dictionary whose batch state exceeds the LDS bound -- all Nfft delays on a random pilot mask
+// (Task5_part2.m:181-184), K = 1024 in double (Main_model_Task_5.m) -- goes to omp_wide_kernel, one realisation per workgroup.
+// route: OMP_ROUTE_AUTO for the tiles; ofdm_OMP_estimate_batch can force either kernel, and a forced route that cannot serve
+// the shape is an argument error.
+template <typename T>
+static int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route = OMP_ROUTE_AUTO) {
+  const char* why = nullptr;
+  const int r = omp_route_choose(route, omp_batch_lds_bytes<T>(P), nfft, P.k_atoms, P.taps, &why);
+  OFDM_ARG(r != 0, "OMP_estimate: %s", why);
+  return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, F);
+}
+
 // ---- (H_f - H_est)(H_f - H_est)' / N_carrier for the four estimates (:202-205); H_f = fft(h_jj)(1..N_carrier) from the taps
 template <typename T>
 __global__ __launch_bounds__(256) void p2_nmse_kernel(const int32_t* __restrict__ delay, const c64* __restrict__ amp, int n_taps,
@@ -341,7 +356,7 @@ static int part2_tile_run(ofdm_rx_plan* pl, const void* dtx, const int32_t* ddel
     OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, dref, derrs + 2 * F, dh[2], nullptr, nullptr, 0, 0));
   }
   // OMP
-  OFDM_TRY(omp_batch_run<T>(P, F));
+  OFDM_TRY(omp_stage_run<T>(P, N, F));
   OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, dref, derrs + 3 * F, dh[3], nullptr, nullptr, 0, 0));
   // LS, MMSE: equalise with the given H
   P.h_in = dh[0];
@@ -526,7 +541,7 @@ static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, 
     OFDM_TRY(check_launch("MP stage"));
   }
   // OMP_estimate (:331)
-  OFDM_TRY(omp_batch_run<T>(P, F));
+  OFDM_TRY(omp_stage_run<T>(P, N, F));
   hipLaunchKernelGGL(mse_taps_to_h_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, (const int32_t*)P.tap_idx, (const c64*)P.tap_x, taps, N, nc,
                      dh[3]);
   // the four errors against fft(h)(1..N_carrier) (:334-344)
@@ -586,6 +601,57 @@ extern "C" int ofdm_task5_part2_tile(ofdm_rx_plan* pl, const void* tx_noised, co
                                                 inv_snr, dref, (double*)dnm, (uint32_t*)der));
   else OFDM_TRY(part2_tile_run<float>(pl, dtx, (const int32_t*)ddel, (const c64*)damp, n_ch_taps, n_frames, (const double*)dcv, inv_snr,
                                       dref, (double*)dnm, (uint32_t*)der));
+  return st.finish();
+}
+
+__global__ void omp_index_out_kernel(const int32_t* __restrict__ tap_idx, int32_t* __restrict__ index_out, int64_t count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) index_out[i] = tap_idx[i] + 1;                    // 1-based, 0 = unused
+}
+
+template <typename T>
+static int omp_estimate_batch_run(ofdm_rx_plan* pl, const void* dy, int64_t n, int route, int32_t* didx, c64* dx, void* dh) {
+  hipStream_t st = ctx().stream;
+  FastPlanView pv;
+  make_plan_view(pl, pv);
+  pv.ev = nullptr;
+  pv.d_wt = nullptr;
+  pv.mmse_ls = 0;
+  FastParams<T> P;
+  const void* tw = nullptr;
+  OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
+  OFDM_TRY(fast_params_prepare<T>(pv, tw, n, P));
+  OFDM_HIP(hipMemcpyAsync(P.ypil, dy, sizeof(cx<T>) * (size_t)pl->np * n, hipMemcpyDeviceToDevice, st));
+  OFDM_TRY(omp_stage_run<T>(P, pl->nfft, n, route));
+  const int64_t count = (int64_t)pl->taps * n;
+  hipLaunchKernelGGL(omp_index_out_kernel, dim3(cdiv_u(count, 256)), dim3(256), 0, st, (const int32_t*)P.tap_idx, didx, count);
+  OFDM_HIP(hipMemcpyAsync(dx, P.tap_x, sizeof(c64) * (size_t)count, hipMemcpyDeviceToDevice, st));
+  if (dh)
+    hipLaunchKernelGGL(mse_taps_to_h_kernel<T>, dim3((unsigned)n), dim3(256), 0, st, (const int32_t*)P.tap_idx, (const c64*)P.tap_x,
+                       pl->taps, pl->nfft, pl->n_carrier, (cx<T>*)dh);
+  return check_launch("OMP_estimate_batch");
+}
+
+extern "C" int ofdm_OMP_estimate_batch(ofdm_rx_plan* pl, const void* y, int64_t n, int route, int32_t* index_out, void* x_out,
+                                       void* h_out, int flags) {
+  OFDM_TRY(ensure_init());
+  OFDM_ARG(pl && y && index_out && x_out, "OMP_estimate_batch: null argument");
+  OFDM_PLAN_DEVICE(pl);
+  OFDM_ARG((is_f64(flags) ? 1 : 0) == pl->f64, "OMP_estimate_batch: precision flag differs from the plan's");
+  OFDM_ARG(n >= 0 && n <= 65535, "OMP_estimate_batch: at most 65535 realisations");
+  OFDM_ARG(route == OMP_ROUTE_AUTO || route == OMP_ROUTE_BATCH || route == OMP_ROUTE_WIDE,
+           "OMP_estimate_batch: route must be 0 (library's choice), 1 (omp_batch_kernel) or 2 (wide)");
+  if (n == 0) return OFDM_OK;
+  const size_t cs = csize(flags);
+  Stage st(flags);
+  const void* dy;
+  void *didx, *dx, *dh = nullptr;
+  OFDM_TRY(st.in(y, cs * (size_t)pl->np * n, &dy));
+  OFDM_TRY(st.out(index_out, sizeof(int32_t) * (size_t)pl->taps * n, &didx));
+  OFDM_TRY(st.out(x_out, sizeof(c64) * (size_t)pl->taps * n, &dx));
+  if (h_out) OFDM_TRY(st.out(h_out, cs * (size_t)pl->n_carrier * n, &dh));
+  if (pl->f64) OFDM_TRY(omp_estimate_batch_run<double>(pl, dy, n, route, (int32_t*)didx, (c64*)dx, dh));
+  else OFDM_TRY(omp_estimate_batch_run<float>(pl, dy, n, route, (int32_t*)didx, (c64*)dx, dh));
   return st.finish();
 }
 

@@ -39,6 +39,114 @@ __device__ __forceinline__ double wave_sum(double v, int) {
 
 __host__ __device__ constexpr int omp_wave_rs(int taps) { return taps | 1; }          // odd row stride of R
 
+// ---- the refit of one pick, shared by omp_frame_wave below and omp_wide_kernel (ofdm_omp_wide.hip): the state of a pursuit
+// in the lanes of ONE wavefront (lane q: pick q, x_q, z_q) and R = L^-1 in LDS.
+template <typename T>
+struct OmpWaveState {
+  int pk = -1;                                   // lane q: pick q (0-based atom), x_q, z_q
+  cx<T> xq, zq;
+  int n = 0;
+  double rho;
+  bool active;                                   // wave-uniform
+};
+
+template <typename T>
+__device__ __forceinline__ void omp_wave_begin(OmpWaveState<T>& s, cx<T>* __restrict__ Rm, int taps, bool live, double ynorm) {
+  const int lane = threadIdx.x & 63;
+  const int RS = omp_wave_rs(taps);
+  s.pk = -1;
+  s.xq = mk<T>(0, 0); s.zq = mk<T>(0, 0);
+  s.n = 0;
+  s.rho = ynorm;
+  s.active = live;
+  if constexpr (sizeof(T) == 4) {
+    for (int i = lane; i < taps * RS; i += 64) Rm[i] = mk<T>(0, 0);
+    wave_sync();
+  }
+}
+
+// Pick kp (wave-uniform) enters the pursuit.  gram(d) = a_k^H a_{k+d} for d in (-K, K); bn() = a_kp^H y = c0[kp]; g0 = gram(0).x;
+// ns = s.n in a scalar register.  Returns false on a repeated pick (the equal split, then `break`, OMP_estimate.m:14-23 with
+// pinv); the stop rule clears s.active.
+template <typename T, typename Gram, typename Bn>
+__device__ __forceinline__ bool omp_wave_refit(OmpWaveState<T>& s, int it, int ns, int kp, Gram gram, Bn bn_of, T g0,
+                                               cx<T>* __restrict__ Rm, int taps) {
+  const int lane = threadIdx.x & 63;
+  const int RS = omp_wave_rs(taps);
+  int& pk = s.pk; int& n = s.n;
+  cx<T>& xq = s.xq; cx<T>& zq = s.zq;
+  // ---- a repeated pick: pinv with a repeated column splits the coefficient equally; residual unchanged -> break
+  const unsigned long long dupm = __ballot(lane < n && pk == kp);
+  if (dupm) {
+    const int dup = __builtin_ctzll(dupm);
+    if (lane == dup) xq = xq * (T)0.5;
+    const cx<T> half = lane_bcast(xq, dup);
+    if (lane == n) { xq = half; pk = kp; }
+    n += 1;
+    return false;
+  }
+  // ---- new Cholesky row through R = L^-1:  l_j = sum_{k<=j} G(n,k) conj(R(j,k)),  G(n,k) = a_n^H a_k = gram(idx_k - idx_n)
+  cx<T> g = mk<T>(0, 0);
+  if (lane < n) g = gram(pk - kp);
+  cx<T> l = mk<T>(0, 0);
+  // fp32: R's upper triangle holds zeros (cleared per frame, omp_wave_begin), so the sums run unconditionally over k < n; lanes
+  // past the picks read a clamped row / column and their results are never used
+  const int lc = lane < taps ? lane : taps - 1;
+  const cx<T>* Rrow = Rm + (sizeof(T) == 4 ? lc : lane) * RS;
+  for (int k = 0; k < ns; ++k) {
+    const cx<T> gq = lane_bcast(g, k);
+    if constexpr (sizeof(T) == 4) cmaddc(l, gq, Rrow[k]);
+    else if (k <= lane && lane < n) l = l + mulc(gq, Rrow[k]);
+  }
+  const T nrm = wave_sum(lane < n ? norm2(l) : T(0), lane);
+  const cx<T> lzp = l * zq;                    // zq = 0 in lanes >= n
+  const cx<T> lz = mk<T>(wave_sum(lane < n ? lzp.x : T(0), lane), wave_sum(lane < n ? lzp.y : T(0), lane));
+  const T inv = T(1) / sqrt(g0 - nrm);
+  const cx<T> bn = bn_of();                    // b_n = a_n^H y = c0[kp]
+  const cx<T> zn = (bn - lz) * inv;
+  // ---- R(n, j) = -(1/lambda) sum_{k>=j} l_k R(k, j);  x_j += conj(R(n, j)) z_n (j < n);  x_n = z_n / lambda
+  cx<T> r = mk<T>(0, 0);
+  for (int k = 0; k < ns; ++k) {
+    const cx<T> lq = lane_bcast(l, k);
+    if constexpr (sizeof(T) == 4) cmadd(r, lq, Rm[k * RS + lc]);
+    else if (k >= lane && lane < n) r = r + lq * Rm[k * RS + lane];
+  }
+  r = r * (-inv);
+  if (lane < n) {
+    Rm[n * RS + lane] = r;
+    xq = xq + conj(r) * zn;
+  }
+  if (lane == n) {
+    Rm[n * RS + n] = mk<T>(inv, 0);
+    xq = zn * inv;
+    zq = zn;
+    pk = kp;
+  }
+  // ||r_n||^2 = ||r_{n-1}||^2 - |z_n|^2 ; stop when ||r_n - r_{n-1}|| / ||r_{n-1}|| < 1e-2 (:20), compared squared
+  const double num = (double)zn.x * zn.x + (double)zn.y * zn.y;
+  if (it >= 1 && (!(num > 0.0) || num < 1e-4 * s.rho)) s.active = false;
+  s.rho -= num;
+  n += 1;
+  wave_sync();                                 // row n of R is read by other lanes in the next iteration
+  return true;
+}
+
+// est_fade_chan(index(i1)) = x(i1): a later duplicate overwrites an earlier one (:31-33)
+template <typename T>
+__device__ __forceinline__ void omp_wave_store(const FastParams<T>& P, const OmpWaveState<T>& s, int taps, int64_t f) {
+  const int lane = threadIdx.x & 63;
+  bool later = false;
+  for (int q = 1; q < s.n; ++q) {
+    const int pq = __builtin_amdgcn_readlane(s.pk, q);
+    if (lane < q && s.pk == pq) later = true;
+  }
+  if (lane < taps) {
+    const bool have = lane < s.n;
+    P.tap_idx[f * taps + lane] = have ? s.pk : -1;
+    P.tap_x[f * taps + lane] = (have && !later) ? c64{(double)s.xq.x, (double)s.xq.y} : c64{0, 0};
+  }
+}
+
 // cf = c0 of the frame [K], g2 = two-sided Gram table [KP + K] (index d + KP, KP = K rounded up to 512), Rm = this wavefront's R [taps][omp_wave_rs(taps)]
 // C0REG: c0 of the frame sits in registers (c0r[u] = c0[lane + 64 u], K <= 512; cf is not read) -- the LDS it came from is
 // then free for the R states (omp_layout, reg_c0)
@@ -47,20 +155,12 @@ __device__ __forceinline__ void omp_frame_wave(const FastParams<T>& P, const cx<
                                                const cx<T>* __restrict__ g2, cx<T>* __restrict__ Rm, int K, int taps,
                                                bool live, double ynorm, int64_t f) {
   const int lane = threadIdx.x & 63;
-  const int RS = omp_wave_rs(taps);
   const int KP = (K + 511) & ~511;               // the table's zero shift sits at KP
   const T g0 = g2[KP].x;
-  int pk = -1;                                   // lane q: pick q (0-based atom), x_q, z_q
-  cx<T> xq = mk<T>(0, 0), zq = mk<T>(0, 0);
-  int n = 0;
-  double rho = ynorm;
-  bool active = live;                            // wave-uniform
-  if constexpr (sizeof(T) == 4) {
-    for (int i = lane; i < taps * RS; i += 64) Rm[i] = mk<T>(0, 0);
-    wave_sync();
-  }
-  for (int it = 0; it < taps && active; ++it) {
-    const int ns = __builtin_amdgcn_readfirstlane(n);        // picks made so far, in a scalar register: uniform loops
+  OmpWaveState<T> s;
+  omp_wave_begin<T>(s, Rm, taps, live, ynorm);
+  for (int it = 0; it < taps && s.active; ++it) {
+    const int ns = __builtin_amdgcn_readfirstlane(s.n);      // picks made so far, in a scalar register: uniform loops
     // ---- residual correlation c = c0 - G(:, index) x and its first arg-max (OMP_estimate.m:7,:14)
     float bs = -1.0f;
     int bi = 0x7fffffff;
@@ -77,13 +177,13 @@ __device__ __forceinline__ void omp_frame_wave(const FastParams<T>& P, const cx<
       const cx<T>* gk = g2 + KP - kb - 448;
       if (ns > 0) {
         cx<T> ga[8], gb[8];
-        int pq = __builtin_amdgcn_readlane(pk, 0);
+        int pq = __builtin_amdgcn_readlane(s.pk, 0);
 #pragma unroll
         for (int u = 0; u < 8; ++u) ga[u] = gk[pq + 64 * (7 - u)];
         for (int q = 0; q < ns; q += 2) {        // two picks per trip: the second pick's Gram values are in flight
-          const cx<T> xa = lane_bcast(xq, q);
+          const cx<T> xa = lane_bcast(s.xq, q);
           const bool two = q + 1 < ns;
-          const int pn = __builtin_amdgcn_readlane(pk, two ? q + 1 : q);
+          const int pn = __builtin_amdgcn_readlane(s.pk, two ? q + 1 : q);
 #pragma unroll
           for (int u = 0; u < 8; ++u) gb[u] = gk[pn + 64 * (7 - u)];
 #pragma unroll
@@ -91,8 +191,8 @@ __device__ __forceinline__ void omp_frame_wave(const FastParams<T>& P, const cx<
             if constexpr (sizeof(T) == 4) cmsub(c[u], ga[u], xa); else c[u] = c[u] - ga[u] * xa;
           }
           if (two) {
-            const cx<T> xb = lane_bcast(xq, q + 1);
-            const int p2 = __builtin_amdgcn_readlane(pk, q + 2 < ns ? q + 2 : q + 1);
+            const cx<T> xb = lane_bcast(s.xq, q + 1);
+            const int p2 = __builtin_amdgcn_readlane(s.pk, q + 2 < ns ? q + 2 : q + 1);
 #pragma unroll
             for (int u = 0; u < 8; ++u) ga[u] = gk[p2 + 64 * (7 - u)];
 #pragma unroll
@@ -116,81 +216,20 @@ __device__ __forceinline__ void omp_frame_wave(const FastParams<T>& P, const cx<
     const float gmax = group_max_f(bs, 64, lane);
     bi = group_min_i(bs == gmax ? bi : 0x7fffffff, 64, lane);
     const int kp = bi < K ? bi : 0;              // all-NaN scores: MATLAB max returns index 1
-    // ---- a repeated pick: pinv with a repeated column splits the coefficient equally; residual unchanged -> break
-    const unsigned long long dupm = __ballot(lane < n && pk == kp);
-    if (dupm) {
-      const int dup = __builtin_ctzll(dupm);
-      if (lane == dup) xq = xq * (T)0.5;
-      const cx<T> half = lane_bcast(xq, dup);
-      if (lane == n) { xq = half; pk = kp; }
-      n += 1;
-      break;
-    }
-    // ---- new Cholesky row through R = L^-1:  l_j = sum_{k<=j} G(n,k) conj(R(j,k)),  G(n,k) = a_n^H a_k = g2[K + idx_k - idx_n]
-    cx<T> g = mk<T>(0, 0);
-    if (lane < n) g = g2[KP + pk - kp];
-    cx<T> l = mk<T>(0, 0);
-    // fp32: R's upper triangle holds zeros (cleared per frame below), so the sums run unconditionally over k < n; lanes
-    // past the picks read a clamped row / column and their results are never used
-    const int lc = lane < taps ? lane : taps - 1;
-    const cx<T>* Rrow = Rm + (sizeof(T) == 4 ? lc : lane) * RS;
-    for (int k = 0; k < ns; ++k) {
-      const cx<T> gq = lane_bcast(g, k);
-      if constexpr (sizeof(T) == 4) cmaddc(l, gq, Rrow[k]);
-      else if (k <= lane && lane < n) l = l + mulc(gq, Rrow[k]);
-    }
-    const T nrm = wave_sum(lane < n ? norm2(l) : T(0), lane);
-    const cx<T> lzp = l * zq;                    // zq = 0 in lanes >= n
-    const cx<T> lz = mk<T>(wave_sum(lane < n ? lzp.x : T(0), lane), wave_sum(lane < n ? lzp.y : T(0), lane));
-    const T inv = T(1) / sqrt(g0 - nrm);
-    cx<T> bn;                                    // b_n = a_n^H y = c0[kp]
-    if constexpr (C0REG) {
-      cx<T> pick = c0r[0];
+    const auto gram = [&](int d) { return g2[KP + d]; };
+    const auto bn_of = [&]() {
+      if constexpr (C0REG) {
+        cx<T> pick = c0r[0];
 #pragma unroll
-      for (int u = 1; u < 8; ++u) pick = (kp >> 6) == u ? c0r[u] : pick;       // kp is wave-uniform
-      bn = lane_bcast(pick, kp & 63);
-    } else {
-      bn = cf[kp];
-    }
-    const cx<T> zn = (bn - lz) * inv;
-    // ---- R(n, j) = -(1/lambda) sum_{k>=j} l_k R(k, j);  x_j += conj(R(n, j)) z_n (j < n);  x_n = z_n / lambda
-    cx<T> r = mk<T>(0, 0);
-    for (int k = 0; k < ns; ++k) {
-      const cx<T> lq = lane_bcast(l, k);
-      if constexpr (sizeof(T) == 4) cmadd(r, lq, Rm[k * RS + lc]);
-      else if (k >= lane && lane < n) r = r + lq * Rm[k * RS + lane];
-    }
-    r = r * (-inv);
-    if (lane < n) {
-      Rm[n * RS + lane] = r;
-      xq = xq + conj(r) * zn;
-    }
-    if (lane == n) {
-      Rm[n * RS + n] = mk<T>(inv, 0);
-      xq = zn * inv;
-      zq = zn;
-      pk = kp;
-    }
-    // ||r_n||^2 = ||r_{n-1}||^2 - |z_n|^2 ; stop when ||r_n - r_{n-1}|| / ||r_{n-1}|| < 1e-2 (:20), compared squared
-    const double num = (double)zn.x * zn.x + (double)zn.y * zn.y;
-    if (it >= 1 && (!(num > 0.0) || num < 1e-4 * rho)) active = false;
-    rho -= num;
-    n += 1;
-    wave_sync();                                 // row n of R is read by other lanes in the next iteration
+        for (int u = 1; u < 8; ++u) pick = (kp >> 6) == u ? c0r[u] : pick;       // kp is wave-uniform
+        return lane_bcast(pick, kp & 63);
+      } else {
+        return cf[kp];
+      }
+    };
+    if (!omp_wave_refit<T>(s, it, ns, kp, gram, bn_of, g0, Rm, taps)) break;
   }
-  // est_fade_chan(index(i1)) = x(i1): a later duplicate overwrites an earlier one (:31-33)
-  if (live) {
-    bool later = false;
-    for (int q = 1; q < n; ++q) {
-      const int pq = __builtin_amdgcn_readlane(pk, q);
-      if (lane < q && pk == pq) later = true;
-    }
-    if (lane < taps) {
-      const bool have = lane < n;
-      P.tap_idx[f * taps + lane] = have ? pk : -1;
-      P.tap_x[f * taps + lane] = (have && !later) ? c64{(double)xq.x, (double)xq.y} : c64{0, 0};
-    }
-  }
+  if (live) omp_wave_store<T>(P, s, taps, f);
 }
 
 }  // namespace ofdm
