@@ -513,11 +513,27 @@ int ofdm_task5_mse_tile(ofdm_rx_plan* plan, const void* tx, const int32_t* tap_d
  * read): Nfft 512, 1024, 2048 or 4096, K <= Nfft, taps <= 32, any pilot set -- all Nfft delays on a random pilot mask
  * (Task5_part2.m:58-64, :181-184).  1 / 2 force either kernel; a route that cannot serve the shape (omp_batch_kernel beyond its
  * LDS, the wide kernel at Nfft 8192 or below 512) is OFDM_ERR_ARG, never a fallback.  Both kernels give the same picks and, in
- * double, coefficients equal to rounding.  ofdm_rx_chain_task5 and the BER sweeps keep omp_batch_kernel alone.
+ * double, coefficients equal to rounding.  ofdm_rx_chain_task5 and the BER sweeps take the route of their plan
+ * (ofdm_rx_plan_set_omp_route): omp_batch_kernel unless the plan says otherwise.
  * The plan's dense dictionary (n_pilots x K, built by ofdm_rx_plan_create) stays: MP_estimate of the tiles reads it.
  * At most 65535 realisations per call. */
 int ofdm_OMP_estimate_batch(ofdm_rx_plan* plan, const void* y, int64_t n, int route, int32_t* index_out, void* x_out,
                             void* h_out, int flags);
+/* The OMP stage of ofdm_rx_chain_task5(_ex), ofdm_ber_sweep_task5(_ex) and ofdm_ber_sweep_task5_fading on this plan; route is the
+ * OMP_ROUTE_* of ofdm_OMP_estimate_batch (0 auto, 1 batch, 2 wide).  A new plan is in 1 (batch): omp_batch_kernel, or the fused
+ * symbol-1 + OMP launch where the plan takes it, and its refusal of a state beyond 150 KB of LDS ("OMP stage needs ...").
+ *   0 (auto): exactly that route, bit for bit, wherever omp_batch_kernel's state fits; else the three-launch receiver with
+ *             omp_wide_kernel in the middle -- K = Nfft on a random pilot mask at Nfft 4096, at Nfft 2048 in double
+ *             (Task5_part2.m:58-64, :181-184).
+ *   2 (wide): always rx_pilot_kernel (or the split form's pilot stage) -> omp_wide_kernel -> the plan's symbol stage, also on a
+ *             plan that would take the fused launch.
+ * A shape the chosen kernel cannot serve (the wide kernel at Nfft 8192 or below 512; 2 on a plan of the generic single-kernel
+ * entry, which runs its own pursuit: Nfft < 512, a pilot outside 1..N_carrier) makes the receiver call OFDM_ERR_ARG with the
+ * reason, before anything is launched; it is never a fallback.  The MMSE modes have no OMP stage and ignore the route.
+ * ofdm_rx_plan_get_omp_route: *route_out = the setting, *last_out = the kernel the stage ran in the last receiver call (1 batch --
+ * the fused launch included --, 2 wide, 0 none: MMSE mode or the generic entry); either pointer may be NULL. */
+int ofdm_rx_plan_set_omp_route(ofdm_rx_plan* plan, int route);
+int ofdm_rx_plan_get_omp_route(const ofdm_rx_plan* plan, int* route_out, int* last_out);
 /* Measurement aid: with timing enabled every ofdm_rx_chain_task5 call brackets its launches with HIP
  * events on the launch stream; ms3 = {symbol-1 kernel, OMP kernel, symbols kernel} of the last call
  * (comb pilot layouts run the first two as one launch and report {symbol-1 + OMP kernel, 0, symbols

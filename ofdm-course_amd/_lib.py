@@ -71,6 +71,8 @@ SIGNATURES = {
     "ofdm_rx_plan_destroy": [_vp],
     "ofdm_rx_plan_set_mmse": [_vp, _vp, _i64, _d, _i],
     "ofdm_rx_plan_set_mmse_ls": [_vp, _i, _d],
+    "ofdm_rx_plan_set_omp_route": [_vp, _i],
+    "ofdm_rx_plan_get_omp_route": [_vp, _pi, _pi],
     "ofdm_rx_chain_task4": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_rx_chain_task4_ex": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i],
     "ofdm_tx_frames": [_vp, _vp, _i, _d, _i, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _i],

@@ -696,6 +696,32 @@ class RxPlan:
         L.check(self.lib.ofdm_rx_plan_set_mmse_ls(self.handle, 0 if SNR is None else 1, 0.0 if SNR is None else float(SNR)),
                 "rx_plan_set_mmse_ls")
 
+    def set_omp_route(self, route):
+        """The OMP stage of rx_chain_task5 and ber_sweep on this plan (ofdm_rx_plan_set_omp_route), in the words of
+        OMP_estimate_batch(route=): "batch" (a new plan: omp_batch_kernel or the fused symbol-1 + OMP launch, as ever), "auto"
+        (the same wherever omp_batch_kernel's state fits the LDS, else omp_wide_kernel: K = Nfft on a random pilot mask,
+        T5/Task5_part2.m:58-64,:181-184) or "wide" (always rx_pilot_kernel -> omp_wide_kernel -> the symbol stage).  A shape
+        the chosen kernel cannot serve makes the receiver call raise OfdmError; the MMSE modes ignore the route."""
+        if route not in _OMP_ROUTES:
+            raise OfdmError(f"set_omp_route: route must be one of {sorted(_OMP_ROUTES)}")
+        L.check(self.lib.ofdm_rx_plan_set_omp_route(self.handle, _OMP_ROUTES[route]), "rx_plan_set_omp_route")
+
+    def _omp_route_get(self):
+        r, last = C.c_int(0), C.c_int(0)
+        L.check(self.lib.ofdm_rx_plan_get_omp_route(self.handle, C.byref(r), C.byref(last)), "rx_plan_get_omp_route")
+        return r.value, last.value
+
+    @property
+    def omp_route(self):
+        """The route set_omp_route left the plan in: "auto", "batch" or "wide"."""
+        return _OMP_ROUTE_NAMES[self._omp_route_get()[0]]
+
+    @property
+    def last_omp_route(self):
+        """The kernel the OMP stage of the last rx_chain_task5 / ber_sweep call ran: "batch" (the fused launch included), "wide",
+        or None (MMSE mode, the generic entry, no call yet)."""
+        return {1: "batch", 2: "wide"}.get(self._omp_route_get()[1])
+
     def set_descrambler(self, Register=None):
         """Per-frame DeScrambler(Register, .) inside rx_chain_task5 / rx_chain_task4 (T5/Main_model_Task_5.m:257-274): the
         demapped bits of every frame are descrambled in the pack stage before they are written / compared.  None = off."""
@@ -1174,6 +1200,7 @@ def task5_mse_tile(plan: RxPlan, Tx, channel_taps, SNRs, seed=0, stream0=0):
 
 
 _OMP_ROUTES = {"auto": 0, "batch": 1, "wide": 2}
+_OMP_ROUTE_NAMES = {v: k for k, v in _OMP_ROUTES.items()}
 
 
 def OMP_estimate_batch(plan: RxPlan, Y, route="auto", want_h=False):

@@ -9,6 +9,7 @@
 
 #include "demap_core.hpp"
 #include "fft_core.hpp"
+#include "omp_wide_host.hpp"
 
 namespace ofdm {
 
@@ -676,6 +677,8 @@ struct FastPlanView {
   int ls_bw = 0, ls_span = 0;
   void** ws_lsv = nullptr;                    // [n_frames][np] MMSE estimate at the pilots
   size_t* ws_lsv_bytes = nullptr;
+  int omp_route = OMP_ROUTE_BATCH;            // OMP stage of the receiver: OMP_ROUTE_* (ofdm_rx_plan_set_omp_route); ignored in the MMSE modes
+  int* omp_out = nullptr;                     // set to the kernel the OMP stage ran: OMP_ROUTE_BATCH (the fused launch included) or OMP_ROUTE_WIDE
   bool mmse() const { return d_wt != nullptr || mmse_ls != 0; }   // the symbol stages take H from ws_h
 };
 
@@ -687,6 +690,35 @@ template <typename T>
 unsigned omp_batch_lds_bytes(const FastParams<T>& P);     // ofdm_chain_fast.hip: the LDS omp_batch_run asks for (it refuses above 150 KB)
 template <typename T>
 int omp_wide_run(const FastParams<T>& P, int nfft, int64_t n_frames);                                   // ofdm_omp_wide.hip
+
+// ---- OMP_estimate.m:7-23 of every realisation, P.ypil -> P.tap_idx / P.tap_x.  omp_batch_kernel for every shape it can run (its
+// results do not move); a dictionary whose batch state exceeds the LDS bound -- all Nfft delays on a random pilot mask
+// (Task5_part2.m:181-184), K = 1024 in double (Main_model_Task_5.m) -- goes to omp_wide_kernel, one realisation per workgroup.
+// route: OMP_ROUTE_AUTO for the tiles; ofdm_OMP_estimate_batch and a plan (ofdm_rx_plan_set_omp_route) can force either kernel,
+// and a forced route that cannot serve the shape is an argument error.  taken: the kernel that ran.
+template <typename T>
+inline int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route = OMP_ROUTE_AUTO, int* taken = nullptr) {
+  const char* why = nullptr;
+  const int r = omp_route_choose(route, omp_batch_lds_bytes<T>(P), nfft, P.k_atoms, P.taps, &why);
+  OFDM_ARG(r != 0, "OMP_estimate: %s", why);
+  if (taken) *taken = r;
+  return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, F);
+}
+
+// The OMP stage of the Task-5 receiver (ofdm_chain_fast.hip, ofdm_chain_split.hip) under the plan's route.  A plan left in
+// OMP_ROUTE_BATCH makes the call it always made, refusal and wording included (rx_chain_task5: OMP stage needs ...).
+template <typename T>
+inline int omp_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_t n_frames) {
+  if (pv.omp_route == OMP_ROUTE_BATCH) {
+    if (pv.omp_out) *pv.omp_out = OMP_ROUTE_BATCH;
+    return omp_batch_run<T>(P, n_frames);
+  }
+  return omp_stage_run<T>(P, pv.nfft, n_frames, pv.omp_route, pv.omp_out);
+}
+
+// Before the first launch of a receiver call on a plan in OMP_ROUTE_AUTO / OMP_ROUTE_WIDE: a shape the chosen kernel cannot serve
+// is refused here, so that no front end runs for it.  (OMP_ROUTE_BATCH keeps its refusal where it was, inside the stage.)
+int omp_route_check(const FastPlanView& pv);                                                            // ofdm_omp_route.hip
 
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,

@@ -720,7 +720,7 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   if (fast || split) {
     FastPlanView pv;
     make_plan_view(pl, pv, ls_inv_snr);
-    pl->last_fast = 1;
+    pl->last_fast = 1; OFDM_TRY(omp_route_check(pv));
     descr_pass = (pl->descr & DESCR_ON) && (mer || !(fast && chain_wave_supported(pv)));
     if (descr_pass) {
       OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
@@ -738,7 +738,7 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
   OFDM_ARG(!pl->d_wt && !pl->mmse_ls, "rx_chain_task5: the MMSE mode of a plan needs pilots inside 1..N_carrier, at most 32 taps and a frame "
                       "whose decisions fit the workgroup's LDS (ofdm_MMSE_CE covers every other case)");
-  pl->last_fast = 0;
+  pl->last_fast = 0; OFDM_TRY(omp_route_check_generic(pl));
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[0], ctx().stream));
   {
     void* cb = descr_pass ? craw : dbits;

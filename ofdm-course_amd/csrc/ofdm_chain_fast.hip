@@ -489,7 +489,7 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
   const int ncu = ctx().num_cu;
   hipStream_t st = ctx().stream;
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[0], st));
-  const bool fused = !mmse && pv.comb_lg_up >= 0 && pv.taps <= OMP_RT && pv.k_atoms <= 512 && !getenv("OFDM_FAST_UNFUSED");
+  const bool fused = !mmse && pv.comb_lg_up >= 0 && pv.taps <= OMP_RT && pv.k_atoms <= 512 && pv.omp_route != OMP_ROUTE_WIDE && !getenv("OFDM_FAST_UNFUSED");
   if (pv.fused_out) *pv.fused_out = fused ? 1 : 0;
   if (fused) {
     // kernels 1+2 in one launch (comb pilots): c0 by a wave-local inverse transform (ofdm_chain_pilot.hip)
@@ -507,7 +507,7 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
     if (mmse) {
       OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
     } else {
-      OFDM_TRY(omp_batch_run<T>(P, n_frames));
+      OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
     }
   }
   if (pv.ev && !fused) OFDM_HIP(hipEventRecord(pv.ev[2], st));
@@ -595,7 +595,7 @@ int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64
 }
 
 // The dynamic LDS omp_batch_run asks for at the shape of P (its omp_layout): above 150 KB it refuses, and the Task-5 part-2 tiles
-// take omp_wide_kernel instead (ofdm_part2.hip, omp_stage_run).  The two lines are those of omp_batch_run (:457-458) and must
+// take omp_wide_kernel instead (omp_stage_run, chain_fast_core.hpp).  The two lines are those of omp_batch_run (:457-458) and must
 // stay equal to them: the route choice and the refusal agree only then (omp_batch_run keeps its own copy so that its lines,
 // which tests/routes.py cites, do not move).
 template <typename T>

@@ -708,7 +708,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
                                      (int64_t)(8192 + pv.t_guard) * pv.n_symb));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[1], st));
       if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
-      else OFDM_TRY(omp_batch_run<T>(P, n_frames));
+      else OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
       if (r2) OFDM_TRY(chain_r2_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
       else OFDM_TRY(chain_coop_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
@@ -747,7 +747,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   }
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[1], st));
   if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
-  else OFDM_TRY(omp_batch_run<T>(P, n_frames));
+  else OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
   OFDM_TRY(eq_demap_run<T>(pv, P, xk, pv.n_carrier, mmse, n_frames, bits, ref, errs, h_out, idx_out, nullptr, 0, 0, 0,
                            mer));                                      // (+ the MER_func sums of the whole RX_IQ: skip 0)

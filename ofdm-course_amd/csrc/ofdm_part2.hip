@@ -8,7 +8,7 @@
 //                                                                  then the same spline operator
 //   MP_estimate                                    (:192)          mp_batch_kernel: S^H residue on the matrix cores per iteration
 //   OMP_estimate                                   (:193)          omp_batch_kernel (ofdm_chain_fast.hip) while its state fits the LDS,
-//                                                                  else omp_wide_kernel (ofdm_omp_wide.hip): omp_stage_run
+//                                                                  else omp_wide_kernel (ofdm_omp_wide.hip): omp_stage_run (chain_fast_core.hpp)
 //   NMSE of the four estimates                     (:202-205)      p2_nmse_kernel against H = fft(h_jj)
 //   equalize_signal -> get_payload -> demapping -> BER_func, four times (:269-304)   eq_demap_kernel (ofdm_chain_split.hip)
 // Nothing returns to the host but 4 x n NMSE values and 4 x n error counts.
@@ -214,19 +214,6 @@ __global__ __launch_bounds__(256) void mp_batch_kernel(FastParams<T> P, MpLayout
     }
     __syncthreads();
   }
-}
-
-// ---- OMP_estimate.m:7-23 of every realisation, P.ypil -> P.tap_idx / P.tap_x.  omp_batch_kernel for every shape it can run (its
-// results do not move); a dictionary whose batch state exceeds the LDS bound -- all Nfft delays on a random pilot mask
-// (Task5_part2.m:181-184), K = 1024 in double (Main_model_Task_5.m) -- goes to omp_wide_kernel, one realisation per workgroup.
-// route: OMP_ROUTE_AUTO for the tiles; ofdm_OMP_estimate_batch can force either kernel, and a forced route that cannot serve
-// the shape is an argument error.
-template <typename T>
-static int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route = OMP_ROUTE_AUTO) {
-  const char* why = nullptr;
-  const int r = omp_route_choose(route, omp_batch_lds_bytes<T>(P), nfft, P.k_atoms, P.taps, &why);
-  OFDM_ARG(r != 0, "OMP_estimate: %s", why);
-  return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, F);
 }
 
 // ---- (H_f - H_est)(H_f - H_est)' / N_carrier for the four estimates (:202-205); H_f = fft(h_jj)(1..N_carrier) from the taps

@@ -59,6 +59,8 @@ struct ofdm_rx_plan {
   size_t ws_raw_bytes = 0;
   uint32_t descr = 0;      // per-frame DeScrambler of the pack stages (ofdm_rx_plan_set_descrambler): 0 or DESCR_ON | register bits
   void* d_p2_sop = nullptr; // ofdm_task5_part2_tile: spline operator of interpolate.m [n_carrier x np], double
+  int omp_route = ofdm::OMP_ROUTE_BATCH;   // OMP stage of ofdm_rx_chain_task5 and the Task-5 sweeps (ofdm_rx_plan_set_omp_route)
+  int last_omp = 0;         // the kernel that stage ran in the last call: OMP_ROUTE_BATCH / OMP_ROUTE_WIDE, 0 = none (MMSE mode, generic entry)
 };
 
 // every entry that takes a plan: the context must still be on the plan's device
@@ -77,6 +79,8 @@ int rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8
                        uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
+// ofdm_omp_route.hip: the generic single-kernel entry runs its own in-kernel pursuit -- a plan in OMP_ROUTE_WIDE is refused there
+int omp_route_check_generic(ofdm_rx_plan* pl);
 }
 
 // view of a plan for the fast / split stages
@@ -103,4 +107,5 @@ inline void make_plan_view(ofdm_rx_plan* pl, ofdm::FastPlanView& pv, double ls_i
   pv.ws_lsv = &pl->ws_lsv; pv.ws_lsv_bytes = &pl->ws_lsv_bytes;
   pv.data_mod4 = pl->data_mod4;
   pv.descr = pl->descr;
+  pv.omp_route = pl->omp_route; pv.omp_out = &pl->last_omp;
 }

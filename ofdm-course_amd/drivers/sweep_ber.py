@@ -35,6 +35,12 @@ travel in the float64 all-reduce.  The JSON line names the profile under "fading
 decodes all points of a batch in one call with --fused, with --fading, --mer and --nmse as for omp.  (--estimator mmse is the
 fixed-h form of T5/Task5_part2.m:176-177: one point per call, no --fading.)  The JSON line names the estimator.
 
+--fused --random-pilots NP [--mask-seed S] [--dictionary full] (M): the random-mask study of T5/Task5_part2.m:58-64 at sweep
+rate.  The plan's pilots are a sorted random mask of NP carriers in 1..N_carrier (`task5_part2.random_pilot_layout`, seeded by
+--mask-seed); --dictionary full gives the estimator all Nfft delays (K = Nfft, :181-184) and puts the plan's OMP stage in "auto"
+(`RxPlan.set_omp_route`): omp_batch_kernel while its state fits the LDS, else omp_wide_kernel.  The JSON line carries "pilots":
+"random", "n_pilots", "mask_seed", "K" and "omp_route", the kernel the OMP stage ran.
+
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -67,8 +73,45 @@ def check_fading(config, estimator, fused, fading, nmse):
     return None
 
 
+def check_pilots(config, estimator, fused, random_pilots, dictionary):
+    """What --random-pilots / --dictionary full need; the text of the refusal, or None."""
+    if random_pilots is None and dictionary != "full":
+        return None
+    if not fused:
+        return "--random-pilots / --dictionary full need --fused"
+    if config != "M":
+        return "--random-pilots / --dictionary full are for config M (the wide OMP route is not built for Nfft 8192)"
+    if estimator != "omp":
+        return "--random-pilots / --dictionary full need the OMP estimator"
+    if random_pilots is not None and random_pilots < 3:
+        return "--random-pilots needs at least 3 pilots"
+    return None
+
+
+def apply_pilots(cfg, random_pilots, mask_seed, dictionary):
+    """The frame configuration with the random mask (T5/Task5_part2.m:58-64) and / or the dictionary of all Nfft delays."""
+    from ofdm_course_amd.drivers.task5_part2 import random_pilot_layout
+    if random_pilots is not None:
+        cfg.pilots = random_pilot_layout(cfg.Nfft, cfg.N_carrier, random_pilots, mask_seed)[1]
+        if cfg.K_atoms is None:
+            cfg.K_atoms = int(np.ceil(cfg.N_carrier / cfg.comb))       # the comb's dictionary, unless --dictionary full
+    if dictionary == "full":
+        cfg.K_atoms = cfg.Nfft                                         # :181 F = dftmtx(Nfft), all columns
+    return cfg
+
+
+def make_sweep_plan(cfg, lib, precision, device_index, dictionary="comb"):
+    """The plan of the sweep; with the dictionary of all Nfft delays its OMP stage may take the wide kernel ("auto")."""
+    from ofdm_course_amd import frames as fr
+    plan = fr.make_plan(cfg, lib, precision=precision, device=device_index)
+    if dictionary == "full":
+        plan.set_omp_route("auto")
+    return plan
+
+
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
-        rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False, fading=None, nmse=False):
+        rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False, fading=None, nmse=False,
+        random_pilots=None, mask_seed=1, dictionary="comb"):
     """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}.
     Per batch of the tiles this rank holds, one call decodes one tile (rx_chain_task5 on make_frames_device frames, or
     ber_sweep for an MMSE plan, which is built for one SNR) or all of the batch's points (ber_sweep with --fused,
@@ -79,14 +122,15 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     from ofdm_course_amd import sweep
     from ofdm_course_amd.drivers.common import fading_profile
 
-    bad = check_fading(config, estimator, fused, fading, nmse)
+    bad = check_fading(config, estimator, fused, fading, nmse) or check_pilots(config, estimator, fused, random_pilots, dictionary)
     if bad:
         raise ValueError(bad)
     ofdm.init(device_index)
     dev = torch.device("cuda", device_index)
     cfg = {"C5": fr.config_C5, "M": fr.config_M, "C3": fr.config_C3}[config]()
     snrs = np.arange(0.0, 30.0, 1.5) if snrs is None else np.asarray(snrs, dtype=float)      # 20 points
-    plan = fr.make_plan(cfg, ofdm, precision=precision, device=device_index)
+    cfg = apply_pilots(cfg, random_pilots, mask_seed, dictionary)
+    plan = make_sweep_plan(cfg, ofdm, precision, device_index, dictionary)
     task4 = config == "C3"
     h, _ = ofdm.get_MP_channel_resp(cfg.taps, cfg.Nfft)
     if estimator == "mmse":
@@ -163,6 +207,10 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         res.update(order="noise_first", impairments={"Time_Delay": "random", "Freq_Shift": "random"})
     elif fused:
         res.update(order="noise_first", fused=True)
+    if random_pilots is not None:
+        res.update(pilots="random", n_pilots=int(random_pilots), mask_seed=int(mask_seed))
+    if random_pilots is not None or dictionary == "full":
+        res.update(K=int(cfg.K), omp_route=plan.last_omp_route)
     if fading:
         res["fading"] = {"profile": fading, "sampling_rate": FADING_SAMPLING_RATE, "delays": profile[0].tolist(),
                          "powers": profile[1].tolist()}
@@ -192,6 +240,11 @@ def parser():
     ap.add_argument("--fading", choices=["EPA", "EVA", "ETU"], default=None,
                     help="with --fused at C5 / M: a channel realisation of this delay profile per frame")
     ap.add_argument("--nmse", action="store_true", help="with --fading: per-point NMSE of the channel estimate")
+    ap.add_argument("--random-pilots", type=int, default=None, metavar="NP",
+                    help="with --fused at M: a sorted random mask of NP pilot carriers in 1..N_carrier (Task5_part2.m:58-64)")
+    ap.add_argument("--mask-seed", type=int, default=1, help="seed of the random pilot mask")
+    ap.add_argument("--dictionary", choices=["comb", "full"], default="comb",
+                    help="full: K = Nfft, all delays (Task5_part2.m:181-184); the plan's OMP route is then 'auto'")
     ap.add_argument("--json", default=None)
     return ap
 
@@ -200,7 +253,8 @@ def parse_args(argv=None):
     """The command line; a --fading / --nmse combination the sweep cannot run is a usage error."""
     ap = parser()
     a = ap.parse_args(argv)
-    bad = check_fading(a.config, a.estimator, a.fused, a.fading, a.nmse)
+    bad = check_fading(a.config, a.estimator, a.fused, a.fading, a.nmse) or \
+        check_pilots(a.config, a.estimator, a.fused, a.random_pilots, a.dictionary)
     if bad:
         ap.error(bad)
     return a
@@ -221,7 +275,8 @@ def main():
         else:
             dist.init_process_group(a.backend)
     res = run(a.config, a.snrs, a.batches, a.frames_per_tile, a.precision, estimator=a.estimator, rank=rank, world=world,
-              device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer, fading=a.fading, nmse=a.nmse)
+              device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer, fading=a.fading, nmse=a.nmse,
+              random_pilots=a.random_pilots, mask_seed=a.mask_seed, dictionary=a.dictionary)
     if rank == 0:
         text = json.dumps(res)
         if a.json:
