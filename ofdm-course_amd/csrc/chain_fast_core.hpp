@@ -9,11 +9,10 @@
 
 #include "demap_core.hpp"
 #include "fft_core.hpp"
+#include "chain_route.hpp"
 #include "omp_wide_host.hpp"
 
 namespace ofdm {
-
-constexpr int FAST_MAXT = 32;
 
 __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -21,13 +20,11 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-constexpr int WAVE_LDS_ELEMS = 512 + 64;
-
 // Twiddles of the two inner passes of the wave-local 512-point transform, kept in LDS as
 // [pass][t-1][lane] (lane-contiguous: conflict-free ds_read_b64, no VALU, no live registers):
 //   pass B: W_64^(t*(lane&7))      pass C: W_512^(t*lane)        t = 1..7
 // 2 * 7 * 64 complex values, shared by every wavefront of the workgroup.
-constexpr int WAVE_TW_ELEMS = 2 * 7 * 64;
+// (WAVE_LDS_ELEMS, WAVE_TW_ELEMS: chain_route.hpp)
 
 // tw = exp(-2 pi i m / N) table of the full transform, N = 512 * NW.  Call with all threads; the
 // caller synchronises the workgroup before the first transform.
@@ -255,7 +252,6 @@ __device__ __forceinline__ int group_min_i(int v, int LPF, int lane) {
 // A frame is a group of LPF lanes (sl = lane inside the group); all lanes of the group compute the tiny solve
 // redundantly from group-uniform inputs: no serial lane, no LDS state, no broadcast.  cf = c0 of the frame
 // (LDS), gl = Gram table (LDS).  Writes tap_idx / tap_x of frame f.
-constexpr int OMP_RT = 8;
 template <typename T, int RT = OMP_RT>
 __device__ __forceinline__ void omp_frame_reg(const FastParams<T>& P, const cx<T>* __restrict__ cf,
                                               const cx<T>* __restrict__ gl, int K, int taps, int LPF, int sl,
@@ -641,6 +637,20 @@ __device__ __forceinline__ unsigned pack_frame(const uint8_t* __restrict__ codes
   return pack_frame_t<BPS, false>(codes, n_codes, bps_rt, frame_words, out_f, ref_f, tid, nthr, 0u);
 }
 
+// The kernel-variant axes of the symbol-stage launchers: a run-time slicer order (bits per axis of a square QAM, 0 = table search)
+// or flag becomes a compile-time constant handed to a generic lambda, f(std::integral_constant<int, 0|2|3|4>{}) / f(std::bool_constant<b>{}).
+template <typename F>
+inline int with_ba(int ba, F&& f) {
+  switch (ba) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+template <typename F>
+inline int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
 // What the fast / split paths need to know about an RX plan (ofdm_chain.hip owns the plan)
 struct FastPlanView {
   int nfft, t_guard, n_symb, n_carrier, np, nd, k_atoms, taps, bps, f64, frame_words;
@@ -679,15 +689,17 @@ struct FastPlanView {
   size_t* ws_lsv_bytes = nullptr;
   int omp_route = OMP_ROUTE_BATCH;            // OMP stage of the receiver: OMP_ROUTE_* (ofdm_rx_plan_set_omp_route); ignored in the MMSE modes
   int* omp_out = nullptr;                     // set to the kernel the OMP stage ran: OMP_ROUTE_BATCH (the fused launch included) or OMP_ROUTE_WIDE
+  const ChainRoute* route = nullptr;          // the receiver's route of this call (chain_route.hpp); null outside rx_chain_task5_run
+                                              // (the launchers that read it refuse a view without one: OFDM_NEEDS_ROUTE)
   bool mmse() const { return d_wt != nullptr || mmse_ls != 0; }   // the symbol stages take H from ws_h
 };
+
+#define OFDM_NEEDS_ROUTE(pv) OFDM_ARG((pv).route, "rx_chain_task5: internal: the stage was called without the route of its call")
 
 template <typename T>
 int fast_params_prepare(const FastPlanView& pv, const void* tw, int64_t n_frames, FastParams<T>& P);   // ofdm_chain_fast.hip
 template <typename T>
-int omp_batch_run(const FastParams<T>& P, int64_t n_frames);                                            // ofdm_chain_fast.hip
-template <typename T>
-unsigned omp_batch_lds_bytes(const FastParams<T>& P);     // ofdm_chain_fast.hip: the LDS omp_batch_run asks for (it refuses above 150 KB)
+int omp_batch_run(const FastParams<T>& P, const OmpLayout& lay, bool by_fft, int64_t n_frames);                                            // ofdm_chain_fast.hip
 template <typename T>
 int omp_wide_run(const FastParams<T>& P, int nfft, int64_t n_frames);                                   // ofdm_omp_wide.hip
 
@@ -695,30 +707,18 @@ int omp_wide_run(const FastParams<T>& P, int nfft, int64_t n_frames);           
 // results do not move); a dictionary whose batch state exceeds the LDS bound -- all Nfft delays on a random pilot mask
 // (Task5_part2.m:181-184), K = 1024 in double (Main_model_Task_5.m) -- goes to omp_wide_kernel, one realisation per workgroup.
 // route: OMP_ROUTE_AUTO for the tiles; ofdm_OMP_estimate_batch and a plan (ofdm_rx_plan_set_omp_route) can force either kernel,
-// and a forced route that cannot serve the shape is an argument error.  taken: the kernel that ran.
+// and a forced route that cannot serve the shape is an argument error.  taken: the kernel that ran.  The receiver passes the kernel
+// its route chose (ChainRoute::omp_taken): this is the one function that calls omp_batch_run and omp_wide_run.
 template <typename T>
 inline int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route = OMP_ROUTE_AUTO, int* taken = nullptr) {
   const char* why = nullptr;
-  const int r = omp_route_choose(route, omp_batch_lds_bytes<T>(P), nfft, P.k_atoms, P.taps, &why);
+  bool by_fft;
+  const OmpLayout lay = omp_batch_layout(std::is_same<T, double>::value, P.comb_m, P.np, P.k_atoms, P.taps, &by_fft);
+  const int r = omp_route_choose(route, lay.total, nfft, P.k_atoms, P.taps, &why);
   OFDM_ARG(r != 0, "OMP_estimate: %s", why);
   if (taken) *taken = r;
-  return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, F);
+  return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, lay, by_fft, F);
 }
-
-// The OMP stage of the Task-5 receiver (ofdm_chain_fast.hip, ofdm_chain_split.hip) under the plan's route.  A plan left in
-// OMP_ROUTE_BATCH makes the call it always made, refusal and wording included (rx_chain_task5: OMP stage needs ...).
-template <typename T>
-inline int omp_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_t n_frames) {
-  if (pv.omp_route == OMP_ROUTE_BATCH) {
-    if (pv.omp_out) *pv.omp_out = OMP_ROUTE_BATCH;
-    return omp_batch_run<T>(P, n_frames);
-  }
-  return omp_stage_run<T>(P, pv.nfft, n_frames, pv.omp_route, pv.omp_out);
-}
-
-// Before the first launch of a receiver call on a plan in OMP_ROUTE_AUTO / OMP_ROUTE_WIDE: a shape the chosen kernel cannot serve
-// is refused here, so that no front end runs for it.  (OMP_ROUTE_BATCH keeps its refusal where it was, inside the stage.)
-int omp_route_check(const FastPlanView& pv);                                                            // ofdm_omp_route.hip
 
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,
@@ -733,7 +733,6 @@ int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t*
 void mmse_band_spline(const std::vector<double>& sop, int nc, int np, std::vector<float>& w, std::vector<int32_t>& c0, int& bw, int& span);
 int spline_band_run(const float* sb_w, const int32_t* sb_c0, int bw, int span, const void* v, void* hout, int np, int n_carrier,
                     int64_t n_frames);      // 1 = not taken (LDS), 0 ok, < 0 error
-bool mmse_factored_usable(int np, int np_pad);
 int mmse_factored_run(const void* mt, int np_pad, const float* sb_w, const int32_t* sb_c0, int bw, int span, const void* y, void* v,
                       void* hout, int np, int n_carrier, int64_t n_frames);
 template <typename T>
@@ -766,17 +765,15 @@ inline int mmse_stage_run(const FastPlanView& pv, const FastParams<T>& P, int64_
 }
 
 // ofdm_chain_wave.hip: the symbol stage with one wavefront per frame (Nfft 2048, fp32, N_carrier <= 512)
-bool chain_wave_supported(const FastPlanView& pv);
 int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                            const void* ref, void* errs, void* h_out, void* idx_out, double* mer = nullptr /* MER variant */);
 
 // ofdm_chain_coop.hip: the symbol stage for Nfft 8192 (fp32, N_carrier <= 2048) in one pass over the samples
-bool chain_coop_supported(const FastPlanView& pv);
 int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                            const void* ref, void* errs, void* h_out, void* idx_out, double* mer = nullptr /* MER variant */);
 
 // ofdm_chain_pilot.hip: symbol-1 transform + OMP of every frame in one launch (comb pilots, taps <= OMP_RT)
 template <typename T>
-int pilot_omp_run(const FastParams<T>& P, int nfft, bool prune2, int lg_up, const void* rx, int64_t n_frames);
+int pilot_omp_run(const FastParams<T>& P, int nfft, bool prune2, int lg_up, int fpw, const void* rx, int64_t n_frames);
 
 }  // namespace ofdm

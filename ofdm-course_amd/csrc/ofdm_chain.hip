@@ -20,11 +20,11 @@
 #include <cstring>
 
 #include "chain_fast_core.hpp"
+#include "omp_wave_core.hpp"
 #include "rx_plan.hpp"
 
 namespace ofdm {
 
-constexpr int CH_MAXT = 32;      // dominant taps supported by the fused chain
 
 template <typename T>
 struct ChainParams {
@@ -396,34 +396,41 @@ int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* re
 using namespace ofdm;
 
 namespace ofdm {
-bool chain_fast_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb);     // ofdm_chain_fast.hip
 int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t* pilot_loc, int np, int n_carrier,
                         int m_pad, std::vector<c64>& wt);                                  // ofdm_chain_mmse.hip
-bool chain_split_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb, bool f64);   // ofdm_chain_split.hip
 int chain_split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
                     const void* ref, void* errs, void* h_out, void* idx_out, const int32_t* d_pc0, double* mer);
 int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
                    const void* ref, void* errs, void* h_out, void* idx_out, double* mer);
 }  // namespace ofdm
 
-constexpr size_t GENERIC_LDS_LIMIT = 158 * 1024;
-// dynamic LDS the generic single kernel would ask for (mirrors chain_layout + launch_chain)
-static size_t generic_lds_bytes(const ofdm_rx_plan* pl) {
-  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
-  size_t b = 0;
-  b += align16(cs * (size_t)fft_lds_elems(pl->nfft));
-  b += align16(cs * (size_t)pl->np);
-  b += align16(cs * (size_t)pl->k_atoms);
-  b += align16(sizeof(c64) * CH_MAXT * 2);
-  b += align16(sizeof(int) * (CH_MAXT + 4));
-  b += align16(sizeof(c64) * (size_t)pl->taps * pl->taps);
-  b += align16((size_t)pl->nd * pl->n_symb);
-  return b * (size_t)fft_xforms_per_wg(pl->nfft);
+// chain_route.hpp is free of the device headers and restates three of their sizes: tied together here, where both are seen
+static_assert(route_fft_lds_elems(64) == fft_lds_elems(64) && route_fft_lds_elems(2048) == fft_lds_elems(2048) &&
+              route_fft_lds_elems(8192) == fft_lds_elems(8192), "chain_route.hpp restates fft_lds_elems");
+static_assert(route_fft_xforms_per_wg(64) == fft_xforms_per_wg(64) && route_fft_xforms_per_wg(1024) == fft_xforms_per_wg(1024) &&
+              route_fft_xforms_per_wg(2048) == fft_xforms_per_wg(2048) && route_fft_xforms_per_wg(8192) == fft_xforms_per_wg(8192),
+              "chain_route.hpp restates fft_xforms_per_wg");
+static_assert(route_omp_wave_rs(9) == omp_wave_rs(9) && route_omp_wave_rs(32) == omp_wave_rs(32), "chain_route.hpp restates omp_wave_rs");
+
+// The plan and the request of one call as the numbers the route depends on (chain_route.hpp)
+static ChainShape chain_shape(const ofdm_rx_plan* pl, bool want_mer) {
+  ChainShape s{};
+  s.nfft = pl->nfft; s.n_symb = pl->n_symb; s.n_carrier = pl->n_carrier; s.np = pl->np; s.nd = pl->nd;
+  s.k_atoms = pl->k_atoms; s.taps = pl->taps; s.bps = pl->bps;
+  s.bits_per_axis = pl->cinfo.kind == 1 ? pl->cinfo.bits_per_axis : 0;
+  s.f64 = pl->f64; s.pilots_in_band = pl->pilots_in_band;
+  s.comb_m = pl->comb_m; s.comb_lg_up = pl->comb_lg_up; s.data_mod4 = pl->data_mod4;
+  s.estimator = pl->mmse_ls ? EST_MMSE_LS : pl->d_wt ? EST_MMSE : EST_OMP;
+  s.mmse_factors = pl->d_mt != nullptr; s.np_pad = pl->np_pad; s.m_pad = pl->m_pad;
+  s.descr_on = (pl->descr & DESCR_ON) != 0;
+  s.omp_route = pl->omp_route;
+  s.want_mer = want_mer;
+  return s;
 }
 
 template <typename T, int N>
 static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
+                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer, size_t route_lds) {
   ChainParams<T> P;
   P.n_symb = pl->n_symb; P.t_guard = pl->t_guard; P.n_carrier = pl->n_carrier; P.np = pl->np; P.nd = pl->nd;
   P.k_atoms = pl->k_atoms; P.taps = pl->taps;
@@ -435,7 +442,8 @@ static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, 
   constexpr int FPW = fft_xforms_per_wg(N);
   chain_layout<T>(P, N, pl->bps);
   const size_t dyn = (size_t)P.group_bytes * FPW;
-  OFDM_ARG(dyn <= GENERIC_LDS_LIMIT, "rx_chain_task5: configuration needs %zu bytes of LDS (limit 158 KiB; use fp32 or a smaller frame)", dyn);
+  OFDM_ARG(dyn == route_lds && dyn <= GENERIC_LDS_LIMIT, "rx_chain_task5: internal: chain_layout asks for %zu bytes of LDS, the route counted %zu",
+           dyn, route_lds);                              // (generic_lds_bytes of chain_route.hpp mirrors chain_layout; the route refused a frame beyond the limit)
   if (mer) {                                                           // the MER variant
     OFDM_HIP(hipFuncSetAttribute((const void*)rx_chain_kernel<T, N, MerSums>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     hipLaunchKernelGGL((rx_chain_kernel<T, N, MerSums>), dim3(cdiv_u(n_frames, FPW)), dim3(fft_wg_threads(N)), dyn, ctx().stream,
@@ -689,6 +697,40 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   OFDM_ARG(!errors_out || ref_bits, "rx_chain_task5: errors_out needs ref_bits");
   OFDM_ARG(pl->nd >= 1, "rx_chain_task5: the plan has no data carriers");
   if (n_frames == 0) return OFDM_OK;
+  // the route of this call, before anything is launched or allocated for it; a refused call leaves the plan's last_* as the
+  // stage that refuses used to leave them
+  ChainRoute route;
+  const char* why = nullptr;
+  const int refusal = chain_route_choose(chain_shape(pl, mer_sums_out != nullptr), route, &why);
+  const bool generic = route.entry == ENTRY_GENERIC;
+  if (refusal != REFUSE_MMSE_ENTRY) {
+    pl->last_fast = generic ? 0 : 1;
+    pl->last_omp = route.omp_taken;
+  }
+  switch (refusal) {                                   // (every OFDM_ARG(false, ...) returns: no case reaches the next)
+    case ROUTE_OK: break;
+    case REFUSE_OMP_ROUTE: OFDM_ARG(false, "rx_chain_task5: %s", why);
+    case REFUSE_WIDE_GENERIC:
+      OFDM_ARG(false, "rx_chain_task5: the wide OMP route needs the three-launch receiver (Nfft 512, 1024, 2048 or 4096, pilots inside "
+               "1..N_carrier); this plan takes the generic single-kernel entry (Nfft %d, %s), which runs its own pursuit",
+               pl->nfft, pl->pilots_in_band ? "pilots in band" : "a pilot outside 1..N_carrier");
+    case REFUSE_MMSE_ENTRY:
+      OFDM_ARG(false, "rx_chain_task5: the MMSE mode of a plan needs pilots inside 1..N_carrier, at most 32 taps and a frame "
+                      "whose decisions fit the workgroup's LDS (ofdm_MMSE_CE covers every other case)");
+    case REFUSE_GENERIC_LDS:
+      OFDM_ARG(false, "rx_chain_task5: configuration needs %zu bytes of LDS (limit 158 KiB; use fp32 or a smaller frame)", route.generic_lds);
+    case REFUSE_OMP_LDS:
+      pl->last_fused = 0;
+      OFDM_ARG(false, "rx_chain_task5: OMP stage needs %u bytes of LDS", route.omp.total);
+    case REFUSE_SYMBOL_LDS:
+      pl->last_fused = route.front == FRONT_FUSED ? 1 : 0;
+      OFDM_ARG(false, "rx_chain_task5: symbol stage needs %zu bytes of LDS", route.symbol_lds);
+    case REFUSE_EQ_DEMAP_LDS:
+      pl->last_fused = 0;
+      OFDM_ARG(false, "rx_chain: equalise / demap stage needs %zu bytes of LDS", route.symbol_lds);
+    default:
+      OFDM_ARG(false, "rx_chain_task5: internal: refusal %d of the route has no message", refusal);
+  }
   const size_t cs = csize(flags);
   const size_t frame_samples = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t fb = (size_t)pl->frame_words * 4;
@@ -704,52 +746,32 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_frames, &dmer));
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
-  const bool fast = pl->pilots_in_band &&
-                    chain_fast_supported(pl->nfft, pl->n_carrier, pl->taps, pl->bps, (int64_t)pl->nd * pl->n_symb);
-  // split form: Nfft beyond the wave-local fast path, a frame state that does not fit the generic kernel's LDS, or
-  // MMSE mode outside the fast path
-  bool split = false;
-  if (!fast && pl->pilots_in_band &&
-      chain_split_supported(pl->nfft, pl->n_carrier, pl->taps, pl->bps, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0))
-    split = pl->nfft > 4096 || pl->d_wt != nullptr || pl->mmse_ls || generic_lds_bytes(pl) > GENERIC_LDS_LIMIT;
   // DeScrambler of the plan: fused into the pack stage of the wave-per-frame symbol kernel; every other path -- and the wave
-  // kernel's MER variant -- hands its raw decisions to descr_pass_kernel (the stages themselves then neither compare nor count)
+  // kernel's MER and MMSE variants -- hands its raw decisions to descr_pass_kernel (the stages themselves then neither compare
+  // nor count)
   void* craw = nullptr;
-  bool descr_pass = false;
+  const bool descr_pass = route.descr == DESCR_PASS;
   double* mer = (double*)dmer;
-  if (fast || split) {
+  if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
+  void* cb = descr_pass ? craw : dbits;
+  const void* cr = descr_pass ? nullptr : dref;
+  void* ce = descr_pass ? nullptr : derr;
+  if (!generic) {
     FastPlanView pv;
     make_plan_view(pl, pv, ls_inv_snr);
-    pl->last_fast = 1; OFDM_TRY(omp_route_check(pv));
-    descr_pass = (pl->descr & DESCR_ON) && (mer || !(fast && chain_wave_supported(pv)));
-    if (descr_pass) {
-      OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
-      pv.descr = 0;
-    }
-    void* cb = descr_pass ? craw : dbits;
-    const void* cr = descr_pass ? nullptr : dref;
-    void* ce = descr_pass ? nullptr : derr;
-    if (fast) OFDM_TRY(chain_fast_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, mer));
+    pv.route = &route;
+    if (descr_pass) pv.descr = 0;
+    if (route.entry == ENTRY_FAST) OFDM_TRY(chain_fast_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, mer));
     else OFDM_TRY(chain_split_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, (const int32_t*)pl->d_pc0, mer));
     if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
     return st.finish();
   }
-  descr_pass = (pl->descr & DESCR_ON) != 0;
-  if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, n_frames, &craw));
-  OFDM_ARG(!pl->d_wt && !pl->mmse_ls, "rx_chain_task5: the MMSE mode of a plan needs pilots inside 1..N_carrier, at most 32 taps and a frame "
-                      "whose decisions fit the workgroup's LDS (ofdm_MMSE_CE covers every other case)");
-  pl->last_fast = 0; OFDM_TRY(omp_route_check_generic(pl));
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[0], ctx().stream));
-  {
-    void* cb = descr_pass ? craw : dbits;
-    const void* cr = descr_pass ? nullptr : dref;
-    void* ce = descr_pass ? nullptr : derr;
 #define CALL(NN)                                                                                        \
-  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer)));  \
-  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer)));
-    OFDM_FFT_DISPATCH(pl->nfft, CALL)
+  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds)));  \
+  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds)));
+  OFDM_FFT_DISPATCH(pl->nfft, CALL)
 #undef CALL
-  }
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[3], ctx().stream));
   return st.finish();

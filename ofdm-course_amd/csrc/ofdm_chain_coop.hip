@@ -28,14 +28,9 @@
 
 namespace ofdm {
 
-constexpr int CP_N = 8192, CP_SUB = 2048, CP_R = 4;
-constexpr int CP_TR_ELEMS = 576;
+// (CP_N, CP_SUB, CP_R, CP_TR_ELEMS and the CP_OFF_* offsets of the dynamic LDS: chain_route.hpp, whose chooser sizes the stage)
 // dynamic LDS: W_2048^(l ka) [7][64] | W_64^(t (l & 7)) [7][64] | 4 wave regions | exchange y_s [3][2048] (s = 1..3; its first
 //              512 entries hold h_est during a frame's H transform) | codes [2][nd_pad]      -- 76.1 KB + codes: two workgroups per CU
-constexpr unsigned CP_OFF_TWA = 0, CP_OFF_TWB = 8 * 64 * 7;
-constexpr unsigned CP_OFF_WAVE = CP_OFF_TWB + 8 * 64 * 7;
-constexpr unsigned CP_OFF_EX = CP_OFF_WAVE + CP_R * 8 * CP_TR_ELEMS;
-constexpr unsigned CP_OFF_CODES = CP_OFF_EX + 3 * CP_SUB * 8;
 
 __device__ __forceinline__ cx<float> cp_w32(int m) {
   constexpr float C[9] = {1.0f, 0.98078528040323044913f, 0.92387953251128675613f, 0.83146961230254523708f,
@@ -315,20 +310,11 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
   }
 }
 
-// the kernel's geometry: Nfft 8192, fp32, N_carrier <= 2048, K <= 512, no data carrier on the residue class 0 (mod 4), whole
-// 32-code groups per symbol
-bool chain_coop_supported(const FastPlanView& pv) {
-  if (getenv("OFDM_SPLIT_NO_COOP")) return false;
-  if (pv.f64 || pv.nfft != CP_N || pv.n_carrier > CP_N / 4 || pv.k_atoms > 512 || pv.taps > FAST_MAXT) return false;
-  if ((pv.data_mod4 & 1) != 0 || (pv.nd & 31) != 0 || pv.n_symb < 1) return false;
-  if (pv.descr & DESCR_ON) return false;
-  return CP_OFF_CODES + 2u * (unsigned)((pv.nd + 63) & ~31) <= 78u * 1024;
-}
-
 int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                            const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
+  OFDM_NEEDS_ROUTE(pv);
   const unsigned codes_bytes = (unsigned)((pv.nd + 63) & ~31);
-  const unsigned lds = CP_OFF_CODES + 2 * codes_bytes;
+  const unsigned lds = (unsigned)pv.route->symbol_lds;              // CP_OFF_CODES + 2 * codes_bytes
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const bool mmse = pv.mmse();
@@ -340,20 +326,14 @@ int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
                        (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab, mer_arg...);
     return OFDM_OK;
   };
-  const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-#define COOP_CASE(BAV)                                                                               \
-  if (mer) {                                                                                         \
-    if (mmse) OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, true, MerSums>, MerSums{mer}));           \
-    else OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, false, MerSums>, MerSums{mer}));               \
-  } else if (mmse) OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, true>));                            \
-  else OFDM_TRY(launch(rx_symbols_coop4_kernel<BAV, false>))
-  switch (ba) {
-    case 2: COOP_CASE(2); break;
-    case 3: COOP_CASE(3); break;
-    case 4: COOP_CASE(4); break;
-    default: COOP_CASE(0); break;
-  }
-#undef COOP_CASE
+  OFDM_TRY(with_ba(pv.route->ba, [&](auto BA) {
+    return with_bool(mmse, [&](auto HX) {
+      constexpr int B = decltype(BA)::value;
+      constexpr bool H = decltype(HX)::value;
+      if (mer) return launch(rx_symbols_coop4_kernel<B, H, MerSums>, MerSums{mer});
+      return launch(rx_symbols_coop4_kernel<B, H>);
+    });
+  }));
   return check_launch("rx_symbols_coop4_kernel");
 }
 

@@ -86,52 +86,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? 4 : 3) : 2) voi
 //            and the refit is spread over the group's lanes with R = L^-1 updated in place.
 //            Solve arithmetic is in the data precision T (double in parity mode).
 // ---------------------------------------------------------------------------------------------
-struct OmpLayout {          // byte offsets into dynamic LDS
-  unsigned off_y, off_c0, off_gram, off_state, off_fft, state_bytes, total;
-  int fpw;                  // frames per wavefront
-  int c0_stride;            // row stride of c0 (k_atoms, or np + 1 when c0 overwrites Y in place)
-  int reg_c0;               // wave form with c0 by transform: c0 lands on Y's rows, moves to registers, and the R state takes the bytes
-};
-
-template <typename T>
-static OmpLayout omp_layout(int np, int k_atoms, int taps, int fft_elems = 0) {
-  OmpLayout o;
-  const bool wave = taps > OMP_RT;            // more than OMP_RT taps: one frame per wavefront (omp_wave_core.hpp)
-  // per frame: up to OMP_RT taps nothing (registers); beyond, R = L^-1 [taps][odd stride] complex T
-  o.state_bytes = wave ? (unsigned)((sizeof(cx<T>) * (size_t)taps * omp_wave_rs(taps) + 15) & ~15u) : 16u;
-  const size_t gram_elems = wave ? (size_t)((k_atoms + 511) & ~511) + k_atoms : (size_t)k_atoms;   // two-sided table for the wave form
-  const size_t per_frame = sizeof(cx<T>) * (np + 1) + sizeof(cx<T>) * k_atoms + o.state_bytes;
-  int fpw = wave ? 1 : 4;     // 16 frames per workgroup: 2 workgroups per CU keep 8 wavefronts in flight
-  if (const char* e = getenv("OFDM_OMP_FPW")) { const int v = atoi(e); if (!wave && (v == 1 || v == 2 || v == 4 || v == 8)) fpw = v; }
-  while (fpw > 1 && 4 * fpw * per_frame + sizeof(cx<T>) * gram_elems > 96 * 1024) fpw >>= 1;
-  o.fpw = fpw;
-  const int fb = 4 * fpw;
-  unsigned b = 0;
-  o.c0_stride = k_atoms;
-  o.reg_c0 = (wave && fft_elems > 0 && k_atoms <= 512 && k_atoms <= np + 1 && !getenv("OFDM_OMP_C0_LDS")) ? 1 : 0;
-  const unsigned fft_bytes = (unsigned)((sizeof(cx<T>) * (size_t)fft_elems + 15) & ~15u);
-  if (o.reg_c0) {
-    // Gram table | { Y rows (c0 written over them) + transform scratch }  ==  { R state of the four frames }: 41.8 KB instead of
-    // 74.8 KB at 32 taps, K = Np = 512 -- three resident workgroups per CU instead of two for a pursuit that is bound by the
-    // instruction issue of its (few) wavefronts
-    o.off_gram = b;  b += (unsigned)((sizeof(cx<T>) * gram_elems + 15) & ~15u);
-    o.off_y = b; o.off_c0 = b; o.c0_stride = np + 1;
-    const unsigned ybytes = (unsigned)((sizeof(cx<T>) * fb * (np + 1) + 15) & ~15u);
-    o.off_fft = b + ybytes;
-    o.off_state = b;
-    b += std::max<unsigned>(fb * o.state_bytes, ybytes + fft_bytes);
-    o.total = b;
-    return o;
-  }
-  o.off_y = b;     b += (unsigned)((sizeof(cx<T>) * fb * (np + 1) + 15) & ~15u);   // rows padded by one element
-  o.off_c0 = b;    b += (unsigned)((sizeof(cx<T>) * fb * k_atoms + 15) & ~15u);
-  o.off_gram = b;  b += (unsigned)((sizeof(cx<T>) * gram_elems + 15) & ~15u);
-  // the transform scratch of the c0 stage is dead before the per-frame OMP state is first written: same bytes
-  o.off_state = b; o.off_fft = b;
-  b += std::max<unsigned>(fb * o.state_bytes, fft_bytes);
-  o.total = b;
-  return o;
-}
+// (OmpLayout and omp_layout: chain_route.hpp, whose chooser sizes the stage before anything is launched)
 
 // CM = 2048: comb pilots with Nfft/comb = 2048 -- c0 = S^H Y is the first K outputs of a 2048-point inverse transform of
 // Y (one workgroup transform per frame, tw_m = its twiddle table) instead of the K x Np dictionary correlation.
@@ -405,15 +360,6 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
 // host side
 // ---------------------------------------------------------------------------------------------
 
-bool chain_fast_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb) {
-  if (getenv("OFDM_CHAIN_GENERIC")) return false;
-  if (!(nfft == 512 || nfft == 1024 || nfft == 2048 || nfft == 4096)) return false;
-  if (taps > FAST_MAXT || bps > 8) return false;
-  if (nd_nsymb > 48 * 1024) return false;
-  (void)n_carrier;
-  return true;
-}
-
 // Fills the kernel parameter block of a plan and grows the plan's workspace to n_frames (shared by the fast
 // path here and the split path of ofdm_chain_split.hip).
 template <typename T>
@@ -452,13 +398,12 @@ template int fast_params_prepare<double>(const FastPlanView&, const void*, int64
 
 // omp_batch_kernel over n_frames frames: pilot LS values P.ypil -> taps P.tap_idx / P.tap_x
 template <typename T>
-int omp_batch_run(const FastParams<T>& P, int64_t n_frames) {
+int omp_batch_run(const FastParams<T>& P, const OmpLayout& lay, bool by_fft, int64_t n_frames) {   // (lay, by_fft: omp_batch_layout)
   hipStream_t st = ctx().stream;
-  const bool by_fft = P.comb_m == 2048 && P.np <= 2048 && P.k_atoms <= 2048 && !getenv("OFDM_OMP_NO_FFT");   // (= omp_batch_lds_bytes below)
-  const OmpLayout lay = omp_layout<T>(P.np, P.k_atoms, P.taps, by_fft ? fft_lds_elems(2048) : 0);
-  OFDM_ARG(lay.total <= 150 * 1024, "rx_chain_task5: OMP stage needs %u bytes of LDS", lay.total);
+  constexpr bool f64 = std::is_same<T, double>::value;
+  OFDM_ARG(lay.total <= STAGE_LDS_LIMIT, "rx_chain_task5: OMP stage needs %u bytes of LDS", lay.total);
   const unsigned grid = cdiv_u(n_frames, 4 * lay.fpw);
-  const bool mfma = std::is_same<T, float>::value && (P.k_atoms % 16 == 0) && (P.np % 4 == 0) && !getenv("OFDM_OMP_NO_MFMA");
+  const bool mfma = omp_mfma_ok(f64, P.np, P.k_atoms);
   auto launch = [&](auto kern, const void* twm) -> int {
     OFDM_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lay.total, st, P, lay, n_frames, (const cx<T>*)twm);
@@ -475,8 +420,8 @@ int omp_batch_run(const FastParams<T>& P, int64_t n_frames) {
   }
   return check_launch("omp_batch_kernel");
 }
-template int omp_batch_run<float>(const FastParams<float>&, int64_t);
-template int omp_batch_run<double>(const FastParams<double>&, int64_t);
+template int omp_batch_run<float>(const FastParams<float>&, const OmpLayout&, bool, int64_t);
+template int omp_batch_run<double>(const FastParams<double>&, const OmpLayout&, bool, int64_t);
 
 template <typename T, int NW, bool PRUNE2>
 static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
@@ -489,11 +434,12 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
   const int ncu = ctx().num_cu;
   hipStream_t st = ctx().stream;
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[0], st));
-  const bool fused = !mmse && pv.comb_lg_up >= 0 && pv.taps <= OMP_RT && pv.k_atoms <= 512 && pv.omp_route != OMP_ROUTE_WIDE && !getenv("OFDM_FAST_UNFUSED");
+  const ChainRoute& route = *pv.route;
+  const bool fused = route.front == FRONT_FUSED;
   if (pv.fused_out) *pv.fused_out = fused ? 1 : 0;
   if (fused) {
     // kernels 1+2 in one launch (comb pilots): c0 by a wave-local inverse transform (ofdm_chain_pilot.hip)
-    OFDM_TRY(pilot_omp_run<T>(P, 512 * NW, PRUNE2, pv.comb_lg_up, rx, n_frames));
+    OFDM_TRY(pilot_omp_run<T>(P, 512 * NW, PRUNE2, pv.comb_lg_up, route.fpw, rx, n_frames));
     if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[1], st));
   } else {
     // kernel 1
@@ -507,24 +453,20 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
     if (mmse) {
       OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
     } else {
-      OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
+      OFDM_TRY(omp_stage_run<T>(P, pv.nfft, n_frames, route.omp_taken, pv.omp_out));
     }
   }
   if (pv.ev && !fused) OFDM_HIP(hipEventRecord(pv.ev[2], st));
   // kernel 3
   if constexpr (std::is_same<T, float>::value && NW == 4 && PRUNE2) {
-    // (a MER request under the exact-slicer switch takes the four-wavefront MER variant below)
-    if (chain_wave_supported(pv) && !(mer && getenv("OFDM_WAVE_EXACT_SLICER"))) {   // one wavefront per frame (ofdm_chain_wave.hip)
+    if (route.symbols == SYM_WAVE) {                                 // one wavefront per frame (ofdm_chain_wave.hip)
       OFDM_TRY(chain_wave_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
       return OFDM_OK;
     }
   }
   {
-    constexpr int N = 512 * NW;
-    const size_t dyn = sizeof(cx<T>) * ((size_t)NW * WAVE_LDS_ELEMS + WAVE_TW_ELEMS) +
-                       (((size_t)pv.nd * pv.n_symb + 31) & ~size_t(31));
-    OFDM_ARG(dyn <= 150 * 1024, "rx_chain_task5: symbol stage needs %zu bytes of LDS", dyn);
+    const size_t dyn = route.symbol_lds;                           // (within its 150 KiB: the route refuses a frame beyond)
     // persistent grid = CUs x resident workgroups per CU (from the occupancy API: registers + LDS);
     // workgroups are independent, so an optimistic answer only queues a few of them.
     auto launch = [&](auto kern, auto... mer_arg) -> int {          // (mer_arg: MerSums for a MER variant)
@@ -535,34 +477,14 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
                          (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, mer_arg...);
       return OFDM_OK;
     };
-    const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-    if (mer) {
-      const MerSums ms{mer};
-      switch (ba) {
-        case 2: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 2, true, MerSums>, ms)
-                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 2, false, MerSums>, ms)); break;
-        case 3: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 3, true, MerSums>, ms)
-                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 3, false, MerSums>, ms)); break;
-        case 4: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 4, true, MerSums>, ms)
-                              : launch(rx_symbols_kernel<T, NW, PRUNE2, 4, false, MerSums>, ms)); break;
-        default: OFDM_TRY(mmse ? launch(rx_symbols_kernel<T, NW, PRUNE2, 0, true, MerSums>, ms)
-                               : launch(rx_symbols_kernel<T, NW, PRUNE2, 0, false, MerSums>, ms)); break;
-      }
-    } else if (mmse) {
-      switch (ba) {
-        case 2: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 2, true>)); break;
-        case 3: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 3, true>)); break;
-        case 4: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 4, true>)); break;
-        default: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 0, true>)); break;
-      }
-    } else {
-      switch (ba) {
-        case 2: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 2>)); break;
-        case 3: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 3>)); break;
-        case 4: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 4>)); break;
-        default: OFDM_TRY(launch(rx_symbols_kernel<T, NW, PRUNE2, 0>)); break;
-      }
-    }
+    OFDM_TRY(with_ba(route.ba, [&](auto BA) {
+      return with_bool(mmse, [&](auto HX) {
+        constexpr int B = decltype(BA)::value;
+        constexpr bool H = decltype(HX)::value;
+        if (mer) return launch(rx_symbols_kernel<T, NW, PRUNE2, B, H, MerSums>, MerSums{mer});
+        return launch(rx_symbols_kernel<T, NW, PRUNE2, B, H>);
+      });
+    }));
     OFDM_TRY(check_launch("rx_symbols_kernel"));
   }
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
@@ -572,18 +494,19 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
 template <typename T>
 static int dispatch_fast(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
                          const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
-  const int nw = pv.nfft / 512;
-  const bool prune = pv.n_carrier <= 128 * nw;
-#define FAST_CALL(NWV)                                                                                       \
-  return prune ? launch_fast<T, NWV, true>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer)       \
-               : launch_fast<T, NWV, false>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer)
-  switch (nw) {
-    case 1: FAST_CALL(1);
-    case 2: FAST_CALL(2);
-    case 4: FAST_CALL(4);
-    case 8: FAST_CALL(8);
+  OFDM_NEEDS_ROUTE(pv);
+  auto call = [&](auto NWC) {
+    constexpr int NWV = decltype(NWC)::value;
+    return with_bool(pv.route->prune != 0, [&](auto PR) {
+      return launch_fast<T, NWV, decltype(PR)::value>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
+    });
+  };
+  switch (pv.route->nw) {
+    case 1: return call(std::integral_constant<int, 1>{});
+    case 2: return call(std::integral_constant<int, 2>{});
+    case 4: return call(std::integral_constant<int, 4>{});
+    case 8: return call(std::integral_constant<int, 8>{});
   }
-#undef FAST_CALL
   set_error("rx_chain_task5(fast): unsupported Nfft %d", pv.nfft);
   return OFDM_ERR_UNSUPPORTED;
 }
@@ -593,17 +516,5 @@ int chain_fast_run(const FastPlanView& pv, const void* tw, const void* rx, int64
   if (pv.f64) return dispatch_fast<double>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
   return dispatch_fast<float>(pv, tw, rx, n_frames, bits, ref, errs, h_out, idx_out, mer);
 }
-
-// The dynamic LDS omp_batch_run asks for at the shape of P (its omp_layout): above 150 KB it refuses, and the Task-5 part-2 tiles
-// take omp_wide_kernel instead (omp_stage_run, chain_fast_core.hpp).  The two lines are those of omp_batch_run (:457-458) and must
-// stay equal to them: the route choice and the refusal agree only then (omp_batch_run keeps its own copy so that its lines,
-// which tests/routes.py cites, do not move).
-template <typename T>
-unsigned omp_batch_lds_bytes(const FastParams<T>& P) {
-  const bool by_fft = P.comb_m == 2048 && P.np <= 2048 && P.k_atoms <= 2048 && !getenv("OFDM_OMP_NO_FFT");
-  return omp_layout<T>(P.np, P.k_atoms, P.taps, by_fft ? fft_lds_elems(2048) : 0).total;
-}
-template unsigned omp_batch_lds_bytes<float>(const FastParams<float>&);
-template unsigned omp_batch_lds_bytes<double>(const FastParams<double>&);
 
 }  // namespace ofdm

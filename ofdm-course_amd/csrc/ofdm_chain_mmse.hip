@@ -468,12 +468,10 @@ int spline_band_run(const float* sb_w, const int32_t* sb_c0, int bw, int span, c
   return check_launch("spline_band_kernel");
 }
 
-bool mmse_factored_usable(int np, int np_pad) { return np % 4 == 0 && np_pad % 16 == 0 && !getenv("OFDM_MMSE_NO_MFMA") && !getenv("OFDM_MMSE_DENSE"); }
-
 int mmse_factored_run(const void* mt, int np_pad, const float* sb_w, const int32_t* sb_c0, int bw, int span, const void* y, void* v,
                       void* hout, int np, int n_carrier, int64_t n_frames) {
   hipStream_t st = ctx().stream;
-  if (np_pad <= 256 && hout && !getenv("OFDM_MMSE_TWO_LAUNCHES")) {   // both factors in one launch
+  if (hout && mmse_one_launch(np_pad)) {   // both factors in one launch
     constexpr int ft = 32;                                     // (16 frames per workgroup, two workgroups per CU: 0.096 against 0.086 ms)
     const size_t lds = sizeof(cx<float>) * (size_t)np_pad * (ft + 2);
     (void)hipFuncSetAttribute((const void*)mmse_fused_kernel<ft>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -481,16 +479,15 @@ int mmse_factored_run(const void* mt, int np_pad, const float* sb_w, const int32
                        (const cx<float>*)y, (const float4*)sb_w, sb_c0, bw, (cx<float>*)hout, np, np_pad, n_carrier, n_frames);
     return check_launch("mmse_fused_kernel");
   }
-  int G = 4;                                                  // 32 rows x 32 frames per wavefront (G = 8 / 4 / 2 / 1 measured: 146 / 129 / 129 / 141 us per 8192 frames)
-  if (const char* e = getenv("OFDM_MMSE_G")) G = atoi(e);
+  const int G = mmse_factored_g();
   const unsigned gy = (unsigned)(((np_pad + 31) / 32 + 3) / 4);
   auto launch = [&](auto kern, int g) {
     hipLaunchKernelGGL(kern, dim3((unsigned)((n_frames + 8 * g - 1) / (8 * g)), gy), dim3(256), 0, st, (const cx<float>*)mt,
                        (const cx<float>*)y, (cx<float>*)v, np, np_pad, np, n_frames);
   };
-  if (G >= 8) launch(mmse_apply_mfma_kernel<8>, 8);
-  else if (G >= 4) launch(mmse_apply_mfma_kernel<4>, 4);
-  else if (G >= 2) launch(mmse_apply_mfma_kernel<2>, 2);
+  if (G == 8) launch(mmse_apply_mfma_kernel<8>, 8);
+  else if (G == 4) launch(mmse_apply_mfma_kernel<4>, 4);
+  else if (G == 2) launch(mmse_apply_mfma_kernel<2>, 2);
   else launch(mmse_apply_mfma_kernel<1>, 1);
   OFDM_TRY(check_launch("mmse_apply_mfma_kernel"));
   const int rc = spline_band_run(sb_w, sb_c0, bw, span, v, hout, np, n_carrier, n_frames);
@@ -502,7 +499,7 @@ template <typename T>
 int mmse_apply_run(const void* wt, const void* y, void* hout, int np, int m_pad, int n_carrier, int64_t n_frames) {
   hipStream_t st = ctx().stream;
   if constexpr (std::is_same<T, float>::value) {
-    if (np % 4 == 0 && m_pad % 16 == 0 && !getenv("OFDM_MMSE_NO_MFMA")) {
+    if (mmse_dense_mfma_ok(false, np, m_pad)) {
       const dim3 grid((unsigned)((n_frames + 63) / 64), (unsigned)(((m_pad + 31) / 32 + 3) / 4));
       hipLaunchKernelGGL(mmse_apply_mfma_kernel<8>, grid, dim3(256), 0, st, (const cx<float>*)wt, (const cx<float>*)y,
                          (cx<float>*)hout, np, m_pad, n_carrier, n_frames);

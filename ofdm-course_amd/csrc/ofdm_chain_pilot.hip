@@ -114,12 +114,8 @@ __global__ __launch_bounds__(64 * NW) void rx_pilot_omp_kernel(FastParams<T> P, 
 }
 
 template <typename T, int NW, bool PRUNE2, int RT>
-static int pilot_omp_launch(const FastParams<T>& P, int lg_up, const void* rx, int64_t n_frames) {
-  // frames per wavefront: as many as keep the per-group Y / c0 buffer within 8 KB (4 workgroups of ~35 KB per CU)
+static int pilot_omp_launch(const FastParams<T>& P, int lg_up, int fpw, const void* rx, int64_t n_frames) {   // (fpw: pilot_omp_fpw, chain_route.hpp)
   const int ystride = std::max(P.np, P.k_atoms);
-  int fpw = 4;
-  if (const char* e = getenv("OFDM_PILOT_FPW")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) fpw = v; }
-  while (fpw > 1 && sizeof(cx<T>) * (size_t)NW * fpw * ystride > 8 * 1024) fpw >>= 1;
   const size_t dyn = sizeof(cx<T>) * ((size_t)NW * WAVE_LDS_ELEMS + WAVE_TW_ELEMS + P.k_atoms + (size_t)NW * fpw * ystride);
   OFDM_ARG(dyn <= 150 * 1024, "rx_chain_task5: pilot stage needs %zu bytes of LDS", dyn);
   auto kern = rx_pilot_omp_kernel<T, NW, PRUNE2, RT>;
@@ -131,19 +127,19 @@ static int pilot_omp_launch(const FastParams<T>& P, int lg_up, const void* rx, i
 }
 
 template <typename T, int NW, bool PRUNE2>
-static int pilot_omp_taps(const FastParams<T>& P, int lg_up, const void* rx, int64_t n_frames) {
-  if (P.taps <= 2) return pilot_omp_launch<T, NW, PRUNE2, 2>(P, lg_up, rx, n_frames);
-  if (P.taps <= 4) return pilot_omp_launch<T, NW, PRUNE2, 4>(P, lg_up, rx, n_frames);
-  if (P.taps <= 6) return pilot_omp_launch<T, NW, PRUNE2, 6>(P, lg_up, rx, n_frames);
-  return pilot_omp_launch<T, NW, PRUNE2, 8>(P, lg_up, rx, n_frames);
+static int pilot_omp_taps(const FastParams<T>& P, int lg_up, int fpw, const void* rx, int64_t n_frames) {
+  if (P.taps <= 2) return pilot_omp_launch<T, NW, PRUNE2, 2>(P, lg_up, fpw, rx, n_frames);
+  if (P.taps <= 4) return pilot_omp_launch<T, NW, PRUNE2, 4>(P, lg_up, fpw, rx, n_frames);
+  if (P.taps <= 6) return pilot_omp_launch<T, NW, PRUNE2, 6>(P, lg_up, fpw, rx, n_frames);
+  return pilot_omp_launch<T, NW, PRUNE2, 8>(P, lg_up, fpw, rx, n_frames);
 }
 
 template <typename T>
-int pilot_omp_run(const FastParams<T>& P, int nfft, bool prune2, int lg_up, const void* rx, int64_t n_frames) {
+int pilot_omp_run(const FastParams<T>& P, int nfft, bool prune2, int lg_up, int fpw, const void* rx, int64_t n_frames) {
   OFDM_ARG(P.taps <= OMP_RT && P.k_atoms <= 512 && lg_up >= 0, "rx_chain_task5: pilot stage called outside its domain");
 #define PILOT_CALL(NWV)                                                              \
-  return prune2 ? pilot_omp_taps<T, NWV, true>(P, lg_up, rx, n_frames)               \
-                : pilot_omp_taps<T, NWV, false>(P, lg_up, rx, n_frames)
+  return prune2 ? pilot_omp_taps<T, NWV, true>(P, lg_up, fpw, rx, n_frames)               \
+                : pilot_omp_taps<T, NWV, false>(P, lg_up, fpw, rx, n_frames)
   switch (nfft / 512) {
     case 1: PILOT_CALL(1);
     case 2: PILOT_CALL(2);
@@ -155,7 +151,7 @@ int pilot_omp_run(const FastParams<T>& P, int nfft, bool prune2, int lg_up, cons
   return OFDM_ERR_UNSUPPORTED;
 }
 
-template int pilot_omp_run<float>(const FastParams<float>&, int, bool, int, const void*, int64_t);
-template int pilot_omp_run<double>(const FastParams<double>&, int, bool, int, const void*, int64_t);
+template int pilot_omp_run<float>(const FastParams<float>&, int, bool, int, int, const void*, int64_t);
+template int pilot_omp_run<double>(const FastParams<double>&, int, bool, int, int, const void*, int64_t);
 
 }  // namespace ofdm

@@ -575,17 +575,10 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
   }
 }
 
-static size_t r2_lds_bytes(const FastPlanView& pv) {
-  return sizeof(cx<float>) * ((size_t)8 * WAVE_LDS_ELEMS + WAVE_TW_ELEMS) + (((size_t)pv.nd * pv.n_symb + 31) & ~size_t(31));
-}
-static bool chain_r2_supported(const FastPlanView& pv) {
-  if (getenv("OFDM_SPLIT_NO_R2")) return false;
-  if (pv.f64 || pv.nfft != 8192 || pv.n_carrier > 2048 || pv.taps > FAST_MAXT || pv.n_symb < 1) return false;
-  return r2_lds_bytes(pv) <= 78u * 1024;                       // two workgroups per CU
-}
 static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                                 const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
-  const size_t lds = r2_lds_bytes(pv);
+  OFDM_NEEDS_ROUTE(pv);
+  const size_t lds = pv.route->symbol_lds;
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const void *tw4 = nullptr, *tw8 = nullptr;
@@ -601,29 +594,15 @@ static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>&
                        mer_arg...);
     return OFDM_OK;
   };
-  const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-#define R2_CASE(BAV)                                                                              \
-  if (mer) {                                                                                      \
-    if (mmse) OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, true, MerSums>, MerSums{mer}));           \
-    else OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, false, MerSums>, MerSums{mer}));               \
-  } else if (mmse) OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, true>));                            \
-  else OFDM_TRY(launch(rx_symbols_r2_kernel<BAV, false>))
-  switch (ba) {
-    case 2: R2_CASE(2); break;
-    case 3: R2_CASE(3); break;
-    case 4: R2_CASE(4); break;
-    default: R2_CASE(0); break;
-  }
-#undef R2_CASE
+  OFDM_TRY(with_ba(pv.route->ba, [&](auto BA) {
+    return with_bool(mmse, [&](auto HX) {
+      constexpr int B = decltype(BA)::value;
+      constexpr bool H = decltype(HX)::value;
+      if (mer) return launch(rx_symbols_r2_kernel<B, H, MerSums>, MerSums{mer});
+      return launch(rx_symbols_r2_kernel<B, H>);
+    });
+  }));
   return check_launch("rx_symbols_r2_kernel");
-}
-
-bool chain_split_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb, bool f64) {
-  if (getenv("OFDM_CHAIN_GENERIC")) return false;
-  if (taps > FAST_MAXT || bps > 8) return false;
-  const size_t lds = (size_t)(f64 ? 16 : 8) * n_carrier + (((size_t)nd_nsymb + 31) & ~size_t(31));
-  (void)nfft;
-  return lds <= 120 * 1024;
 }
 
 // equalise + demap + pack + BER of n_frames frames from X columns of x_stride rows (rows 1..N_carrier are read)
@@ -634,9 +613,8 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
   hipStream_t st = ctx().stream;
   DemapTable<T> tab;
   fill_demap_table<T>(*pv.dict, *pv.cinfo, tab);
-  const size_t dyn = sizeof(cx<T>) * (size_t)pv.n_carrier + (((size_t)pv.nd * pv.n_symb + 31) & ~size_t(31)) + 16;
-  const bool vec = std::is_same<T, float>::value && (pv.n_carrier & 1) == 0 && (x_stride & 1) == 0 && pv.n_carrier <= 2048 &&
-                   !getenv("OFDM_EQD_SCALAR");
+  const size_t dyn = eq_demap_lds_bytes(std::is_same<T, double>::value, pv.n_carrier, (int64_t)pv.nd * pv.n_symb);
+  const bool vec = eq_demap_vec_ok(std::is_same<T, double>::value, pv.n_carrier, x_stride);
   OFDM_ARG(dyn <= 150 * 1024, "rx_chain: equalise / demap stage needs %zu bytes of LDS", dyn);
   auto grid_of = [&](const void* kern) {
     int per_cu = resident_blocks_per_cu(kern, 256, dyn);
@@ -656,32 +634,16 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
     return OFDM_OK;
   };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-#define SPLIT_CASE(BAV)                                                                                    \
-  if (mer_sums) {                                                                                          \
-    if constexpr (std::is_same<T, float>::value) {                                                         \
-      if (vec) {                                                                                           \
-        if (hext) OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, true, true, MerOut>));                           \
-        else OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, false, true, MerOut>));                               \
-        break;                                                                                             \
-      }                                                                                                    \
-    }                                                                                                      \
-    if (hext) OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, true, false, MerOut>)); else OFDM_TRY(launch_mer(eq_demap_kernel<T, BAV, false, false, MerOut>)); \
-    break;                                                                                                 \
-  }                                                                                                        \
-  if constexpr (std::is_same<T, float>::value) {                                                           \
-    if (vec) {                                                                                             \
-      if (hext) OFDM_TRY(launch(eq_demap_kernel<T, BAV, true, true>)); else OFDM_TRY(launch(eq_demap_kernel<T, BAV, false, true>)); \
-      break;                                                                                               \
-    }                                                                                                      \
-  }                                                                                                        \
-  if (hext) OFDM_TRY(launch(eq_demap_kernel<T, BAV, true>)); else OFDM_TRY(launch(eq_demap_kernel<T, BAV, false>))
-  switch (ba) {
-    case 2: SPLIT_CASE(2); break;
-    case 3: SPLIT_CASE(3); break;
-    case 4: SPLIT_CASE(4); break;
-    default: SPLIT_CASE(0); break;
-  }
-#undef SPLIT_CASE
+  OFDM_TRY(with_ba(ba, [&](auto BA) {
+    return with_bool(hext, [&](auto HX) {
+      constexpr int B = decltype(BA)::value;
+      constexpr bool H = decltype(HX)::value;
+      if constexpr (std::is_same<T, float>::value) {                 // (fp64 has no VEC build)
+        if (vec) return mer_sums ? launch_mer(eq_demap_kernel<T, B, H, true, MerOut>) : launch(eq_demap_kernel<T, B, H, true>);
+      }
+      return mer_sums ? launch_mer(eq_demap_kernel<T, B, H, false, MerOut>) : launch(eq_demap_kernel<T, B, H, false>);
+    });
+  }));
   return check_launch("eq_demap_kernel");
 }
 template int eq_demap_run<float>(const FastPlanView&, const FastParams<float>&, const cx<float>*, int, bool, int64_t, void*,
@@ -695,9 +657,10 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   FastParams<T> P;
   OFDM_TRY(fast_params_prepare<T>(pv, tw, n_frames, P));
   const bool mmse = pv.mmse();
+  OFDM_NEEDS_ROUTE(pv);
+  const ChainRoute& route = *pv.route;
   if constexpr (std::is_same<T, float>::value) {
-    const bool coop = chain_coop_supported(pv);                        // (the faster one where its layout conditions hold)
-    const bool r2 = !coop && chain_r2_supported(pv);
+    const bool coop = route.symbols == SYM_COOP4, r2 = route.symbols == SYM_R2;
     if (r2 || coop) {
       // one pass over the samples (ofdm_chain_coop.hip): the first symbol of every frame -> stash + pilot LS values, the
       // estimator, then every other symbol transformed, equalised, sliced, packed and counted without an X round trip
@@ -708,7 +671,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
                                      (int64_t)(8192 + pv.t_guard) * pv.n_symb));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[1], st));
       if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
-      else OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
+      else OFDM_TRY(omp_stage_run<T>(P, pv.nfft, n_frames, route.omp_taken, pv.omp_out));
       if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
       if (r2) OFDM_TRY(chain_r2_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
       else OFDM_TRY(chain_coop_symbols_run(pv, P, rx, n_frames, bits, ref, errs, h_out, idx_out, mer));
@@ -727,13 +690,13 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   hipStream_t st = ctx().stream;
   if (pv.fused_out) *pv.fused_out = 0;
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[0], st));
-  if (pv.nfft == 8192 && !getenv("OFDM_SPLIT_GENERIC_FFT")) {
+  if (route.front != FRONT_DEMOD_GENERIC_PLS) {
     // the pilot LS values come out of the transform of each frame's first symbol (no pilot_ls pass)
-    const bool fuse = !getenv("OFDM_SPLIT_NO_PLS_FUSE");
+    const bool fuse = route.front != FRONT_DEMOD8192_PLS;
     // the rows of pilot-only sub-transforms are skipped on data symbols -- only when the pilot LS values come out of this
     // kernel (the separate pilot_ls pass and h_out-less consumers read the data rows and the first symbol's pilots only)
     OFDM_TRY(demod_keep8192_run<T>(rx, xk, n_frames * pv.n_symb, pv.t_guard, pv.n_carrier, fuse ? (void*)P.ypil : nullptr, d_pc0,
-                                   P.pilots, pv.np, pv.n_symb, fuse && !getenv("OFDM_SPLIT_ALL_ROWS") ? pv.d_drole : nullptr));
+                                   P.pilots, pv.np, pv.n_symb, route.front == FRONT_DEMOD8192 ? pv.d_drole : nullptr));
     if (!fuse) {
       hipLaunchKernelGGL(pilot_ls_kernel<T>, dim3(cdiv_u(n_frames * pv.np, 256)), dim3(256), 0, st, P, (const cx<T>*)xk, d_pc0,
                          n_frames);
@@ -747,7 +710,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   }
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[1], st));
   if (mmse) OFDM_TRY(mmse_stage_run<T>(pv, P, n_frames));
-  else OFDM_TRY(omp_stage_run<T>(pv, P, n_frames));
+  else OFDM_TRY(omp_stage_run<T>(P, pv.nfft, n_frames, route.omp_taken, pv.omp_out));
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
   OFDM_TRY(eq_demap_run<T>(pv, P, xk, pv.n_carrier, mmse, n_frames, bits, ref, errs, h_out, idx_out, nullptr, 0, 0, 0,
                            mer));                                      // (+ the MER_func sums of the whole RX_IQ: skip 0)

@@ -36,22 +36,8 @@
 
 namespace ofdm {
 
-constexpr int WV_N = 2048;
-constexpr int WV_TR_ELEMS = 576;          // wave-private transpose region (largest index 72*7+63 = 567, 65*7+63 = 518)
-constexpr int WV_TW_ROWS = 31;            // W_2048^(lane * kj), kj = 1..31
 constexpr int WV_WPB = 4;              // wavefronts (= frames in flight) per workgroup; three workgroups per CU
 
-// dynamic LDS: W_2048 table [31][64] | W_64 table [7][64] | data positions [4][64] (8-byte stride) | per-wave regions
-constexpr unsigned WV_OFF_TW = 0, WV_OFF_TWB = 8 * 64 * WV_TW_ROWS, WV_OFF_DD = WV_OFF_TWB + 8 * 64 * 7;
-constexpr unsigned WV_OFF_LUT = WV_OFF_DD + 8 * 64 * 4;              // decision thresholds of demap_square_lut
-constexpr unsigned WV_OFF_WAVE = WV_OFF_LUT + 256;
-constexpr unsigned WV_TRASH_OFF = 8 * WV_TR_ELEMS, WV_DESCR_OFF = WV_TRASH_OFF + 8 * 64, WV_CODES_OFF = WV_DESCR_OFF + 16;
-// (WV_DESCR_OFF: one word per wavefront, the DeScrambler state between the pack batches of a frame -- in LDS so that it
-//  costs no register across the symbol loop)
-struct WaveLayout {
-  unsigned wave_bytes, total;
-  int cb;                                 // symbols per pack batch
-};
 
 // W_32^m = exp(-2 pi i m / 32), m compile-time after unrolling
 __device__ __forceinline__ cx<float> w32(int m) {
@@ -402,35 +388,13 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static bool wave_layout(int nd, int n_symb, int wpb, WaveLayout& lay) {
-  // symbols per pack batch: every batch but the last must end on a 32-code boundary
-  int cb = 1;
-  while ((cb * nd) % 32 != 0) ++cb;                                    // cb <= 32
-  const int unit = cb;
-  while (cb * nd < 1920 && cb < n_symb) cb += unit;
-  if (cb >= n_symb) cb = n_symb;                                       // one batch: the whole frame
-  const unsigned codes_bytes = (unsigned)(((size_t)cb * nd + 31 + 32) & ~size_t(31));
-  if (codes_bytes > 6144) return false;
-  lay.cb = cb;
-  lay.wave_bytes = (WV_CODES_OFF + codes_bytes + 15) & ~15u;
-  lay.total = WV_OFF_WAVE + (unsigned)wpb * lay.wave_bytes;
-  return lay.total <= (wpb == 8 ? 78u : 52u) * 1024;                   // two / three workgroups per CU
-}
-
-bool chain_wave_supported(const FastPlanView& pv) {
-  if (getenv("OFDM_FAST_NO_WAVE")) return false;
-  if ((pv.descr & DESCR_ON) && pv.mmse()) return false;      // DeScrambler + MMSE mode: the four-wavefront symbol stage
-  if (pv.f64 || pv.nfft != WV_N || pv.n_carrier > WV_N / 4 || pv.taps > FAST_MAXT) return false;
-  WaveLayout lay;
-  return wave_layout(pv.nd, pv.n_symb, 4, lay) && wave_layout(pv.nd, pv.n_symb, 8, lay);
-}
-
 int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                            const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   // two builds of the kernel: 4 wavefronts per workgroup at <= 168 VGPRs (three workgroups = 12 wavefronts per CU) and
   // 8 per workgroup at <= 128 VGPRs (two workgroups = 16 wavefronts per CU)
   const int wpb = WV_WPB;       // (eight wavefronts per workgroup at <= 128 VGPRs, the LUT slicer and the form without look-ahead
                                 //  registers were measured in round 2 -- 965 / 937 / +1.5 % against 911 us -- and are no longer built)
+  OFDM_NEEDS_ROUTE(pv);
   WaveLayout lay;
   OFDM_ARG(wave_layout(pv.nd, pv.n_symb, wpb, lay), "rx_chain_task5(wave): frame does not fit the wave-per-frame stage");
   DemapTable<float> tab;
@@ -446,68 +410,43 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
                        mer_arg...);
     return OFDM_OK;
   };
-  const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
-  const bool exact = getenv("OFDM_WAVE_EXACT_SLICER") != nullptr;
-  // no data carrier with index = 0 (mod 4) -- pilots "1:4:end", the benchmark layout: the round of that residue class is not
-  // computed on data symbols (a quarter of the post-register work and of the register transform's second stage)
-  const bool skip0 = (pv.data_mod4 & 15) == 14 && !getenv("OFDM_WAVE_NO_SKIP");
-  const bool skip02 = (pv.data_mod4 & 15) == 10 && !getenv("OFDM_WAVE_NO_SKIP");      // pilots 1:2:end: two of the four rounds
-#define WAVE_CASE(BAV, HX)                                                                \
-  if (exact) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 0>));            \
-  else if (skip0) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 1>));    \
-  else if (skip02) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 5>));   \
-  else OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4>))
-  // per-frame DeScrambler in the pack stage (ofdm_rx_plan_set_descrambler): its own instantiations, OMP mode only
-#define WAVE_CASE_D(BAV)                                                                            \
-  if (exact) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 0, 0, true>));          \
-  else if (skip0) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 1, true>));     \
-  else if (skip02) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 5, true>));    \
-  else OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, false, 4, 0, true, 2, 0, true>))
-  // MER variants (default slicer only; the caller routes MER requests under OFDM_WAVE_EXACT_SLICER and DeScrambler plans
-  // elsewhere): P.descr must be off here, descr_pass_kernel descrambles
-#define WAVE_CASE_M(BAV, HX)                                                                                         \
-  if (skip0) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 1, false, MerSums>, MerSums{mer}));      \
-  else if (skip02) OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 5, false, MerSums>, MerSums{mer})); \
-  else OFDM_TRY(launch(rx_symbols_wave_kernel<BAV, HX, 4, 0, true, 2, 0, false, MerSums>, MerSums{mer}))
-  if (mer) {
-    OFDM_ARG(!exact && !(P.descr & DESCR_ON), "rx_chain_task5(wave): no MER variant of the exact-slicer / DeScrambler forms");
-    switch (ba) {
-      case 2: if (mmse) { WAVE_CASE_M(2, true); } else { WAVE_CASE_M(2, false); } break;
-      case 3: if (mmse) { WAVE_CASE_M(3, true); } else { WAVE_CASE_M(3, false); } break;
-      case 4: if (mmse) { WAVE_CASE_M(4, true); } else { WAVE_CASE_M(4, false); } break;
-      default: if (mmse) { WAVE_CASE_M(0, true); } else { WAVE_CASE_M(0, false); } break;
+  // the skip forms leave out the rounds of residue classes without data carriers (a quarter / half of the post-register work
+  // and of the register transform's second stage)
+  const int form = pv.route->wave_form;
+  const bool exact = form == WAVE_FORM_EXACT, skip0 = form == WAVE_FORM_SKIP0, skip02 = form == WAVE_FORM_SKIP02;
+  const bool descr = (P.descr & DESCR_ON) != 0;
+  // MER builds exist for the default slicer only and never descramble; the DeScrambler builds (pack stage) exist in OMP mode only:
+  // the route sends every other request elsewhere (ofdm_rx_plan_set_descrambler: descr_pass_kernel)
+  OFDM_ARG(!mer || (!exact && !descr), "rx_chain_task5(wave): no MER variant of the exact-slicer / DeScrambler forms");
+  OFDM_ARG(mer || !descr || !mmse, "rx_chain_task5(wave): the DeScrambler variant exists in OMP mode only");
+  OFDM_TRY(with_ba(pv.route->ba, [&](auto BA) {
+    constexpr int B = decltype(BA)::value;
+    if (mer) return with_bool(mmse, [&](auto HX) {
+      constexpr bool H = decltype(HX)::value;
+      const MerSums ms{mer};
+      if (skip0) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 1, false, MerSums>, ms);
+      if (skip02) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 5, false, MerSums>, ms);
+      return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 0, false, MerSums>, ms);
+    });
+    if (descr) {
+      if (exact) return launch(rx_symbols_wave_kernel<B, false, 4, 0, true, 0, 0, true>);
+      if (skip0) return launch(rx_symbols_wave_kernel<B, false, 4, 0, true, 2, 1, true>);
+      if (skip02) return launch(rx_symbols_wave_kernel<B, false, 4, 0, true, 2, 5, true>);
+      return launch(rx_symbols_wave_kernel<B, false, 4, 0, true, 2, 0, true>);
     }
-  } else if (P.descr & DESCR_ON) {
-    OFDM_ARG(!mmse, "rx_chain_task5(wave): the DeScrambler variant exists in OMP mode only");
-    switch (ba) {
-      case 2: WAVE_CASE_D(2); break;
-      case 3: WAVE_CASE_D(3); break;
-      case 4: WAVE_CASE_D(4); break;
-      default: WAVE_CASE_D(0); break;
-    }
-  } else if (mmse) {
-    switch (ba) {
-      case 2: WAVE_CASE(2, true); break;
-      case 3: WAVE_CASE(3, true); break;
-      case 4: WAVE_CASE(4, true); break;
-      default: WAVE_CASE(0, true); break;
-    }
-  } else {
-    switch (ba) {
-      case 2: WAVE_CASE(2, false); break;
-      case 3:
+    return with_bool(mmse, [&](auto HX) {
+      constexpr bool H = decltype(HX)::value;
 #ifdef OFDM_DIAG   // tools-only build (libofdm_mi355x_diag.so, build.py --diag): issue time without the sample stream
-        if (getenv("OFDM_WAVE_ABL")) { OFDM_TRY(launch(rx_symbols_wave_kernel<3, false, 4, 1>)); break; }
+      if constexpr (B == 3 && !H) {
+        if (getenv("OFDM_WAVE_ABL")) return launch(rx_symbols_wave_kernel<3, false, 4, 1>);
+      }
 #endif
-        WAVE_CASE(3, false);
-        break;
-      case 4: WAVE_CASE(4, false); break;
-      default: WAVE_CASE(0, false); break;
-    }
-  }
-#undef WAVE_CASE
-#undef WAVE_CASE_D
-#undef WAVE_CASE_M
+      if (exact) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 0>);
+      if (skip0) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 1>);
+      if (skip02) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 5>);
+      return launch(rx_symbols_wave_kernel<B, H, 4>);
+    });
+  }));
   return check_launch("rx_symbols_wave_kernel");
 }
 

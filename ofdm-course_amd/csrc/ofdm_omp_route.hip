@@ -4,42 +4,10 @@
 //   OMP_ROUTE_AUTO   the same wherever omp_batch_kernel's state fits the LDS (fused launch included, bit-identical); else
 //                    rx_pilot_kernel / the split form's pilot stage -> omp_wide_kernel (ofdm_omp_wide.hip) -> the symbol stage
 //   OMP_ROUTE_WIDE   always the three-launch form with omp_wide_kernel
-// A shape the chosen kernel cannot serve is an argument error before anything is launched, never a fallback.  The dispatch itself
-// is omp_stage_run (chain_fast_core.hpp) at the three call sites of the receiver; the MMSE modes have no OMP stage and ignore the
-// route.
+// A shape the chosen kernel cannot serve is an argument error before anything is launched, never a fallback: chain_route_choose
+// (chain_route.hpp) decides, omp_stage_run (chain_fast_core.hpp) launches what it chose at the three call sites of the receiver;
+// the MMSE modes have no OMP stage and ignore the route.
 #include "rx_plan.hpp"
-
-namespace ofdm {
-
-int omp_route_check(const FastPlanView& pv) {
-  if (pv.omp_out) *pv.omp_out = pv.mmse() ? 0 : OMP_ROUTE_BATCH;      // (the fused launch is a batch pursuit; omp_stage_run overwrites)
-  if (pv.mmse() || pv.omp_route == OMP_ROUTE_BATCH) return OFDM_OK;
-  unsigned lds;
-  if (pv.f64) {
-    FastParams<double> P{};
-    P.np = pv.np; P.k_atoms = pv.k_atoms; P.taps = pv.taps; P.comb_m = pv.comb_m;
-    lds = omp_batch_lds_bytes<double>(P);
-  } else {
-    FastParams<float> P{};
-    P.np = pv.np; P.k_atoms = pv.k_atoms; P.taps = pv.taps; P.comb_m = pv.comb_m;
-    lds = omp_batch_lds_bytes<float>(P);
-  }
-  const char* why = nullptr;
-  const int r = omp_route_choose(pv.omp_route, lds, pv.nfft, pv.k_atoms, pv.taps, &why);
-  OFDM_ARG(r != 0, "rx_chain_task5: %s", why);
-  return OFDM_OK;
-}
-
-int omp_route_check_generic(ofdm_rx_plan* pl) {
-  pl->last_omp = 0;
-  OFDM_ARG(pl->omp_route != OMP_ROUTE_WIDE,
-           "rx_chain_task5: the wide OMP route needs the three-launch receiver (Nfft 512, 1024, 2048 or 4096, pilots inside "
-           "1..N_carrier); this plan takes the generic single-kernel entry (Nfft %d, %s), which runs its own pursuit",
-           pl->nfft, pl->pilots_in_band ? "pilots in band" : "a pilot outside 1..N_carrier");
-  return OFDM_OK;
-}
-
-}  // namespace ofdm
 
 using namespace ofdm;
 

@@ -22,7 +22,6 @@
 namespace ofdm {
 
 int demod_keep_device(const void* y, void* x, int nfft, int64_t n_symb, int t_guard, int n_keep, bool f64);   // ofdm_modem.hip
-bool chain_split_supported(int nfft, int n_carrier, int taps, int bps, int64_t nd_nsymb, bool f64);           // ofdm_chain_split.hip
 
 // ---- conv(x, h_f.', 'full')(1:len) for every realisation f: sparse taps (delay, amplitude) per realisation
 template <typename T>
@@ -552,7 +551,7 @@ extern "C" int ofdm_task5_part2_tile(ofdm_rx_plan* pl, const void* tx_noised, co
   OFDM_ARG((is_f64(flags) ? 1 : 0) == pl->f64, "task5_part2_tile: precision flag differs from the plan's");
   OFDM_ARG(pl->pilots_in_band && pl->np >= 2, "task5_part2_tile: needs at least two pilots, all inside 1..N_carrier");
   OFDM_ARG(n_ch_taps >= 1 && n_ch_taps <= 64 && n_frames >= 0 && n_frames <= 65535, "task5_part2_tile: 1..64 channel taps, at most 65535 realisations");
-  OFDM_ARG(chain_split_supported(pl->nfft, pl->n_carrier, pl->taps, pl->bps, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0),
+  OFDM_ARG(chain_split_fits(pl->taps, pl->bps, pl->n_carrier, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0),
            "task5_part2_tile: the frame's decisions do not fit the equalise stage's LDS");
   if (n_frames == 0) return OFDM_OK;
   const size_t cs = csize(flags);

@@ -79,8 +79,6 @@ int rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8
                        uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
-// ofdm_omp_route.hip: the generic single-kernel entry runs its own in-kernel pursuit -- a plan in OMP_ROUTE_WIDE is refused there
-int omp_route_check_generic(ofdm_rx_plan* pl);
 }
 
 // view of a plan for the fast / split stages

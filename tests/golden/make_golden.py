@@ -138,8 +138,39 @@ def papr_fixture():
                         ccdf_in=np.round(paprs, 3), ccdf_x=x, ccdf=c)
 
 
+def chain_routes_parent():
+    """tests/golden/chain_routes_parent.json: every case of routes.CASES through test_gpu_chain_routes._call on the GPU, twice; a
+    field is kept when its hashes agree between the two runs in every case.  The library must be the one whose outputs are to
+    be pinned: the build of the commit before the receiver's route decision moved into chain_route.hpp, named by OFDM_LIB_PATH
+    (that commit has neither this recipe nor tests/test_gpu_chain_routes_parent.py, whose route_hashes it uses: run it from
+    this tree against that build).  A case added later is recorded the same way, against the same build."""
+    import json
+
+    import pytest
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ofdm_course_amd as ofdm
+    from routes import CASES
+    from test_gpu_chain_routes_parent import route_hashes
+    ofdm.init()
+    runs = []
+    for _ in range(2):
+        with pytest.MonkeyPatch.context() as mp:
+            runs.append({c.name: route_hashes(ofdm, o, mp, c) for c in CASES})
+    fields = [f for f in ("packed", "errors", "index", "H")
+              if all(runs[0][n].get(f) == runs[1][n].get(f) for n in runs[0])]
+    cases = {n: {f: r[f] for f in fields if f in r} for n, r in runs[0].items()}
+    path = os.environ.get("OFDM_GOLDEN_OUT", os.path.join(HERE, "chain_routes_parent.json"))
+    with open(path, "w") as fh:
+        fh.write('{"fields": ' + json.dumps(fields) + ',\n "cases": {\n')
+        fh.write(",\n".join(f'  {json.dumps(n)}: {json.dumps(cases[n], sort_keys=True, separators=(",", ":"))}' for n in sorted(cases)))
+        fh.write("\n }}\n")
+    print(os.path.basename(path), "fields kept:", fields, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    if "--papr-only" in sys.argv:
+    if "--chain-routes-parent" in sys.argv:
+        chain_routes_parent()
+    elif "--papr-only" in sys.argv:
         papr_fixture()
     else:
         main()

@@ -193,14 +193,12 @@ def test_route_matches_oracle(ofdm, oracle, monkeypatch, case):
 
 @pytest.mark.parametrize("case", REFUSALS, ids=lambda c: c.name)
 def test_route_refusals(ofdm, oracle, monkeypatch, case):
-    """Host-side argument errors: the message is the one of the cited line, the stage whose LDS need is over its limit is not
-    launched, and the plan (and the library) keep working afterwards.  (refuse-omp-lds: launch_fast has already launched
-    rx_pilot_kernel when omp_batch_run refuses, ofdm_chain_fast.hip:498-511 -- the call ends with a half-run front end, whose
-    workspace the next call overwrites.)"""
+    """Host-side argument errors: the message is the one of the refusal the model names, the stage whose LDS need is over its
+    limit is not launched, and the plan (and the library) keep working afterwards."""
     from ofdm_course_amd import frames as fr
     with pytest.raises(routes.Refused) as model:
         case.route()
-    assert model.value.where == routes.REFUSAL_LINES[case.name]
+    assert model.value.where == routes.REFUSAL_IDS[case.name]
     cfg = case.cfg()
     _set_env(monkeypatch, {})
     plan = fr.make_plan(cfg, ofdm, precision=case.precision)

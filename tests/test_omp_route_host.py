@@ -44,10 +44,10 @@ def test_comb_pilots_alias_the_full_dictionary(oracle):
 
 def test_case_routes_are_the_ones_meant():
     lim = routes.STAGE_LDS_LIMIT
-    for c in oc.AUTO_4096 + oc.AUTO_2048:                           # a default plan refuses them at the cited line
+    for c in oc.AUTO_4096 + oc.AUTO_2048:                           # a default plan refuses them: omp_lds
         with pytest.raises(routes.Refused) as e:
             routes.expected_route(c, c.precision, "omp", False, True, {})
-        assert e.value.where == "ofdm_chain_fast.hip:459"
+        assert e.value.where == "omp_lds"
     for c in oc.WIDE_512:
         assert routes.expected_route(c, c.precision, "omp", False, True, {}).front == "fused"
     for c in oc.WIDE_512_MASK + oc.WIDE_1024:
@@ -72,16 +72,33 @@ def test_binding_and_python_surface():
 
 
 def test_receiver_call_sites_go_through_the_stage_function():
-    """The three OMP call sites of the receiver honour the plan's route; omp_batch_run is called by the stage function only."""
+    """The three OMP call sites of the receiver run the kernel the route chose (ChainRoute::omp_taken) and report it;
+    omp_batch_run and omp_wide_run are each called from the one stage function only, which ofdm_chain_fast.hip,
+    ofdm_chain_split.hip and ofdm_part2.hip reach and nothing calls around."""
     code = {}
-    for fn in ("ofdm_chain_fast.hip", "ofdm_chain_split.hip", "ofdm_part2.hip"):
-        src = open(os.path.join(CSRC, fn)).read()
-        code[fn] = "\n".join(ln.split("//")[0] for ln in src.splitlines())
-    assert len(re.findall(r"OFDM_TRY\(omp_stage_run<T>\(pv, P, n_frames\)\)", code["ofdm_chain_fast.hip"])) == 1
-    assert len(re.findall(r"OFDM_TRY\(omp_stage_run<T>\(pv, P, n_frames\)\)", code["ofdm_chain_split.hip"])) == 2
+    for fn in sorted(os.listdir(CSRC)):
+        if fn.endswith((".hip", ".hpp")):
+            src = open(os.path.join(CSRC, fn)).read()
+            code[fn] = "\n".join(ln.split("//")[0] for ln in src.splitlines())
+    site = r"OFDM_TRY\(omp_stage_run<T>\(P, pv\.nfft, n_frames, route\.omp_taken, pv\.omp_out\)\)"
+    assert len(re.findall(site, code["ofdm_chain_fast.hip"])) == 1
+    assert len(re.findall(site, code["ofdm_chain_split.hip"])) == 2
+    assert len(re.findall(r"omp_stage_run<T>\(", code["ofdm_chain_fast.hip"])) == 1
+    assert len(re.findall(r"omp_stage_run<T>\(", code["ofdm_chain_split.hip"])) == 2
+    assert len(re.findall(r"OFDM_TRY\(omp_stage_run<T>\(", code["ofdm_part2.hip"])) == 3
     for fn in ("ofdm_chain_split.hip", "ofdm_part2.hip"):
-        assert "omp_batch_run" not in code[fn], fn
+        assert "omp_batch_run" not in code[fn] and "omp_wide_run" not in code[fn], fn
     assert "OFDM_TRY(omp_batch_run" not in code["ofdm_chain_fast.hip"]
+    # calls (a name followed by its template argument and a parenthesis, outside a declaration or definition): one each, in the
+    # stage function of chain_fast_core.hpp
+    calls = {k: [(fn, m.group(0)) for fn, c in code.items() for m in re.finditer(r"(?<!int )\b" + k + r"<T>\(", c)]
+             for k in ("omp_batch_run", "omp_wide_run")}
+    for k, v in calls.items():
+        assert [fn for fn, _ in v] == ["chain_fast_core.hpp"], (k, v)
+    stage = code["chain_fast_core.hpp"]
+    body = stage[stage.index("inline int omp_stage_run("):]
+    body = body[: body.index("\n}\n")]
+    assert "omp_batch_run<T>(" in body and "omp_wide_run<T>(" in body and stage.count("inline int omp_stage_run(") == 1
 
 
 # ---- the drivers against a library that records

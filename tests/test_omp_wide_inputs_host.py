@@ -78,7 +78,7 @@ def test_host_code_under_the_sanitizers(host_program):
     assert lines[-1] == f"visited {want}"
 
 
-# (shape, batch layout refused?) -- the bounds of omp_batch_kernel from its own layout (ofdm_chain_fast.hip:97-134)
+# (shape, batch layout refused?) -- the bounds of omp_batch_kernel from its own layout (omp_layout, chain_route.hpp)
 def _batch_total(np_, k, taps, f64, comb_m=0):
     by_fft = comb_m == 2048 and np_ <= 2048 and k <= 2048
     return routes.omp_layout(np_, k, taps, f64, routes.fft_lds_elems(2048) if by_fft else 0, {})[2]

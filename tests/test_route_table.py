@@ -112,7 +112,7 @@ def test_every_field_value_and_pair_occurs(precision, fields):
     assert pairs == {(s, b) for s in fam for b in (0, 2, 3, 4)}, {(s, b) for s in fam for b in (0, 2, 3, 4)} - pairs
     # (by family: ROUTES says which (instantiation, ba) pairs are knowingly left out)
     est = {(routes.symbols_family(r.symbols), routes.estimator_family(r.estimator)) for r in rs}
-    want = {(s, e) for s in fam for e in ("omp", "mmse")} - {("chain_generic", "mmse")}          # refused: ofdm_chain.hip:739
+    want = {(s, e) for s in fam for e in ("omp", "mmse")} - {("chain_generic", "mmse")}          # refused: mmse_entry
     assert est == want, want - est
 
 
@@ -126,8 +126,8 @@ def test_refusals_are_where_the_model_says():
     for c in REFUSALS:
         with pytest.raises(routes.Refused) as e:
             c.route()
-        assert e.value.where == routes.REFUSAL_LINES[c.name], c.name
-    # ofdm_chain_fast.hip:527 cannot fire (routes.FAST_SYMBOL_LDS_MAX): no case for it
+        assert e.value.where == routes.REFUSAL_IDS[c.name], c.name
+    # the symbol_lds refusal of the fast form cannot fire (routes.FAST_SYMBOL_LDS_MAX): no case for it
     assert routes.FAST_SYMBOL_LDS_MAX <= routes.STAGE_LDS_LIMIT
     # the refused frames really are oracle-sized and the refusing geometry is reachable without the refusing condition
     base = dataclasses.replace([c for c in REFUSALS if c.name == "refuse-generic-lds"][0], env={})
