@@ -1156,10 +1156,9 @@ def task5_part2_tile(plan: RxPlan, tx_noised, taps_list, SNR_dB, ref_bits_packed
     Returns dict(nmse=[4, n] float64, errors=[4, n] uint32) with rows LS, MMSE, MP, OMP."""
     call = _Call(tx_noised, f64=plan.f64)
     n = len(taps_list)
-    t0 = np.asarray(taps_list[0])
-    T = t0.shape[0]
-    delay = np.empty((n, T), dtype=np.int32)
-    amp = np.empty((n, T), dtype=np.complex128)
+    T = np.asarray(taps_list[0]).shape[0] if n else 1
+    delay = np.zeros((max(n, 1), T), dtype=np.int32)                  # (an empty tile still hands the entry valid pointers)
+    amp = np.zeros((max(n, 1), T), dtype=np.complex128)
     for i, t in enumerate(taps_list):
         t = np.asarray(t)
         if t.shape[0] != T:
@@ -1174,6 +1173,9 @@ def task5_part2_tile(plan: RxPlan, tx_noised, taps_list, SNR_dB, ref_bits_packed
     nm, pnm = call._out((n, 4), np.float64, torch.float64 if call.dev else None)      # memory [4][n]
     er, per = call._out((n, 4), np.uint32, torch.int32 if call.dev else None)
     ampv = np.ascontiguousarray(amp).view(np.float64)
+    if n == 0:
+        pnm = call._out((1, 4), np.float64, torch.float64 if call.dev else None)[1]
+        per = call._out((1, 4), np.uint32, torch.int32 if call.dev else None)[1]
     L.check(call.lib.ofdm_task5_part2_tile(plan.handle, call.cin(tx_noised), C.c_void_p(delay.ctypes.data),
                                            C.c_void_p(ampv.ctypes.data), T, n, float(SNR_dB), pref, pnm, per, call.flags),
             "task5_part2_tile")

@@ -314,7 +314,7 @@ static int part2_tile_run(ofdm_rx_plan* pl, const void* dtx, const int32_t* ddel
   // MMSE: v = rf2 (rf2 + I/snr)^-1 Y per realisation, H = Sop * v
   {
     const size_t dyn = sizeof(c64) * 4 * (size_t)np * 4;
-    OFDM_ARG(dyn <= 150 * 1024, "task5_part2_tile: MMSE stage supports at most 585 pilots");
+    OFDM_ARG(np <= 585, "task5_part2_tile: MMSE stage supports at most 585 pilots");
     OFDM_HIP(hipFuncSetAttribute((const void*)mmse_wave_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     hipLaunchKernelGGL(mmse_wave_kernel<T>, dim3(cdiv_u(F, 4)), dim3(256), dyn, st, (const cx<T>*)P.ypil, dcvals, inv_snr, np, dv, F);
     hipLaunchKernelGGL(p2_apply_operator_kernel<T>, og, dim3(128), sizeof(cx<T>) * np * P2_FT, st, (const double*)pl->d_p2_sop,
