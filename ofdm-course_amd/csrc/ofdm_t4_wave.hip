@@ -1,7 +1,7 @@
 // OFDM_demodulator of the batched Task-4 receiver (ofdm_rx_chain_task4, T4/Main_model_Task_4.m:292-310) with ONE WAVEFRONT PER
 // SYMBOL RUN: Nfft = 2048, fp32, N_carrier <= 1024 (BASELINE config 3).
 //
-// The four-wavefronts-per-symbol form (t4_demod_kernel, ofdm_sync.hip) pays four workgroup barriers per symbol and transforms
+// The four-wavefronts-per-symbol form (t4_demod_kernel, ofdm_chain_t4.hip) pays four workgroup barriers per symbol and transforms
 // all 2048 bins; here a run of consecutive symbols of one frame never leaves its wavefront (the decomposition of the metric
 // kernel, ofdm_chain_wave.hip): lane l holds x[l + 64 j], j < 32 -- 32 coalesced 8-byte nontemporal loads per symbol, taken
 // from rx THROUGH the STO fix (add_STO(Rx, TgPosition); add_STO(., -(Nfft+T_guard)), :292-294) and multiplied by the merged
@@ -17,10 +17,12 @@
 #include <algorithm>
 
 #include "chain_fast_core.hpp"
+#include "t4_route.hpp"
 
 namespace ofdm {
 
 constexpr int T4W_N = 2048;
+static_assert(T4W_N == T4_WAVE_NFFT, "t4_demod_wave_supported (t4_route.hpp) asks for this kernel's Nfft");
 constexpr int T4W_TR_ELEMS = 576;                      // wave-private transpose region (largest index 72*7+63, 65*7+63)
 constexpr int T4W_WPB = 4;
 constexpr unsigned T4W_OFF_TW = 0, T4W_OFF_TWB = 8 * 64 * 31, T4W_OFF_PR = T4W_OFF_TWB + 8 * 64 * 7;
@@ -393,10 +395,6 @@ int t4_ifo_wave_launch(const void* rx, const void* tw, int64_t len, int t_guard,
   hipLaunchKernelGGL(t4_ifo_wave_kernel, dim3(grid), dim3(64 * T4W_WPB), T4W_LDS, ctx().stream, (const cx<float>*)rx, (const cx<float>*)tw,
                      len, t_guard, F, td, tg, fo, 0.77, ifo_out, status);
   return check_launch("t4_ifo_wave_kernel");
-}
-
-bool t4_demod_wave_supported(int nfft, int n_keep, int np, bool f64) {
-  return !f64 && nfft == T4W_N && n_keep <= 1024 && (n_keep & 1) == 0 && !getenv("OFDM_T4_NO_WAVE");   // even: 16-byte row alignment
 }
 
 int t4_demod_wave_launch(const void* rx, void* X, const void* tw, int64_t len, int t_guard, int n_symb, int64_t F, int td, int fd,

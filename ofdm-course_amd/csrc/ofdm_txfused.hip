@@ -58,6 +58,7 @@
 
 #include "fft_core.hpp"
 #include "rx_plan.hpp"
+#include "t4_route.hpp"
 #include "tx_philox.hpp"
 
 namespace ofdm {
@@ -673,13 +674,9 @@ static int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, 
   return OFDM_OK;
 }
 
-// bytes per frame of the ofdm_rx_chain_task4 arena (pl->ws_t4, task4_run in ofdm_sync.hip): the aligned stream, the
-// demodulated symbols, the compact pilot rows, the remove_IFO segment + spectrum, the estimates (+ per-frame scalars)
+// bytes per frame of the ofdm_rx_chain_task4 arena (pl->ws_t4): t4_frame_bytes, beside t4_arena_layout in t4_route.hpp
 static size_t t4_frame_bytes(const ofdm_rx_plan* pl) {
-  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32);
-  const size_t len = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
-  return cs * (len + (size_t)pl->nfft * pl->n_symb + (size_t)pl->np * pl->n_symb + 2 * (size_t)pl->nfft + pl->np +
-               pl->n_carrier) + 128 + (size_t)pl->frame_words * 4;
+  return t4_frame_bytes(T4Shape{pl->nfft, pl->t_guard, pl->n_symb, pl->n_carrier, pl->np, pl->f64, 0, 0, 0, 0}, pl->frame_words);
 }
 
 static int txf_check_modes(int sto_mode, int cfo_mode, const char* what) {

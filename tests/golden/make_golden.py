@@ -167,9 +167,36 @@ def chain_routes_parent():
     print(os.path.basename(path), "fields kept:", fields, os.path.getsize(path), "bytes")
 
 
+def t4_routes_parent():
+    """tests/golden/t4_routes_parent.json: every run of test_gpu_task4_routes_parent.RUNS on the GPU, twice; a field is kept when
+    it agrees between the two runs in every run.  As for chain_routes_parent, the library (OFDM_LIB_PATH) must be the build of
+    the commit before the Task-4 receiver's route decision moved into t4_route.hpp; run this from the present tree against it."""
+    import json
+
+    import pytest
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ofdm_course_amd as ofdm
+    from test_gpu_task4_routes_parent import FIELDS, RUNS, route_record, run_id
+    ofdm.init()
+    recs = []
+    for _ in range(2):
+        with pytest.MonkeyPatch.context() as mp:
+            recs.append({run_id(r): route_record(ofdm, o, mp, r) for r in RUNS})
+    fields = [f for f in FIELDS if all(recs[0][n][f] == recs[1][n][f] for n in recs[0])]
+    path = os.environ.get("OFDM_GOLDEN_OUT", os.path.join(HERE, "t4_routes_parent.json"))
+    with open(path, "w") as fh:
+        fh.write('{"fields": ' + json.dumps(fields) + ',\n "runs": {\n')
+        fh.write(",\n".join(f'  {json.dumps(n)}: {json.dumps({f: recs[0][n][f] for f in fields}, sort_keys=True, separators=(",", ":"))}'
+                            for n in sorted(recs[0])))
+        fh.write("\n }}\n")
+    print(os.path.basename(path), "fields kept:", fields, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
     if "--chain-routes-parent" in sys.argv:
         chain_routes_parent()
+    elif "--t4-routes-parent" in sys.argv:
+        t4_routes_parent()
     elif "--papr-only" in sys.argv:
         papr_fixture()
     else:

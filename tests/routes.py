@@ -658,7 +658,7 @@ ROUTES = [
 
 # Excluded from the table by name:
 #   *_WG_PER_CU   resident-workgroup overrides: they change the grid size of a persistent kernel, not which code runs
-#   OFDM_T4_*     switches of the Task-4 receiver (ofdm_sync.hip / ofdm_t4_wave.hip), not of this dispatcher
+#   OFDM_T4_*     switches of the Task-4 receiver (read in t4_route.hpp; tests/t4_routes.py and test_t4_route_host.py audit them), not of this dispatcher
 #   OFDM_WAVE_ABL read only under #ifdef OFDM_DIAG (ofdm_chain_wave.hip): the shipped library does not contain it
 EXCLUDED_SWITCHES = (re.compile(r"_WG_PER_CU$"), re.compile(r"^OFDM_T4_"), re.compile(r"^OFDM_WAVE_ABL$"))
 

@@ -45,7 +45,7 @@ replay(): the function-by-function chain of T4/Main_model_Task_4.m:278-347 on th
 taken from the oracle's own curves (how far the two 0.77 decisions of the reference are from flipping):
   m_acf = min | |rho_i| - 0.77 | over 0-based i from W to the start of the second run (to the end when the search fails)
   m_ifo = min | |spec_k| - 0.77 | / max|spec| over the bins up to and including the first one above 0.77 (all bins when none is)
-A frame is firm when m_acf >= 1e-4 (the fp32 bound on rho stated at acf4 in ofdm_sync.hip) and m_ifo >= 1e-5 (about ten times
+A frame is firm when m_acf >= 1e-4 (the fp32 bound on rho stated at acf4 in sync_core.hpp) and m_ifo >= 1e-5 (about ten times
 the suite's fp32 FFT bound per bin)."""
 from collections import namedtuple
 

@@ -4,7 +4,7 @@ test_gpu_channel_sync.py pins them at Nfft 1024 only.  Inputs: the first frame o
 from it, and its clean TX stream for remove_IFO.  The fp32 runs get the frame cast to complex64; the oracle always gets the
 complex128 frame (fine_sync: the same cast matrix on both sides, as test_fine_sync does).
 
-Bounds: rho 1e-11 (fp64) / 1e-4 (fp32, the bound stated at acf4 in ofdm_sync.hip), FreqOffset 1e-9 / 1e-6, remove_IFO and fine_sync
+Bounds: rho 1e-11 (fp64) / 1e-4 (fp32, the bound stated at acf4 in sync_core.hpp), FreqOffset 1e-9 / 1e-6, remove_IFO and fine_sync
 the bounds of test_remove_ifo / test_fine_sync (1024-point tests).  None was measured: all are inherited."""
 import warnings
 

@@ -1,6 +1,6 @@
 """Instruction and descriptor identity of the kernels two source trees have in common (CPU only).
 
-usage: python tools/asm_identity.py <old csrc dir> <new csrc dir> [file.hip ...]
+usage: python tools/asm_identity.py <old csrc dir> <new csrc dir> [file.hip | old1.hip,old2.hip=new1.hip,new2.hip ...]
 
 Each .hip file is compiled device-only to gfx950 assembly (hipcc -S, the library's flags) from both trees.  Every kernel
 of the old tree must have a twin in the new one with the same demangled name (an empty trailing template pack adds
@@ -51,14 +51,27 @@ def _kernels(text):
     return out
 
 
+def _pool(jobs, tree, names):
+    """The kernels of several files as one table; a kernel instantiated in two of them must be the same in both."""
+    pool = {}
+    for f in names:
+        for k, v in _kernels(jobs[tree, f].result()).items():
+            if pool.setdefault(k, v) != v:
+                sys.exit(f"{tree} {f}: {_demangle([k])[k]} differs from its instance in another file of the pool")
+    return pool
+
+
 def main():
     old, new, files = sys.argv[1], sys.argv[2], sys.argv[3:] or DEFAULT
+    # `a.hip,b.hip=a.hip,c.hip`: the kernels of the old files (left) pooled against those of the new files (right)
+    pairs = [tuple(side.split(",") for side in (f.split("=") if "=" in f else (f, f))) for f in files]
     bad = 0
     with tempfile.TemporaryDirectory() as td, cf.ThreadPoolExecutor(max_workers=8) as ex:
-        jobs = {(t, f): ex.submit(_asm, d, f, os.path.join(td, f"{t}_{f}.s")) for f in files for t, d in (("old", old), ("new", new))}
-        for f in files:
-            ko = _kernels(jobs["old", f].result())
-            kn = _kernels(jobs["new", f].result())
+        jobs = {(t, f): ex.submit(_asm, d, f, os.path.join(td, f"{t}_{f}.s"))
+                for t, d, i in (("old", old, 0), ("new", new, 1)) for p in pairs for f in p[i]}
+        for fo, fn in pairs:
+            f = ",".join(fn)
+            ko, kn = _pool(jobs, "old", fo), _pool(jobs, "new", fn)
             do, dn = _demangle(list(ko)), _demangle(list(kn))
             by_name = {dn[k]: k for k in kn}
             same = 0
