@@ -841,54 +841,36 @@ class RxPlan:
         sum(powers)) e^{2 pi i u} with u from Philox counter (t, 0, frame0 + f, 3), key `seed`.  want_taps adds
         taps=[n_frames, n_taps] complex128, those amplitudes.  With Time_Delay / Freq_Shift / want_draws too
         (ofdm_tx_frames_fading_ex): Noise -> add_STO -> add_CFO -> conv with the frame's own taps, the two per-frame draws
-        independent of each other."""
+        independent of each other.
+        The C entry: ofdm_tx_frames_fused, with fading ofdm_tx_frames_fading; given Time_Delay, Freq_Shift or want_draws their
+        _ex forms.  The plain entries launch no STO / CFO draw kernel and the channel pass without impairments."""
         n_frames = int(n_frames)
-        if fading is not None:
-            return self._tx_frames_fading(n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps, Time_Delay,
-                                          Freq_Shift, want_draws)
-        if want_taps:
+        fade = fading is not None
+        if fade:
+            keep_f, pdl, ppw, nt = self._fading_args(h, fading, "tx_frames_fused")
+            chan, name = (pdl, ppw, nt), "tx_frames_fading"
+        elif want_taps:
             raise OfdmError("tx_frames_fused: want_taps needs fading")
-        ex = Time_Delay is not None or Freq_Shift is not None or want_draws
-        scr = Register is not None
-        (rx, packed, scp, sto, cfo), ptrs, flags = self._outputs(
-            device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
-            ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bytes), np.uint8) if scr else None,
-            ((n_frames,), np.int64) if want_draws else None, ((n_frames,), np.float64) if want_draws else None)
-        keep, ph, nh, pr = self._fused_args(h, Register, "tx_frames_fused")
-        if ex:
-            sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
-            cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
-            L.check(self.lib.ofdm_tx_frames_fused_ex(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
-                                                     sm, int(sv), cm, float(cv), *ptrs, flags), "tx_frames_fused_ex")
-        else:                           # the entry without impairments launches no draw kernel and the plain channel pass
-            L.check(self.lib.ofdm_tx_frames_fused(self.handle, ph, nh, float(SNR), int(seed), int(frame0), n_frames, pr,
-                                                  *ptrs[:3], flags), "tx_frames_fused")
-        out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
-        if scr:
-            out["sc_packed"] = scp
-        if want_draws:
-            out["Time_Delay"], out["Freq_Shift"] = sto, cfo
-        return out
-
-    def _tx_frames_fading(self, n_frames, h, fading, SNR, seed, frame0, device, Register, want_taps, Time_Delay=None,
-                          Freq_Shift=None, want_draws=False):
-        keep_f, pdl, ppw, nt = self._fading_args(h, fading, "tx_frames_fused")
         ex = Time_Delay is not None or Freq_Shift is not None or want_draws
         scr = Register is not None
         (rx, packed, scp, taps, sto, cfo), ptrs, flags = self._outputs(
             device, ((n_frames, self.frame_samples), np.complex128 if self.f64 else np.complex64),
             ((n_frames, self.frame_bytes), np.uint8), ((n_frames, self.frame_bytes), np.uint8) if scr else None,
-            ((n_frames, nt), np.complex128) if want_taps else None, ((n_frames,), np.int64) if want_draws else None,
+            ((n_frames, nt), np.complex128) if fade and want_taps else None, ((n_frames,), np.int64) if want_draws else None,
             ((n_frames,), np.float64) if want_draws else None)
-        keep, _, _, pr = self._fused_args(None, Register, "tx_frames_fused")
+        keep, ph, nh, pr = self._fused_args(None if fade else h, Register, "tx_frames_fused")
+        if not fade:
+            chan, name = (ph, nh), "tx_frames_fused"
+        p_bits, p_taps, p_draws = ptrs[:3], ptrs[3:4] if fade else [], ptrs[4:]
         if ex:
             sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
             cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
-            L.check(self.lib.ofdm_tx_frames_fading_ex(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames,
-                                                      pr, sm, int(sv), cm, float(cv), *ptrs, flags), "tx_frames_fading_ex")
-        else:                           # without impairments: no STO / CFO draw kernel, the channel pass without them
-            L.check(self.lib.ofdm_tx_frames_fading(self.handle, pdl, ppw, nt, float(SNR), int(seed), int(frame0), n_frames,
-                                                   pr, *ptrs[:4], flags), "tx_frames_fading")
+            L.check(getattr(self.lib, f"ofdm_{name}_ex")(self.handle, *chan, float(SNR), int(seed), int(frame0), n_frames, pr,
+                                                         sm, int(sv), cm, float(cv), *p_bits, *p_taps, *p_draws, flags),
+                    f"{name}_ex")
+        else:
+            L.check(getattr(self.lib, f"ofdm_{name}")(self.handle, *chan, float(SNR), int(seed), int(frame0), n_frames, pr,
+                                                      *p_bits, *p_taps, flags), name)
         out = dict(rx=rx.t() if device is not None else rx.T, packed=packed)
         if scr:
             out["sc_packed"] = scp
@@ -938,19 +920,24 @@ class RxPlan:
                                                      sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
                                                      int(max_frames_per_chunk), *ptrs[:4], flags),
                     "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
-        out = dict(errors=err if device is not None else err.astype(np.int64), bits=fpp * self.frame_bits)
-        if want_nmse:
-            out["nmse_sums"] = ns
-            out["NMSE"] = ns / float(max(fpp, 1) * self.N_carrier)
-        if want_frame_nmse:
-            out["frame_nmse"] = fn
-        if want_frame_errors:
-            out["frame_errors"] = fe
-        if want_mer:
-            out["mer_sums"] = ms
-            out["MER_dB"] = _mer_db(ms)
-            if want_frame_mer:
-                out["frame_mer_sums"] = fm
+        return self._sweep_result(device, err, fpp, {}, ns, fn, fe, ms, fm)
+
+    def _sweep_result(self, device, errors, fpp, own, nmse_sums, frame_nmse, frame_errors, mer_sums, frame_mer_sums):
+        """What ber_sweep and ber_sweep_task4 return alike: the errors (int64 on the host), the bits per point, `own` (what only
+        one of them has), then each output that was wanted (None: not wanted) with the figures derived from it."""
+        out = dict(errors=errors if device is not None else errors.astype(np.int64), bits=fpp * self.frame_bits, **own)
+        if nmse_sums is not None:
+            out["nmse_sums"] = nmse_sums
+            out["NMSE"] = nmse_sums / float(max(fpp, 1) * self.N_carrier)
+        if frame_nmse is not None:
+            out["frame_nmse"] = frame_nmse
+        if frame_errors is not None:
+            out["frame_errors"] = frame_errors
+        if mer_sums is not None:
+            out["mer_sums"] = mer_sums
+            out["MER_dB"] = _mer_db(mer_sums)
+            if frame_mer_sums is not None:
+                out["frame_mer_sums"] = frame_mer_sums
         return out
 
     def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
@@ -1011,22 +998,8 @@ class RxPlan:
             L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
                                                      int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer, flags),
                     "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
-        host = device is None
-        out = dict(errors=err.astype(np.int64) if host else err, bits=fpp * self.frame_bits,
-                   status_counts=stc.astype(np.int64) if host else stc, cfo_abs_err=cae)
-        if want_nmse:
-            out["nmse_sums"] = ns
-            out["NMSE"] = ns / float(max(fpp, 1) * self.N_carrier)
-        if want_frame_nmse:
-            out["frame_nmse"] = fn
-        if want_frame_errors:
-            out["frame_errors"] = fe
-        if want_mer:
-            out["mer_sums"] = ms
-            out["MER_dB"] = _mer_db(ms)
-            if want_frame_mer:
-                out["frame_mer_sums"] = fm
-        return out
+        own = dict(status_counts=stc.astype(np.int64) if device is None else stc, cfo_abs_err=cae)
+        return self._sweep_result(device, err, fpp, own, ns, fn, fe, ms, fm)
 
     def set_timing(self, enable=True):
         L.check(self.lib.ofdm_rx_plan_set_timing(self.handle, int(bool(enable))), "rx_plan_set_timing")

@@ -126,7 +126,7 @@ inline T4Arena t4_arena_layout(const T4Shape& s, const T4Route& r, int64_t F) {
   return a;
 }
 
-// bytes per frame of that arena as the BER sweep budgets its chunks (ofdm_txfused.hip), the rho region of OFDM_T4_FULL_ACF not
+// bytes per frame of that arena as the BER sweep budgets its chunks (txf_chunk_task4, txf_plan.hpp), the rho region of OFDM_T4_FULL_ACF not
 // counted: the regions above (+ the per-frame scalars) and the frame's packed bits
 inline size_t t4_frame_bytes(const T4Shape& s, int frame_words) {
   const size_t cs = s.f64 ? 16 : 8;

@@ -1,0 +1,62 @@
+// What the BER sweeps (ofdm_ber_sweep.hip) use of the fused frame generator (ofdm_txfused.hip): the chunk buffers carved from
+// the plan-owned workspace and the generation of one chunk into them.  The decisions of a call are txf_plan.hpp's.
+#pragma once
+
+#include "rx_plan.hpp"
+#include "txf_plan.hpp"
+
+namespace ofdm {
+
+static_assert(TXF_DESCR_ON == DESCR_ON, "txf_plan.hpp restates DESCR_ON");
+
+int tx_dict_device(ofdm_rx_plan* pl);                // ofdm_txgen.hip
+
+// the Task-4 impairments of a generator call (T4/Main_model_Task_4.m:99-110): modes 0 off, 1 fixed, 2 drawn; the chunk's
+// per-frame draws are written to sto / cfo (nf entries each)
+struct TxfImp {
+  int sto_mode = 0;
+  int64_t sto_value = 0;
+  int cfo_mode = 0;
+  double cfo_value = 0;
+  int64_t* sto = nullptr;
+  double* cfo = nullptr;
+  TxfImp() = default;
+  TxfImp(int sm, int64_t sv, int cm, double cv) : sto_mode(sm), sto_value(sv), cfo_mode(cm), cfo_value(cv) {}
+};
+
+// a per-frame channel on the delay line of a TxfChannel (txf_fading), the amplitudes drawn per chunk
+struct TxfFade {
+  TxfGains gains;
+  c64* amp = nullptr;                                // the chunk's amplitudes [nf][n_taps] (tx_fade_draw_kernel)
+  c64* taps_out = nullptr;                           // generator: where the caller wants them (optional)
+};
+
+// chunk buffers inside the plan-owned workspace, one per region of txf_plan.hpp's table (null: the call has no such region)
+struct TxfBuffers {
+  void* tx = nullptr;
+  double* partial = nullptr;
+  uint8_t *b0 = nullptr, *b1 = nullptr;
+  void* rx = nullptr;
+  uint32_t* ref = nullptr;
+  int64_t* sto = nullptr;
+  double* cfo = nullptr;
+  c64* amp = nullptr;
+  void* hest = nullptr;
+};
+
+// what the checks of txf_plan.hpp read from a plan, and a refusal of theirs as the entry's return code and last-error text
+TxfShape txf_shape(const ofdm_rx_plan* pl);
+int txf_refused(int id, const TxfWhy& w);
+
+// grows pl->ws_txf to txf_layout(ch frames) and carves b from it
+int txf_workspace(ofdm_rx_plan* pl, int64_t ch, const TxfUse& u, TxfBuffers& b);
+
+// one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
+// imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
+// fade (optional): a channel per frame -- the draws into fade->amp (and fade->taps_out), the channel pass of
+// tx_channel_fade_kernel; with imp too, both draws and the channel pass of tx_channel_imp_fade_kernel
+int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf,
+                 const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
+                 const TxfImp* imp = nullptr, const TxfFade* fade = nullptr);
+
+}  // namespace ofdm

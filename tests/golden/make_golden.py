@@ -192,8 +192,31 @@ def t4_routes_parent():
     print(os.path.basename(path), "fields kept:", fields, os.path.getsize(path), "bytes")
 
 
+def txf_parent():
+    """tests/golden/txf_parent.json: every run of test_gpu_txf_parent.RUNS on the GPU, twice; a field is kept when it agrees
+    between the two runs in every run that has it.  As for t4_routes_parent, the library (OFDM_LIB_PATH) must be the build of the
+    commit before the generator's and the sweeps' call plan moved into txf_plan.hpp; run this from the present tree against it."""
+    import json
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    import ofdm_course_amd as ofdm
+    from test_gpu_txf_parent import FIELDS, RUNS, record, run_id
+    ofdm.init()
+    recs = [{run_id(r): record(ofdm, r) for r in RUNS} for _ in range(2)]
+    fields = [f for f in FIELDS if all(recs[0][n].get(f) == recs[1][n].get(f) for n in recs[0])]
+    path = os.environ.get("OFDM_GOLDEN_OUT", os.path.join(HERE, "txf_parent.json"))
+    with open(path, "w") as fh:
+        fh.write('{"fields": ' + json.dumps(fields) + ',\n "runs": {\n')
+        fh.write(",\n".join(f'  {json.dumps(n)}: {json.dumps({f: v for f, v in recs[0][n].items() if f in fields}, sort_keys=True, separators=(",", ":"))}'
+                            for n in sorted(recs[0])))
+        fh.write("\n }}\n")
+    print(os.path.basename(path), "fields kept:", fields, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    if "--chain-routes-parent" in sys.argv:
+    if "--txf-parent" in sys.argv:
+        txf_parent()
+    elif "--chain-routes-parent" in sys.argv:
         chain_routes_parent()
     elif "--t4-routes-parent" in sys.argv:
         t4_routes_parent()

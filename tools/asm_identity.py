@@ -18,7 +18,7 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=f
          "-Wno-pass-failed", "-Wno-logical-op-parentheses", "--cuda-device-only", "-S"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 DEFAULT = ["ofdm_chain.hip", "ofdm_chain_fast.hip", "ofdm_chain_wave.hip", "ofdm_chain_coop.hip", "ofdm_chain_split.hip",
-           "ofdm_txfused.hip"]
+           "ofdm_txfused.hip", "ofdm_ber_sweep.hip"]
 
 
 def _asm(csrc, name, out):
