@@ -253,6 +253,23 @@ int ofdm_rx_chain_task4_ex(ofdm_rx_plan* plan, const void* rx, int64_t n_frames,
                            int mp_desync, uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out,
                            int64_t* tg_position_out, double* freq_offset_out, int32_t* ifo_out, int32_t* status_out,
                            void* h_out, int64_t mer_skip, double* mer_sums_out /* [n_frames][2] */, int flags);
+/* ofdm_rx_chain_task4_ex that also returns a window of each frame's RX_IQ = get_payload(.)(:) -- the constellation the
+ * reference's drivers plot: scatterplot(RX_IQ(length(dataCarriers)+1 : 2*length(dataCarriers))) at
+ * T3/Main_model_Task_3.m:154 and T4/Main_model_Task_4.m:165, one scatter per SNR point in the fine-sync study of T4:137-203,
+ * and, with the three desync flags off, the unsynchronised constellations of the Task-3 figures (CFO / STO / multipath):
+ *   iq_out[n_frames][iq_count] (complex in the plan's precision, where `flags` says) = RX_IQ(iq_first .. iq_first + iq_count - 1)
+ *   (0-based) of each frame: the equalised point with fine_sync's rotation applied, exactly the value the demapper slices and
+ *   MER_func sums, element i = s * nd + (data index) of symbol s.
+ * The window may start anywhere, straddle symbol boundaries and end at nd * N_symb; OFDM_ERR_ARG unless 0 <= iq_first,
+ * 1 <= iq_count and iq_first + iq_count <= nd * N_symb (checked behind the plan / mer_skip checks of ofdm_rx_chain_task4_ex,
+ * before anything is launched).  Frames with status -1 / -2 are captured as they are decoded; a non-finite equaliser gives
+ * non-finite values, as the reference's RX_IQ would be.  iq_out = NULL is ofdm_rx_chain_task4_ex (the window is not looked
+ * at); every other output is that call's, bit for bit, whether or not iq_out is given. */
+int ofdm_rx_chain_task4_iq(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int time_desync, int freq_desync,
+                           int mp_desync, uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out,
+                           int64_t* tg_position_out, double* freq_offset_out, int32_t* ifo_out, int32_t* status_out,
+                           void* h_out, int64_t mer_skip, double* mer_sums_out /* [n_frames][2] */, int64_t iq_first,
+                           int64_t iq_count, void* iq_out /* [n_frames][iq_count] */, int flags);
 /* Synthetic RX frames of the plan's geometry, generated on the device (no host payload), per frame:
  *   payload (one Philox4x32-10 draw per QAM symbol, stream = frame0 + f)
  *   -> Scrambler with the register reset per frame (T5/Main_model_Task_5.m:55-69; scr_reg15 = HOST uint8[15], NULL = off)
@@ -464,6 +481,41 @@ int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, co
                                 double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
                                 double* nmse_sums_out /* [n_points] */,
                                 double* frame_nmse_out /* [n_points][frames_per_point] */, int flags);
+/* ofdm_ber_sweep_task4_nmse (static channel; all its arguments and outputs stay, each optional as there) with the
+ * constellation of every sweep point as a density accumulated on the device -- what the scatter per SNR point of
+ * T4/Main_model_Task_4.m:137-203 (:165) becomes when a point is a million frames: every decided point with IQ index >=
+ * scope_skip, of every frame of point p, is counted once in
+ *   density_out[n_points][bins][bins] (uint64, where `flags` says), at [p][row][col] with
+ *     scale = bins / (2 * half_width), computed once on the host in double,
+ *     col = clamp((int)floor((double(re) + half_width) * scale), 0, bins - 1),
+ *     row = the same from im;
+ *   the arithmetic is double in both precisions (one function bins on the device and on the host, csrc/scope_plan.hpp); a
+ *   point outside +-half_width lands in an edge bin; a point with non-finite re or im is not binned but counted in
+ *   density_dropped_out[n_points] (uint64, optional).  Therefore
+ *     sum(density[p]) + dropped[p] == frames_per_point * (nd * N_symb - scope_skip).
+ * The points are those of ofdm_rx_chain_task4_iq (RX_IQ = get_payload(.)(:), fine_sync's rotation applied; frames with
+ * status -1 / -2 as decoded).  scope_skip = Nfft + T_guard is RX_IQ(Nfft+T_Guard+1:end), the span of the study's MER (T4:163).
+ * Counts are integers summed with atomics: bitwise independent of max_frames_per_chunk, of the launch grid and of the order of
+ * arrival.  Refused with OFDM_ERR_ARG, behind every check of ofdm_ber_sweep_task4_nmse, in this order and before anything is
+ * launched or written: density_out == NULL (ofdm_ber_sweep_task4_nmse is the call without it); bins not 8, 16, 32, 64 or 128;
+ * half_width not finite or <= 0; scope_skip outside 0 .. nd * N_symb - 1; the equalise / demap stage's LDS with the grid
+ * (4 * bins^2 bytes behind its present regions) beyond the 150 KiB every stage is held to.
+ * The grids are zeroed on the launch stream before the first chunk.  With OFDM_DEVICE the accumulators are the caller's outputs
+ * and the call keeps the no-host-synchronisation rule of ofdm_ber_sweep_task4 (first-call growth of a small plan-owned buffer
+ * apart, which with OFDM_HOST holds the accumulators until they are copied out).  Every other output is
+ * ofdm_ber_sweep_task4_nmse's, bit for bit. */
+int ofdm_ber_sweep_task4_scope(ofdm_rx_plan* plan, const void* h, int h_len, int sto_mode, int64_t sto_value, int cfo_mode,
+                               double cfo_value, int time_desync, int freq_desync, int mp_desync, const double* snr_db,
+                               const uint64_t* seeds, int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                               const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                               uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
+                               int64_t mer_skip, double* mer_sums_out /* [n_points][2] */,
+                               double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
+                               double* nmse_sums_out /* [n_points] */,
+                               double* frame_nmse_out /* [n_points][frames_per_point] */,
+                               uint64_t* density_out /* [n_points][bins][bins] */,
+                               uint64_t* density_dropped_out /* [n_points], optional */, int bins, double half_width,
+                               int64_t scope_skip, int flags);
 /* Per-frame DeScrambler inside ofdm_rx_chain_task5 / ofdm_rx_chain_task4 (T5/DeScrambler.m:1-16 with
  * the register reset for every frame, T5/Main_model_Task_5.m:257-274, T4/Main_model_Task_4.m:354-364): the demapped bits
  * of a frame go through d[i] = s[i] ^ s[i-13] ^ s[i-14], s[-m] = reg15[m-1], before they are written to bits_out and

@@ -75,6 +75,8 @@ SIGNATURES = {
     "ofdm_rx_plan_get_omp_route": [_vp, _pi, _pi],
     "ofdm_rx_chain_task4": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_rx_chain_task4_ex": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i],
+    "ofdm_rx_chain_task4_iq": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp,
+                               _i],
     "ofdm_tx_frames": [_vp, _vp, _i, _d, _i, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _i],
     "ofdm_tx_frames_ex": [_vp, _vp, _i, _d, _i, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_rx_plan_set_descrambler": [_vp, _vp],
@@ -101,6 +103,8 @@ SIGNATURES = {
                                  _vp, _i],
     "ofdm_ber_sweep_task4_nmse": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp,
                                   _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i],
+    "ofdm_ber_sweep_task4_scope": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp,
+                                   _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i, _d, _i64, _i],
     "ofdm_ber_sweep_task4_fading": [_vp, _vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp,
                                     _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i],
 }

@@ -943,7 +943,7 @@ class RxPlan:
     def ber_sweep_task4(self, SNRs, frames_per_point, h=None, Time_Delay=None, Freq_Shift=None, time_desync=None,
                         freq_desync=None, mp_desync=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                         want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, mer_skip=0,
-                        want_frame_mer=False, fading=None, want_nmse=False, want_frame_nmse=False):
+                        want_frame_mer=False, fading=None, want_nmse=False, want_frame_nmse=False, density=None):
         """One device-resident tile of a BER(SNR) sweep of the Task-4 receiver (ofdm_ber_sweep_task4): for every SNR of
         `SNRs` the frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p], Time_Delay,
         Freq_Shift) decoded by rx_chain_task4(time_desync, freq_desync, mp_desync) on this plan.  A desync flag left at None
@@ -965,9 +965,25 @@ class RxPlan:
         channel, and NMSE=[n] = nmse_sums / (frames_per_point * N_carrier) (T4/Main_model_Task_4.m:205-239); with
         want_frame_nmse the per-frame sums frame_nmse=[n, frames_per_point].  The plain difference of the reference: with
         time_desync / freq_desync on, fine_sync has taken the channel's mean delay and common phase out of what
-        estimate_channel sees, and the difference contains that ramp."""
+        estimate_channel sees, and the difference contains that ramp.
+        density=dict(bins=, half_width=, skip=0) (ofdm_ber_sweep_task4_scope; not with fading): also density=[n, bins, bins]
+        int64, per point the count of its frames' equalised points RX_IQ (those of rx_chain_task4(iq_window=), from 0-based
+        index skip on) at [row of im, column of re] with col = clamp(floor((re + half_width) * bins / (2 half_width)), 0,
+        bins - 1), and density_dropped=[n], the points with a non-finite coordinate, which are not binned: sum(density[p]) +
+        density_dropped[p] = frames_per_point * (nd * N_symb - skip).  The constellation per SNR point of
+        T4/Main_model_Task_4.m:137-203 (:165) at sweep sizes."""
         if want_frame_nmse and not want_nmse:
             raise OfdmError("ber_sweep_task4: want_frame_nmse needs want_nmse")
+        if density is not None:
+            if fading is not None:
+                raise OfdmError("ber_sweep_task4: density is not available with fading")
+            try:
+                extra = set(density) - {"bins", "half_width", "skip"}
+                bins, half_width, skip = int(density["bins"]), float(density["half_width"]), int(density.get("skip", 0))
+            except (TypeError, KeyError, ValueError, AttributeError):
+                raise OfdmError("ber_sweep_task4: density must be dict(bins=, half_width=, skip=0)") from None
+            if extra:
+                raise OfdmError(f"ber_sweep_task4: unknown density keys {sorted(extra)}")
         snr, sd = self._points(SNRs, seeds, seed, "ber_sweep_task4")
         n, fpp = snr.size, int(frames_per_point)
         sm, sv = _imp_mode(Time_Delay, "ber_sweep_task4")
@@ -982,7 +998,16 @@ class RxPlan:
             ((n, fpp), np.float64) if want_frame_nmse else None)
         tail = (snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0))
         mer = (int(mer_skip) if want_mer else 0, *ptrs[4:6])
-        if fading is not None:
+        dens = None
+        if density is not None:
+            nb = bins if bins > 0 else 0                          # (a bad count is the library's refusal)
+            (dens, drop), dptrs, _ = self._outputs(device, ((n, nb, nb), np.uint64), ((n,), np.uint64))
+            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
+            L.check(self.lib.ofdm_ber_sweep_task4_scope(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
+                                                        int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer,
+                                                        *ptrs[6:], *dptrs, bins, half_width, skip, flags),
+                    "ber_sweep_task4_scope")
+        elif fading is not None:
             keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep_task4")
             keep, _, _, pr = self._fused_args(None, Register, "ber_sweep_task4")
             L.check(self.lib.ofdm_ber_sweep_task4_fading(self.handle, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(td),
@@ -999,6 +1024,9 @@ class RxPlan:
                                                      int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer, flags),
                     "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
         own = dict(status_counts=stc.astype(np.int64) if device is None else stc, cfo_abs_err=cae)
+        if dens is not None:                                      # int64 views: a count of 2^63 is out of reach
+            own.update(density=dens if device is not None else dens.view(np.int64),
+                       density_dropped=drop if device is not None else drop.view(np.int64))
         return self._sweep_result(device, err, fpp, own, ns, fn, fe, ms, fm)
 
     def set_timing(self, enable=True):
@@ -1067,7 +1095,7 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
 
 
 def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, ref_bits_packed=None, want_h=False,
-                   want_mer=False, mer_skip=0):
+                   want_mer=False, mer_skip=0, iq_window=None):
     """Task-4 receiver over a batch of frames (T4/Main_model_Task_4.m:278-347 per frame): AutoCorrFunction -> add_STO x2 ->
     add_CFO -> remove_IFO -> OFDM_demodulator -> fine_sync -> estimate_channel -> equalize_signal -> get_payload -> demapping.
 
@@ -1077,11 +1105,19 @@ def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, 
     (0 ok, 1 AutoCorrFunction fallback, -1 no IFO line, -2 TgPosition out of range), H=[N_carrier, n_frames] or None).
     want_mer (ofdm_rx_chain_task4_ex): also mer_sums=[n_frames, 2] float64, the sums {|ideal|^2, |ideal - RX_IQ|^2} of
     MER_func (T5/MER_func.m:3-25) over each frame's get_payload(.)(:) from 0-based index mer_skip on (Nfft + T_guard =
-    RX_IQ(Nfft+T_Guard+1:end) of T4/Main_model_Task_4.m:163), and MER_dB=[n_frames] = 10 log10(s1 / s2)."""
+    RX_IQ(Nfft+T_Guard+1:end) of T4/Main_model_Task_4.m:163), and MER_dB=[n_frames] = 10 log10(s1 / s2).
+    iq_window=(first, count) (ofdm_rx_chain_task4_iq): also RX_IQ=[n_frames, count] complex in the plan's precision, the
+    equalised points get_payload(.)(:) of each frame from 0-based index first on -- what the demapper slices and MER_func sums;
+    (nd, nd) is the scatterplot(RX_IQ(length(dataCarriers)+1 : 2*length(dataCarriers))) of T4/Main_model_Task_4.m:165."""
     call = _Call(rx, f64=plan.f64)
     rows, nfr = _shape2(rx)
     if rows != plan.frame_samples:
         raise OfdmError("rx_chain_task4: rx must have (Nfft+T_guard)*N_symb rows")
+    if iq_window is not None:
+        try:
+            iq_first, iq_count = (int(v) for v in iq_window)
+        except (TypeError, ValueError):
+            raise OfdmError("rx_chain_task4: iq_window must be (first, count)") from None
     flat_bits, pbits = call._out((plan.frame_bytes * nfr,), np.uint8, torch.uint8 if call.dev else None)
     bits = flat_bits.reshape(nfr, plan.frame_bytes)
     pref, errors, perr = None, None, None
@@ -1097,18 +1133,28 @@ def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, 
     ifo, pifo = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
-    if not want_mer:
+    if not want_mer and iq_window is None:
         L.check(call.lib.ofdm_rx_chain_task4(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
                                              int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, call.flags),
                 "rx_chain_task4")
         return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
-    mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
-    mer = mer.T
-    L.check(call.lib.ofdm_rx_chain_task4_ex(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
-                                            int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, int(mer_skip),
-                                            pmer, call.flags), "rx_chain_task4_ex")
-    return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H, mer_sums=mer,
-                MER_dB=_mer_db(mer))
+    out = dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
+    mer, pmer = None, None
+    if want_mer:
+        mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
+        mer = mer.T
+        out.update(mer_sums=mer)
+    head = (plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)), int(bool(mp_desync)), pbits, pref,
+            perr, ptg, pfo, pifo, pst, pH, int(mer_skip) if want_mer else 0, pmer)
+    if iq_window is None:
+        L.check(call.lib.ofdm_rx_chain_task4_ex(*head, call.flags), "rx_chain_task4_ex")
+    else:
+        iq, piq = call.cout((max(iq_count, 0), nfr))                                      # memory [n_frames][count]
+        L.check(call.lib.ofdm_rx_chain_task4_iq(*head, iq_first, iq_count, piq, call.flags), "rx_chain_task4_iq")
+        out.update(RX_IQ=iq.T)
+    if want_mer:
+        out.update(MER_dB=_mer_db(mer))
+    return out
 
 
 def _mer_db(sums):

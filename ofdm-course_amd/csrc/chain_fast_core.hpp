@@ -720,11 +720,24 @@ inline int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route 
   return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, lay, by_fft, F);
 }
 
+// constellation capture of one eq_demap_run call (the SCOPE variant of eq_demap_kernel; checked by scope_plan.hpp's functions):
+// iq != null: the window iq_first .. iq_first + iq_count - 1 of every frame's points -> iq[n_frames][iq_count];
+// bins != 0: the points from IQ index skip on counted into density[bins][bins] (non-finite ones in *dropped), both device
+// accumulators that the caller has zeroed
+struct ScopeCall {
+  int64_t iq_first = 0, iq_count = 0;
+  void* iq = nullptr;
+  int bins = 0;
+  int64_t skip = 0;
+  double half_width = 0.0, scale = 0.0;
+  unsigned long long *density = nullptr, *dropped = nullptr;
+};
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,
                  void* bits, const void* ref, void* errs, void* h_out, void* idx_out, const double* fine_est, int time_desync,
                  int freq_desync, int mer_skip = 0,
-                 double* mer_sums = nullptr /* [n_frames][2]: MER variant */);                        // ofdm_chain_split.hip
+                 double* mer_sums = nullptr /* [n_frames][2]: MER variant */,
+                 const ScopeCall* scope = nullptr /* SCOPE variant */);                               // ofdm_chain_split.hip
 
 // ofdm_chain_mmse.hip: the MMSE estimator of a plan as one operator W^T [np][m_pad] and its batched application
 int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t* pilot_loc, int np, int n_carrier,

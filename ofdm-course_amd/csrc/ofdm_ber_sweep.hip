@@ -20,9 +20,12 @@
 #include <algorithm>
 #include <cmath>
 
+#include "scope_plan.hpp"
 #include "txf_generate.hpp"
 
 namespace ofdm {
+
+int scope_refused(int id, const ScopeWhy& w);                     // ofdm_chain_t4.hip
 
 // the taps of a static channel (host doubles in the kernel arguments) -> device memory, for t5_frame_nmse_kernel
 struct TxfAmps {
@@ -318,6 +321,12 @@ struct T4SweepArgs {
   uint64_t* status_counts_out;
   double* cfo_abs_err_out;
   double *nmse_sums_out, *frame_nmse_out;
+  // ofdm_ber_sweep_task4_scope: the constellation density of every point
+  bool scope = false;
+  int bins = 0;
+  double half_width = 0.0;
+  int64_t scope_skip = 0;
+  uint64_t *density_out = nullptr, *dropped_out = nullptr;
 };
 
 // the body of the Task-4 sweep entries: the checks of txf_task4_prelude, then c's static channel, or the delay line of a
@@ -331,6 +340,11 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   TxfChannel ch;
   TxfFade fade;
   OFDM_TRY(txf_sweep_prelude(pl, c, s, errors_out, flags, txf_task4_prelude, ch, fade));
+  if (a.scope) {                                                // behind every check of the entry without a density
+    ScopeWhy why;
+    OFDM_TRY(scope_refused(scope_density_check(a.density_out != nullptr, a.bins, a.half_width, a.scope_skip, s.f64 != 0,
+                                               s.n_carrier, (int64_t)s.nd * s.n_symb, why), why));
+  }
   const TxfPoints pt{c.snr_db, c.seeds, c.n_points, c.n_frames, c.frame0};
   const int64_t n_points = pt.n_points, frames_per_point = pt.frames_per_point;
   if (n_points == 0) return OFDM_OK;
@@ -345,10 +359,42 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   OFDM_TRY(st.out(a.nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
   OFDM_TRY(st.out(a.frame_nmse_out, sizeof(double) * (size_t)NF, &dfn));
   hipStream_t stream = ctx().stream;
+  // The density grids [n_points][bins][bins] and the dropped counters [n_points] are accumulators of eq_demap_kernel's global
+  // atomics: the caller's device outputs themselves; host outputs, and dropped counters nobody asked for, in a buffer of the
+  // plan's own (pl->ws_scope -- not the generator workspace, whose regions are per chunk).  Zeroed on the launch stream
+  // before the first chunk; host outputs are copied back in front of st.finish()'s synchronisation.
+  const size_t grid_elems = (size_t)a.bins * (size_t)a.bins;
+  unsigned long long *ddens = nullptr, *ddrop = nullptr;
+  const bool scope_dev = st.device_mode();
+  if (a.scope) {
+    const size_t own = sizeof(uint64_t) * (scope_dev ? (a.dropped_out ? 0 : (size_t)n_points) : (size_t)n_points * (grid_elems + 1));
+    if (pl->ws_scope_bytes < own) {
+      OFDM_HIP(hipStreamSynchronize(stream));
+      if (pl->ws_scope) { (void)hipFree(pl->ws_scope); pl->ws_scope = nullptr; pl->ws_scope_bytes = 0; }
+      OFDM_HIP(hipMalloc(&pl->ws_scope, own));
+      pl->ws_scope_bytes = own;
+    }
+    if (scope_dev) {
+      ddens = (unsigned long long*)a.density_out;
+      ddrop = a.dropped_out ? (unsigned long long*)a.dropped_out : (unsigned long long*)pl->ws_scope;
+    } else {
+      ddens = (unsigned long long*)pl->ws_scope;
+      ddrop = ddens + (size_t)n_points * grid_elems;
+    }
+    OFDM_HIP(hipMemsetAsync(ddens, 0, sizeof(uint64_t) * (size_t)n_points * grid_elems, stream));
+    OFDM_HIP(hipMemsetAsync(ddrop, 0, sizeof(uint64_t) * (size_t)n_points, stream));
+  }
+  auto scope_finish = [&]() -> int {
+    if (!a.scope || scope_dev) return OFDM_OK;
+    OFDM_HIP(hipMemcpyAsync(a.density_out, ddens, sizeof(uint64_t) * (size_t)n_points * grid_elems, hipMemcpyDeviceToHost, stream));
+    if (a.dropped_out) OFDM_HIP(hipMemcpyAsync(a.dropped_out, ddrop, sizeof(uint64_t) * (size_t)n_points, hipMemcpyDeviceToHost, stream));
+    return OFDM_OK;
+  };
   if (frames_per_point == 0) {
     if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, stream));
     if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, stream));
     if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, stream));
+    OFDM_TRY(scope_finish());
     return st.finish();
   }
   // the per-frame values of every point, reduced once after the last chunk
@@ -386,11 +432,18 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   }
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, &imp, c.fading ? &fade : nullptr, u,
                             [&](const TxfBuffers& b, int64_t nf, int64_t k) {
-                              OFDM_TRY(ofdm_rx_chain_task4_ex(pl, b.rx, nf, a.time_desync, a.freq_desync, a.mp_desync, nullptr,
-                                                              (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
-                                                              (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
-                                                              b.hest, c.mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
-                                                              rxflags));
+                              ScopeCall sc;                     // a chunk holds frames of one point: one grid per receiver call
+                              if (a.scope) {
+                                const int64_t p = k / frames_per_point;
+                                sc.bins = a.bins; sc.skip = a.scope_skip; sc.half_width = a.half_width;
+                                sc.scale = scope_scale(a.bins, a.half_width);
+                                sc.density = ddens + (size_t)p * grid_elems; sc.dropped = ddrop + p;
+                              }
+                              OFDM_TRY(rx_chain_task4_run(pl, b.rx, nf, a.time_desync, a.freq_desync, a.mp_desync, nullptr,
+                                                          (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
+                                                          (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
+                                                          b.hest, c.mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
+                                                          a.scope ? &sc : nullptr, rxflags));
                               if (!dfn) return (int)OFDM_OK;
                               return txf_frame_nmse(pl, c.fading ? (const c64*)b.amp : (const c64*)dstatic, b.hest, dl,
                                                     c.fading ? n_taps : 0, nf, (double*)dfn + k);
@@ -401,6 +454,7 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   OFDM_TRY(check_launch("t4_point_reduce_kernel"));
   OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
   OFDM_TRY(txf_point_sums<1>(dfn, n_points, frames_per_point, dns));
+  OFDM_TRY(scope_finish());
   return st.finish();
 }
 
@@ -449,6 +503,25 @@ extern "C" int ofdm_ber_sweep_task4_nmse(ofdm_rx_plan* pl, const void* h, int h_
   return t4_sweep(pl, c, T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
                                      status_counts_out, cfo_abs_err_out, nmse_sums_out, frame_nmse_out},
                   errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, flags);
+}
+
+extern "C" int ofdm_ber_sweep_task4_scope(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
+                                          int cfo_mode, double cfo_value, int time_desync, int freq_desync, int mp_desync,
+                                          const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                          int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                          int64_t max_frames_per_chunk, uint64_t* errors_out, uint64_t* status_counts_out,
+                                          double* cfo_abs_err_out, uint32_t* frame_errors_out, int64_t mer_skip,
+                                          double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
+                                          double* frame_nmse_out, uint64_t* density_out, uint64_t* density_dropped_out, int bins,
+                                          double half_width, int64_t scope_skip, int flags) {
+  TxfCall c = TxfCall("ber_sweep_task4", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
+                  .with_imp(sto_mode, cfo_mode).with_points(snr_db, seeds, n_points, max_frames_per_chunk);
+  c.mer_skip = mer_skip;
+  T4SweepArgs a{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
+                status_counts_out, cfo_abs_err_out, nmse_sums_out, frame_nmse_out};
+  a.scope = true; a.bins = bins; a.half_width = half_width; a.scope_skip = scope_skip;
+  a.density_out = density_out; a.dropped_out = density_dropped_out;
+  return t4_sweep(pl, c, a, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "chain_fast_core.hpp"
+#include "scope_plan.hpp"
 
 namespace ofdm {
 
@@ -40,10 +41,50 @@ __global__ __launch_bounds__(256) void pilot_ls_kernel(FastParams<T> P, const cx
 // order of get_payload(:)), in double; wave butterfly, then the four wave partials in index order -> mer.sums[f] = {s1, s2}.
 // No atomics: the sums do not depend on the grid or the batching.  An empty Mer is the kernel as it always was (same
 // arguments, same instructions).
+// SCOPE (a ScopeOut in the pack, eq_demap_run with a ScopeCall): constellation capture of the same points ye, by IQ index.
+//   IQ window: ye stored to iq[f][i - iq_first] for iq_first <= i < iq_first + iq_count.
+//   Density: a bins x bins uint32 grid in dynamic LDS behind the codes (lds_off), zeroed once per workgroup and kept across
+//   its frames; per point with i >= skip one LDS atomicAdd at (row of im, column of re) (scope_bin, scope_plan.hpp), a
+//   non-finite point counted in a register instead; after the workgroup's last frame one 64-bit global atomicAdd per non-zero
+//   bin and one per wavefront with dropped points.  Integers: the result does not depend on the grid, the batching or the
+//   order of arrival.  A uint32 bin cannot wrap: the workgroup flushes its grid early, before the points it has counted
+//   since the last flush and the next frame's n_codes together could exceed 2^32 - 1.
+// The pack holds a MerOut, a ScopeOut, both (in that order) or nothing; without a ScopeOut the kernel is the build it was.
 struct MerOut {
   int skip;
   double* sums;                                                        // [n_frames][2]
 };
+struct ScopeOut {
+  int iq_first, iq_count;                                              // the window (iq null: none)
+  void* iq;                                                            // [n_frames][iq_count] cx<T>
+  int bins, skip;                                                      // bins 0: no density
+  double half_width, scale;
+  unsigned lds_off;                                                    // the grid's byte offset in dynamic LDS
+  unsigned long long* density;                                         // [bins][bins] of the call's sweep point
+  unsigned long long* dropped;                                         // its counter of non-finite points
+};
+template <typename E> struct is_mer_out : std::false_type {};
+template <> struct is_mer_out<MerOut> : std::true_type {};
+template <typename E> struct is_scope_out : std::false_type {};
+template <> struct is_scope_out<ScopeOut> : std::true_type {};
+__device__ __forceinline__ void ext_take(const MerOut& m, MerOut& mo, ScopeOut&) { mo = m; }
+__device__ __forceinline__ void ext_take(const ScopeOut& s, MerOut&, ScopeOut& so) { so = s; }
+
+// one decided point ye of IQ index i: the window store, and the grid count or the thread's dropped count
+template <typename T>
+__device__ __forceinline__ void scope_point(const ScopeOut& sc, cx<T>* __restrict__ iq_frame, uint32_t* __restrict__ grid,
+                                            unsigned& dropped, int i, cx<T> ye) {
+  if (iq_frame) {
+    const int w = i - sc.iq_first;
+    if ((unsigned)w < (unsigned)sc.iq_count) iq_frame[w] = ye;
+  }
+  if (sc.bins && i >= sc.skip) {
+    const int col = scope_bin((double)ye.x, sc.half_width, sc.scale, sc.bins);
+    const int row = scope_bin((double)ye.y, sc.half_width, sc.scale, sc.bins);
+    if (col < 0 || row < 0) ++dropped;
+    else atomicAdd(&grid[row * sc.bins + col], 1u);
+  }
+}
 
 template <typename T, int BA, bool HEXT, bool VEC = false, typename... Mer>
 __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft, const cx<T>* __restrict__ xk,
@@ -53,10 +94,14 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
                                                        int32_t* __restrict__ index_out, DemapTable<T> tab,
                                                        const double* __restrict__ fine_est /* [n_frames][2] or null */,
                                                        int time_desync, int freq_desync, Mer... mer) {
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = (is_mer_out<Mer>::value || ...);
+  constexpr bool SCOPE = (is_scope_out<Mer>::value || ...);
   int mer_skip = 0;
   double* mer_sums = nullptr;
-  if constexpr (MER) ((mer_skip = mer.skip, mer_sums = mer.sums), ...);
+  MerOut mo{};
+  ScopeOut sc{};
+  (ext_take(mer, mo, sc), ...);
+  if constexpr (MER) { mer_skip = mo.skip; mer_sums = mo.sums; }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // fine_est: the residual timing / phase estimates of fine_sync (tau, phase) per frame; its rotation
   // exp(j (2 pi tau k + phase)) (fine_sync.m:36-43) is applied to every sample as it is read, with the rounding of the
@@ -78,10 +123,34 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
   const int n_codes = nd * P.n_symb;
   const int n_groups = (n_codes + 31) >> 5;
   if (gid < 32) codes[((n_codes + 31) & ~31) - 32 + gid] = 0;          // zero padding of the last 32-symbol group
+  uint32_t* grid = nullptr;                                            // SCOPE: the density grid, this thread's dropped points,
+  unsigned sc_dropped = 0;                                             // and the points counted since the last flush
+  unsigned long long sc_pending = 0;
+  if constexpr (SCOPE) {
+    grid = (uint32_t*)(smem + sc.lds_off);
+    for (int i = gid; i < sc.bins * sc.bins; i += 256) grid[i] = 0;
+  }
+  auto scope_flush = [&]() {                                           // (behind a barrier: every count of the frames so far is in)
+    for (int i = gid; i < sc.bins * sc.bins; i += 256) {
+      const uint32_t v = grid[i];
+      if (v) { atomicAdd(&sc.density[i], (unsigned long long)v); grid[i] = 0; }
+    }
+  };
   __syncthreads();
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     if (gid == 0) sh_err = 0;
     double s1 = 0, s2 = 0;                                            // MER sums of this thread's samples
+    cx<T>* iq_frame = nullptr;
+    if constexpr (SCOPE) {
+      if (sc.iq) iq_frame = (cx<T>*)sc.iq + f * sc.iq_count;
+      if (sc.bins) {                                                   // workgroup-uniform
+        if (sc_pending + (unsigned long long)n_codes > 0xffffffffull) {
+          scope_flush();                                               // (the previous frame ended on a barrier)
+          sc_pending = 0;
+        }
+        sc_pending += (unsigned long long)n_codes;
+      }
+    }
     if (!HEXT && gid < taps) {
       const int idx = P.tap_idx[f * taps + gid];
       sh_tidx[gid] = idx;
@@ -194,6 +263,10 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
                   if (cinc[u][0] && ci[u][0] + (s0 + v) * nd >= mer_skip) mer_add(sh_pts[(uint8_t)c0], y0, s1, s2);
                   if (cinc[u][1] && ci[u][1] + (s0 + v) * nd >= mer_skip) mer_add(sh_pts[(uint8_t)c1], y1, s1, s2);
                 }
+                if constexpr (SCOPE) {
+                  if (cinc[u][0]) scope_point<T>(sc, iq_frame, grid, sc_dropped, ci[u][0] + (s0 + v) * nd, y0);
+                  if (cinc[u][1]) scope_point<T>(sc, iq_frame, grid, sc_dropped, ci[u][1] + (s0 + v) * nd, y1);
+                }
               }
             }
         }
@@ -228,6 +301,7 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
                 codes[(s0 + v) * nd + dv[u]] = (uint8_t)code;
                 if constexpr (MER)
                   if ((s0 + v) * nd + dv[u] >= mer_skip) mer_add(sh_pts[(uint8_t)code], ye, s1, s2);
+                if constexpr (SCOPE) scope_point<T>(sc, iq_frame, grid, sc_dropped, (s0 + v) * nd + dv[u], ye);
               }
         }
       }
@@ -254,6 +328,14 @@ __global__ __launch_bounds__(256) void eq_demap_kernel(FastParams<T> P, int nfft
       if (gid == 0) errors_out[f] = sh_err;
     }
     __syncthreads();
+  }
+  if constexpr (SCOPE) {
+    if (sc.bins) {                                                     // (the last frame ended on a barrier; a workgroup without
+      scope_flush();                                                   //  frames adds nothing)
+      unsigned long long d = sc_dropped;
+      for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+      if ((gid & 63) == 0 && d) atomicAdd(sc.dropped, d);
+    }
   }
 }
 
@@ -609,11 +691,19 @@ static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>&
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,
                  void* bits, const void* ref, void* errs, void* h_out, void* idx_out, const double* fine_est, int time_desync,
-                 int freq_desync, int mer_skip, double* mer_sums) {
+                 int freq_desync, int mer_skip, double* mer_sums, const ScopeCall* scope) {
   hipStream_t st = ctx().stream;
   DemapTable<T> tab;
   fill_demap_table<T>(*pv.dict, *pv.cinfo, tab);
-  const size_t dyn = eq_demap_lds_bytes(std::is_same<T, double>::value, pv.n_carrier, (int64_t)pv.nd * pv.n_symb);
+  constexpr bool f64 = std::is_same<T, double>::value;
+  const int64_t decisions = (int64_t)pv.nd * pv.n_symb;
+  // with a density the grid lies behind the stage's regions (scope_plan.hpp; the entry has checked the total before any launch)
+  const size_t dyn = scope && scope->bins ? scope_stage_lds(f64, pv.n_carrier, decisions, scope->bins)
+                                          : eq_demap_lds_bytes(f64, pv.n_carrier, decisions);
+  ScopeOut so{};
+  if (scope)
+    so = ScopeOut{(int)scope->iq_first, (int)scope->iq_count, scope->iq, scope->bins, (int)scope->skip, scope->half_width,
+                  scope->scale, (unsigned)scope_grid_offset(f64, pv.n_carrier, decisions), scope->density, scope->dropped};
   const bool vec = eq_demap_vec_ok(std::is_same<T, double>::value, pv.n_carrier, x_stride);
   OFDM_ARG(dyn <= 150 * 1024, "rx_chain: equalise / demap stage needs %zu bytes of LDS", dyn);
   auto grid_of = [&](const void* kern) {
@@ -633,11 +723,26 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
                        time_desync, freq_desync, MerOut{mer_skip, mer_sums});
     return OFDM_OK;
   };
+  auto launch_ext = [&](auto kern, auto... ext) -> int {       // the capture variants: + the MER sums and / or the ScopeOut
+    hipLaunchKernelGGL(kern, dim3(grid_of((const void*)kern)), dim3(256), dyn, st, P, pv.nfft, xk, x_stride, n_frames,
+                       (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<T>*)h_out, (int32_t*)idx_out, tab, fine_est,
+                       time_desync, freq_desync, ext...);
+    return OFDM_OK;
+  };
   const int ba = pv.cinfo->kind == 1 ? pv.cinfo->bits_per_axis : 0;
   OFDM_TRY(with_ba(ba, [&](auto BA) {
     return with_bool(hext, [&](auto HX) {
       constexpr int B = decltype(BA)::value;
       constexpr bool H = decltype(HX)::value;
+      if (scope) {
+        const MerOut mo{mer_skip, mer_sums};
+        if constexpr (std::is_same<T, float>::value) {
+          if (vec) return mer_sums ? launch_ext(eq_demap_kernel<T, B, H, true, MerOut, ScopeOut>, mo, so)
+                                   : launch_ext(eq_demap_kernel<T, B, H, true, ScopeOut>, so);
+        }
+        return mer_sums ? launch_ext(eq_demap_kernel<T, B, H, false, MerOut, ScopeOut>, mo, so)
+                        : launch_ext(eq_demap_kernel<T, B, H, false, ScopeOut>, so);
+      }
       if constexpr (std::is_same<T, float>::value) {                 // (fp64 has no VEC build)
         if (vec) return mer_sums ? launch_mer(eq_demap_kernel<T, B, H, true, MerOut>) : launch(eq_demap_kernel<T, B, H, true>);
       }
@@ -647,9 +752,9 @@ int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk
   return check_launch("eq_demap_kernel");
 }
 template int eq_demap_run<float>(const FastPlanView&, const FastParams<float>&, const cx<float>*, int, bool, int64_t, void*,
-                                 const void*, void*, void*, void*, const double*, int, int, int, double*);
+                                 const void*, void*, void*, void*, const double*, int, int, int, double*, const ScopeCall*);
 template int eq_demap_run<double>(const FastPlanView&, const FastParams<double>&, const cx<double>*, int, bool, int64_t, void*,
-                                  const void*, void*, void*, void*, const double*, int, int, int, double*);
+                                  const void*, void*, void*, void*, const double*, int, int, int, double*, const ScopeCall*);
 
 template <typename T>
 static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,

@@ -2,6 +2,7 @@
 // which runs the stages the route of t4_route.hpp names.
 #include <algorithm>
 
+#include "scope_plan.hpp"
 #include "spline_op.hpp"
 #include "sync_core.hpp"
 #include "t4_route.hpp"
@@ -540,6 +541,7 @@ struct T4Call {
   void* bits; const void* ref; void* errs; void* h_out;
   int64_t* tg; double* fo; int32_t* ifo; int32_t* stat;
   int mer_skip; double* mer;
+  const ScopeCall* scope;               // constellation capture (IQ window / density), or null
   int64_t *res, *first;
   double *resv, *est;
   cx<T> *y, *X, *hp, *H, *Xp, *rho, *seg, *spec;
@@ -704,7 +706,8 @@ static int t4_equalise_stage(const T4Call<T>& c) {
   void* craw = nullptr;
   if (descr_pass) OFDM_TRY(descr_raw_workspace(pl, c.F, &craw));
   OFDM_TRY(eq_demap_run<T>(pv, P, (const cx<T>*)c.X, c.r.x_stride, true, c.F, descr_pass ? craw : c.bits, descr_pass ? nullptr : c.ref,
-                           descr_pass ? nullptr : c.errs, c.h_out, nullptr, c.rot, c.s.time_desync, c.s.freq_desync, c.mer_skip, c.mer));
+                           descr_pass ? nullptr : c.errs, c.h_out, nullptr, c.rot, c.s.time_desync, c.s.freq_desync, c.mer_skip, c.mer,
+                           c.scope));
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, c.bits, c.ref, c.errs, c.F));
   return OFDM_OK;
 }
@@ -712,7 +715,7 @@ static int t4_equalise_stage(const T4Call<T>& c) {
 template <typename T>
 static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
                      void* dbits, const void* dref, void* derr, int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat,
-                     void* dh_out, int mer_skip, double* dmer) {
+                     void* dh_out, int mer_skip, double* dmer, const ScopeCall* scope) {
   T4Call<T> c{};
   c.pl = pl; c.F = F;
   c.s = T4Shape{pl->nfft, pl->t_guard, pl->n_symb, pl->n_carrier, pl->np, pl->f64, time_desync, freq_desync, mp_desync, pl->f64 ? 0 : 1};
@@ -737,7 +740,7 @@ static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desy
   c.pil = c.r.pilots_compact ? c.Xp : c.X;
   c.rot = c.r.lazy_rot ? c.est : nullptr;
   c.rx = (const cx<T>*)drx; c.bits = dbits; c.ref = dref; c.errs = derr; c.h_out = dh_out;
-  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat; c.mer_skip = mer_skip; c.mer = dmer;
+  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat; c.mer_skip = mer_skip; c.mer = dmer; c.scope = scope;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &c.tw));
   OFDM_TRY(t4_plan_tables<T>(pl));
   // stage brackets (ofdm_rx_plan_set_timing): [0] start, [1] AutoCorrFunction stage, [2] remove_IFO stage, [3] demodulator,
@@ -761,21 +764,28 @@ static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desy
   return OFDM_OK;
 }
 
-}  // namespace ofdm
+int scope_refused(int id, const ScopeWhy& w) {
+  if (id == SCOPE_OK) return OFDM_OK;
+  set_error("%s", w.text);
+  return OFDM_ERR_ARG;
+}
 
-using namespace ofdm;
-
-extern "C" {
-
-int ofdm_rx_chain_task4_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
-                           uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
-                           double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
-                           double* mer_sums_out, int flags) {
+// The body of ofdm_rx_chain_task4_ex / _iq and of the Task-4 sweeps' receiver call.  scope: the capture of this call, or null --
+// an IQ window whose iq is where `flags` says (staged like every other output), or a density whose accumulators are device
+// memory whatever the flags (ofdm_ber_sweep_task4_scope zeroes and owns them).
+int rx_chain_task4_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                       uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                       double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
+                       double* mer_sums_out, const ScopeCall* scope, int flags) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && rx && n_frames >= 0, "rx_chain_task4: bad arguments");
   OFDM_ARG(pl->nd >= 1, "rx_chain_task4: the plan has no data carriers");
   OFDM_ARG(mer_skip >= 0 && mer_skip < (int64_t)pl->nd * pl->n_symb,
            "rx_chain_task4_ex: mer_skip must be 0 .. nd * N_symb - 1 (%lld)", (long long)mer_skip);
+  if (scope && scope->iq) {
+    ScopeWhy why;
+    OFDM_TRY(scope_refused(scope_iq_check(scope->iq_first, scope->iq_count, (int64_t)pl->nd * pl->n_symb, why), why));
+  }
   OFDM_PLAN_DEVICE(pl);
   OFDM_ARG((is_f64(flags) ? 1 : 0) == pl->f64, "rx_chain_task4: precision flag differs from the plan's");
   OFDM_ARG(pl->pilots_in_band, "rx_chain_task4: pilots outside 1..N_carrier are not supported");
@@ -799,13 +809,43 @@ int ofdm_rx_chain_task4_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, i
   if (status_out) OFDM_TRY(st.out(status_out, sizeof(int32_t) * n_frames, &dstat)); else OFDM_TRY(st.scratch(sizeof(int32_t) * n_frames, &dstat));
   void* dmer;
   OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * n_frames, &dmer));
+  ScopeCall sc;
+  if (scope) {
+    sc = *scope;
+    if (sc.iq) OFDM_TRY(st.out(scope->iq, cs * (size_t)sc.iq_count * n_frames, &sc.iq));
+  }
+  const ScopeCall* dsc = scope ? &sc : nullptr;
   if (pl->f64)
     OFDM_TRY(task4_run<double>(pl, drx, n_frames, time_desync, freq_desync, mp_desync, dbits, dref, derr, (int64_t*)dtg, (double*)dfo,
-                               (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer));
+                               (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer, dsc));
   else
     OFDM_TRY(task4_run<float>(pl, drx, n_frames, time_desync, freq_desync, mp_desync, dbits, dref, derr, (int64_t*)dtg, (double*)dfo,
-                              (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer));
+                              (int32_t*)difo, (int32_t*)dstat, dh, (int)mer_skip, (double*)dmer, dsc));
   return st.finish();
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" {
+
+int ofdm_rx_chain_task4_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                           uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                           double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
+                           double* mer_sums_out, int flags) {
+  return rx_chain_task4_run(pl, rx, n_frames, time_desync, freq_desync, mp_desync, bits_out, ref_bits, errors_out, tg_position_out,
+                            freq_offset_out, ifo_out, status_out, h_out, mer_skip, mer_sums_out, nullptr, flags);
+}
+
+int ofdm_rx_chain_task4_iq(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                           uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                           double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
+                           double* mer_sums_out, int64_t iq_first, int64_t iq_count, void* iq_out, int flags) {
+  ScopeCall sc;
+  sc.iq_first = iq_first; sc.iq_count = iq_count; sc.iq = iq_out;
+  return rx_chain_task4_run(pl, rx, n_frames, time_desync, freq_desync, mp_desync, bits_out, ref_bits, errors_out, tg_position_out,
+                            freq_offset_out, ifo_out, status_out, h_out, mer_skip, mer_sums_out, iq_out ? &sc : nullptr, flags);
 }
 
 int ofdm_rx_chain_task4(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,

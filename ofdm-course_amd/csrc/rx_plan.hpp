@@ -55,6 +55,8 @@ struct ofdm_rx_plan {
   int t4_bw = 0, t4_span = 0;
   void* ws_t4 = nullptr;   // ofdm_rx_chain_task4: arena for its per-batch intermediates
   size_t ws_t4_bytes = 0;
+  void* ws_scope = nullptr; // ofdm_ber_sweep_task4_scope: the density grids and dropped counters of a call whose outputs are host memory
+  size_t ws_scope_bytes = 0; // (or whose dropped counters are not wanted); never part of ws_txf
   void* ws_raw = nullptr;  // raw packed decisions of a batch when the DeScrambler runs as a pass of its own (descr_pass_kernel)
   size_t ws_raw_bytes = 0;
   uint32_t descr = 0;      // per-frame DeScrambler of the pack stages (ofdm_rx_plan_set_descrambler): 0 or DESCR_ON | register bits
@@ -77,6 +79,11 @@ namespace ofdm {
 // ofdm_chain.hip: the body of ofdm_rx_chain_task5_ex; ls_inv_snr as in make_plan_view (the BER sweeps: the point's SNR)
 int rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
                        uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr);
+// ofdm_chain_t4.hip: the body of ofdm_rx_chain_task4_ex / _iq; scope = the constellation capture of the call, or null
+int rx_chain_task4_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
+                       uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
+                       double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
+                       double* mer_sums_out, const ScopeCall* scope, int flags);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
 }
