@@ -369,6 +369,43 @@ int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* plan, const int32_t* tap_delay, co
                                 double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
                                 double* nmse_sums_out /* [n_points] */,
                                 double* frame_nmse_out /* [n_points][frames_per_point] */, int flags);
+/* ofdm_ber_sweep_task5_fading (all its arguments and outputs stay, each optional as there) or, with the static channel
+ * h / h_len at the end of those, ofdm_ber_sweep_task5_ex -- with the constellation of every sweep point as a density
+ * accumulated on the device: what the scatter of T5/Main_model_Task_5.m:248-251 becomes when a point is a million frames, over
+ * the points MER_func sums at :282.  Exactly one channel is given: n_taps > 0 (tap_delay / tap_power; h must be NULL and h_len
+ * 0), or h / h_len with n_taps == 0 (h = NULL: no channel; the NMSE outputs, which need the tap-delay line, must then be NULL).
+ * Every decided point with IQ index >= scope_skip, of every frame of point p, is counted once in
+ *   density_out[n_points][bins][bins] (uint64, where `flags` says), at [p][row][col] with
+ *     scale = bins / (2 * half_width), computed once on the host in double,
+ *     col = clamp((int)floor((double(re) + half_width) * scale), 0, bins - 1),
+ *     row = the same from im;
+ *   the arithmetic is double in both precisions (one function bins on the device and on the host, csrc/scope_plan.hpp); a
+ *   point outside +-half_width lands in an edge bin; a point with non-finite re or im is not binned but counted in
+ *   density_dropped_out[n_points] (uint64, optional).  Therefore
+ *     sum(density[p]) + dropped[p] == frames_per_point * (nd * N_symb - scope_skip).
+ * The points are those of ofdm_rx_chain_task5_iq, symbol 1 included, for every estimator of the plan (OMP on the batch or the
+ * wide route, fixed-h MMSE with n_points == 1, ofdm_rx_plan_set_mmse_ls) and with a DeScrambler; each frame is decoded on the
+ * route of ofdm_rx_chain_task5_ex with the MER sums wanted, whose symbol stage keeps a uint32 grid in its LDS across the
+ * frames a workgroup decodes and adds it to density_out with 64-bit atomics.  Counts are integers: bitwise independent of
+ * max_frames_per_chunk, of the launch grid and of the order of arrival.  Refused with OFDM_ERR_ARG, behind every check of the
+ * entry without a density, in this order and before anything is launched or written: density_out == NULL; bins not 8, 16, 32,
+ * 64 or 128; half_width not finite or <= 0; scope_skip outside 0 .. nd * N_symb - 1; the symbol stage's LDS with the grid
+ * (4 * bins^2 bytes behind its present regions) beyond that stage's limit (158 KiB for the generic single kernel, 150 KiB for
+ * every other stage).
+ * The grids are zeroed on the launch stream before the first chunk.  With OFDM_DEVICE the accumulators are the caller's outputs
+ * and the call keeps the no-host-synchronisation rule of ofdm_ber_sweep_task5 (first-call growth of a small plan-owned buffer
+ * apart, which with OFDM_HOST holds the accumulators until they are copied out).  Every other output is bit for bit what the
+ * entry without a density returns with the MER sums wanted; the MER sums themselves are returned only if asked for. */
+int ofdm_ber_sweep_task5_scope(ofdm_rx_plan* plan, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                               const double* snr_db, const uint64_t* seeds, int64_t n_points, int64_t frames_per_point,
+                               int64_t frame0, const uint8_t* scr_reg15, int64_t max_frames_per_chunk, uint64_t* errors_out,
+                               uint32_t* frame_errors_out, double* mer_sums_out /* [n_points][2] */,
+                               double* frame_mer_sums_out /* [n_points][frames_per_point][2] */,
+                               double* nmse_sums_out /* [n_points] */,
+                               double* frame_nmse_out /* [n_points][frames_per_point] */, const void* h, int h_len,
+                               uint64_t* density_out /* [n_points][bins][bins] */,
+                               uint64_t* density_dropped_out /* [n_points], optional */, int bins, double half_width,
+                               int64_t scope_skip, int flags);
 /* ofdm_tx_frames_fused with the Task-4 impairments, in the reference order (T4/Main_model_Task_4.m:94-110,:257-267,
  * T5/Noise.m:3-10, T5/add_STO.m, T5/add_CFO.m): per frame f of length len = (Nfft + T_guard) * N_symb
  *   w[j] = x[j] + sigma_f n(j)            the noise of Noise.m, Philox counter (j, 0, frame0 + f, 0) of the SOURCE index j
@@ -612,6 +649,22 @@ int ofdm_rx_chain_task5(ofdm_rx_plan* plan, const void* rx, int64_t n_frames,
 int ofdm_rx_chain_task5_ex(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
                            uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out /* [n_frames][2] */,
                            int flags);
+/* ofdm_rx_chain_task5_ex that also returns a window of each frame's RX_IQ = get_payload(equalize_signal(.))(:) -- the points
+ * the reference looks at at T5/Main_model_Task_5.m:248-251 (RX_IQ = get_payload(...)(:), scatterplot(RX_IQ(nd+1 : nd+332))) and
+ * sums in MER_func at :282:
+ *   iq_out[n_frames][iq_count] (complex in the plan's precision, where `flags` says) = RX_IQ(iq_first .. iq_first + iq_count - 1)
+ *   (0-based) of each frame: the equalised point, exactly the value the demapper slices and MER_func sums, element
+ *   i = s * nd + (data index) of symbol s, symbol 1 included.
+ * The window may start anywhere, straddle symbol boundaries and end at nd * N_symb; OFDM_ERR_ARG unless 0 <= iq_first,
+ * 1 <= iq_count and iq_first + iq_count <= nd * N_symb (checked behind every check and route refusal of ofdm_rx_chain_task5_ex,
+ * before anything is launched).  A non-finite equaliser gives non-finite values, as the reference's RX_IQ would be.  With a
+ * DeScrambler the captured points are the same: the capture sits in front of the demapper.  The call takes the route of
+ * ofdm_rx_chain_task5_ex with the MER sums wanted (the symbol stage runs the capture variant of its MER build); mer_sums_out is
+ * still optional.  iq_out = NULL is ofdm_rx_chain_task5_ex (the window is not looked at); every other output is bit for bit
+ * what ofdm_rx_chain_task5_ex with mer_sums_out given returns. */
+int ofdm_rx_chain_task5_iq(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out /* [n_frames][2] */,
+                           int64_t iq_first, int64_t iq_count, void* iq_out /* [n_frames][iq_count] */, int flags);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,7 @@ SIGNATURES = {
     "ofdm_rx_plan_last_task4_ms": [_vp, C.POINTER(C.c_float)],
     "ofdm_rx_chain_task5": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_rx_chain_task5_ex": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_rx_chain_task5_iq": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i],
     "ofdm_task5_part2_tile": [_vp, _vp, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _i],
     "ofdm_task5_mse_tile": [_vp, _vp, _vp, _vp, _i, _vp, _i64, C.c_uint64, C.c_uint32, _vp, _i],
     "ofdm_OMP_estimate_batch": [_vp, _vp, _i64, _i, _vp, _vp, _vp, _i],
@@ -94,6 +95,8 @@ SIGNATURES = {
     "ofdm_ber_sweep_task5_ex": [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i],
     "ofdm_tx_frames_fading": [_vp, _vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task5_fading": [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_ber_sweep_task5_scope": [_vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                   _vp, _vp, _i, _d, _i64, _i],
     "ofdm_tx_frames_fused_ex": [_vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_ber_sweep_task4": [_vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp,
                              _vp, _i],

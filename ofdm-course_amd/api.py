@@ -882,7 +882,7 @@ class RxPlan:
 
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
-                  want_nmse=False, want_frame_nmse=False):
+                  want_nmse=False, want_frame_nmse=False, density=None):
         """One device-resident tile of a BER(SNR) sweep (ofdm_ber_sweep_task5): for every SNR of `SNRs` the frames
         frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h, SNR, seeds[p]) decoded by rx_chain_task5 on this plan
         (T3/Main_model_Task_3.m:237-268, T5/Task5_part2.m:134,:148-152).  seeds: one Philox key per point (default: `seed`
@@ -897,18 +897,48 @@ class RxPlan:
         fading=(delays, powers) (ofdm_ber_sweep_task5_fading; not with h): the frames of tx_frames_fused(fading=...), a channel
         realisation per frame (T5/Task5_part2.m:148-155).  want_nmse then adds nmse_sums=[n], per point the sum over its frames
         of sum_k |fft(h_f, Nfft)(k) - H_est_f(k)|^2 on carriers 1..N_carrier, and NMSE=[n] = nmse_sums / (frames_per_point *
-        N_carrier) (T5/Task5_part2.m:202-205,:318); want_frame_nmse the per-frame sums frame_nmse=[n, frames_per_point]."""
+        N_carrier) (T5/Task5_part2.m:202-205,:318); want_frame_nmse the per-frame sums frame_nmse=[n, frames_per_point].
+        density=dict(bins=, half_width=, skip=0) (ofdm_ber_sweep_task5_scope; with h or with fading): also density=[n, bins,
+        bins] int64, per point the count of its frames' equalised points RX_IQ (those of rx_chain_task5(iq_window=), from
+        0-based index skip on) at [row of im, column of re] with col = clamp(floor((re + half_width) * bins / (2 half_width)),
+        0, bins - 1), and density_dropped=[n], the points with a non-finite coordinate, which are not binned: sum(density[p])
+        + density_dropped[p] = frames_per_point * (nd * N_symb - skip).  The scatter of T5/Main_model_Task_5.m:248-251 at sweep
+        sizes, over the points MER_func sums at :282."""
         if want_frame_mer and not want_mer:
             raise OfdmError("ber_sweep: want_frame_mer needs want_mer")
         if (want_nmse or want_frame_nmse) and fading is None:
             raise OfdmError("ber_sweep: want_nmse / want_frame_nmse need fading")
+        if density is not None:
+            try:
+                extra = set(density) - {"bins", "half_width", "skip"}
+                bins, half_width, skip = int(density["bins"]), float(density["half_width"]), int(density.get("skip", 0))
+            except (TypeError, KeyError, ValueError, AttributeError):
+                raise OfdmError("ber_sweep: density must be dict(bins=, half_width=, skip=0)") from None
+            if extra:
+                raise OfdmError(f"ber_sweep: unknown density keys {sorted(extra)}")
         snr, sd = self._points(SNRs, seeds, seed, "ber_sweep")
         n, fpp = snr.size, int(frames_per_point)
         (err, fe, ms, fm, ns, fn), ptrs, flags = self._outputs(
             device, ((n,), np.uint64), ((n, fpp), np.uint32) if want_frame_errors else None,
             ((n, 2), np.float64) if want_mer else None, ((n, fpp, 2), np.float64) if want_frame_mer else None,
             ((n,), np.float64) if want_nmse else None, ((n, fpp), np.float64) if want_frame_nmse else None)
-        if fading is not None:
+        own = {}
+        if density is not None:
+            nb = bins if bins > 0 else 0                          # (a bad count is the library's refusal)
+            (dens, drop), dptrs, _ = self._outputs(device, ((n, nb, nb), np.uint64), ((n,), np.uint64))
+            if fading is not None:
+                keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep")
+                keep, ph, nh, pr = self._fused_args(None, Register, "ber_sweep")
+            else:
+                pdl, ppw, nt = None, None, 0
+                keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
+            L.check(self.lib.ofdm_ber_sweep_task5_scope(self.handle, pdl, ppw, nt, snr.ctypes.data_as(C.c_void_p),
+                                                        sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
+                                                        int(max_frames_per_chunk), *ptrs, ph, nh, *dptrs, bins, half_width,
+                                                        skip, flags), "ber_sweep_task5_scope")
+            own = dict(density=dens if device is not None else dens.view(np.int64),      # int64 views: a count of 2^63 is out of reach
+                       density_dropped=drop if device is not None else drop.view(np.int64))
+        elif fading is not None:
             keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep")
             keep, _, _, pr = self._fused_args(None, Register, "ber_sweep")
             L.check(self.lib.ofdm_ber_sweep_task5_fading(self.handle, pdl, ppw, nt, snr.ctypes.data_as(C.c_void_p),
@@ -920,7 +950,7 @@ class RxPlan:
                                                      sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
                                                      int(max_frames_per_chunk), *ptrs[:4], flags),
                     "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
-        return self._sweep_result(device, err, fpp, {}, ns, fn, fe, ms, fm)
+        return self._sweep_result(device, err, fpp, own, ns, fn, fe, ms, fm)
 
     def _sweep_result(self, device, errors, fpp, own, nmse_sums, frame_nmse, frame_errors, mer_sums, frame_mer_sums):
         """What ber_sweep and ber_sweep_task4 return alike: the errors (int64 on the host), the bits per point, `own` (what only
@@ -1057,7 +1087,7 @@ class RxPlan:
             pass
 
 
-def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_index=False, want_mer=False):
+def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_index=False, want_mer=False, iq_window=None):
     """Fused demod -> OMP -> equalise -> payload -> demap -> BER over a batch of frames.
 
     rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
@@ -1065,11 +1095,20 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
     H=[N_carrier, n_frames] or None, index=[taps, n_frames] int32 or None).
     want_mer (ofdm_rx_chain_task5_ex): also mer_sums=[n_frames, 2] float64, the sums {|ideal|^2, |ideal - RX_IQ|^2} of
     MER_func (T5/MER_func.m:3-25) over each frame's whole RX_IQ (T5/Main_model_Task_5.m:282), and MER_dB=[n_frames] =
-    10 log10(s1 / s2)."""
+    10 log10(s1 / s2).
+    iq_window=(first, count) (ofdm_rx_chain_task5_iq): also RX_IQ=[n_frames, count] complex in the plan's precision, the
+    equalised points get_payload(.)(:) of each frame from 0-based index first on -- what the demapper slices and MER_func sums;
+    (nd, 332) is the scatterplot(RX_IQ(nd+1 : nd+332)) of T5/Main_model_Task_5.m:248-251.  The other outputs are those of the
+    call with want_mer."""
     call = _Call(rx, f64=plan.f64)
     rows, nfr = _shape2(rx)
     if rows != plan.frame_samples:
         raise OfdmError("rx_chain_task5: rx must have (Nfft+T_guard)*N_symb rows")
+    if iq_window is not None:
+        try:
+            iq_first, iq_count = (int(v) for v in iq_window)
+        except (TypeError, ValueError):
+            raise OfdmError("rx_chain_task5: iq_window must be (first, count)") from None
     flat_bits, pbits = call._out((plan.frame_bytes * nfr,), np.uint8, torch.uint8 if call.dev else None)
     bits = flat_bits.reshape(nfr, plan.frame_bytes)
     pref = None
@@ -1083,15 +1122,26 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
         errors, perr = call._out((nfr,), np.uint32, torch.int32 if call.dev else None)
     H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
     idx, pidx = (call._out((plan.taps, nfr), np.int32, torch.int32 if call.dev else None) if want_index else (None, None))
-    if not want_mer:
+    if not want_mer and iq_window is None:
         L.check(call.lib.ofdm_rx_chain_task5(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, call.flags),
                 "rx_chain_task5")
         return dict(bits=bits, errors=errors, H=H, index=idx)
-    mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
-    mer = mer.T
-    L.check(call.lib.ofdm_rx_chain_task5_ex(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, pmer, call.flags),
-            "rx_chain_task5_ex")
-    return dict(bits=bits, errors=errors, H=H, index=idx, mer_sums=mer, MER_dB=_mer_db(mer))
+    out = dict(bits=bits, errors=errors, H=H, index=idx)
+    mer, pmer = None, None
+    if want_mer:
+        mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
+        mer = mer.T
+        out.update(mer_sums=mer)
+    head = (plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, pmer)
+    if iq_window is None:
+        L.check(call.lib.ofdm_rx_chain_task5_ex(*head, call.flags), "rx_chain_task5_ex")
+    else:
+        iq, piq = call.cout((max(iq_count, 0), nfr))                                      # memory [n_frames][count]
+        L.check(call.lib.ofdm_rx_chain_task5_iq(*head, iq_first, iq_count, piq, call.flags), "rx_chain_task5_iq")
+        out.update(RX_IQ=iq.T)
+    if want_mer:
+        out.update(MER_dB=_mer_db(mer))
+    return out
 
 
 def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, ref_bits_packed=None, want_h=False,

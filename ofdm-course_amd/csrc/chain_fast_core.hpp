@@ -11,6 +11,7 @@
 #include "fft_core.hpp"
 #include "chain_route.hpp"
 #include "omp_wide_host.hpp"
+#include "scope_plan.hpp"
 
 namespace ofdm {
 
@@ -483,11 +484,78 @@ __device__ __forceinline__ int slice_symbol(const DemapTable<T>& tab, cx<T> z) {
 struct MerSums {
   double* sums;                                                        // [n_frames][2]
 };
+// Scope variants of the Task-5 symbol stages (constellation capture; ofdm_rx_chain_task5_iq, ofdm_ber_sweep_task5_scope): a
+// Scope5Out behind the MerSums in the pack -- a Scope build exists only on top of a stage's MER build, one per MER build, and
+// serves the IQ window and the density with run-time null checks (iq, bins).  At the per-point site of the MER sums, with IQ index
+// i = s * nd + (data index), symbol 1 included (scope5_point):
+//   IQ window: the equalised point stored to iq[f][i - iq_first] for iq_first <= i < iq_first + iq_count.
+//   Density: a bins x bins uint32 grid in dynamic LDS behind the stage's own regions (lds_off), zeroed once per workgroup and kept
+//   across the frames it decodes; per point with i >= skip one LDS atomicAdd at (row of im, column of re) (scope_bin,
+//   scope_plan.hpp), a non-finite point counted in a register instead; when the workgroup is done with its frames, behind a
+//   workgroup barrier, one 64-bit global atomicAdd per non-zero bin and one per wavefront with dropped points
+//   (scope5_grid_flush).  Integers: the result does not depend on the grid, the batching or the order of arrival.  A uint32 bin
+//   cannot wrap: a receiver call holds at most 2^32 - 1 points (the sweep caps its chunk, rx_chain_task5_run checks it).
+// eq_demap_kernel, the stage both receivers share, keeps the pair it had for the Task-4 capture (ScopeOut and scope_point,
+// ofdm_chain_split.hip: the same fields and the same per-point rule, with an early flush instead of the cap).
+struct Scope5Out {
+  int iq_first, iq_count;                                              // the window (iq null: none)
+  void* iq;                                                            // [n_frames][iq_count] cx<T>
+  int bins, skip;                                                      // bins 0: no density
+  double half_width, scale;
+  unsigned lds_off;                                                    // the grid's byte offset in dynamic LDS
+  unsigned long long* density;                                         // [bins][bins] of the call's sweep point
+  unsigned long long* dropped;                                         // its counter of non-finite points
+};
+__device__ __forceinline__ void mer_pack_take(const MerSums& m, double*& p, Scope5Out&) { p = m.sums; }
+__device__ __forceinline__ void mer_pack_take(const Scope5Out& s, double*&, Scope5Out& so) { so = s; }
 template <typename... Mer>
 __device__ __forceinline__ double* mer_sums_of(Mer... mer) {
   double* p = nullptr;
-  ((p = mer.sums), ...);
+  Scope5Out so{};
+  (mer_pack_take(mer, p, so), ...);
   return p;
+}
+template <typename... Mer>
+__device__ __forceinline__ Scope5Out scope5_out_of(Mer... mer) {
+  double* p = nullptr;
+  Scope5Out so{};
+  (mer_pack_take(mer, p, so), ...);
+  return so;
+}
+
+// one decided point ye of IQ index i: the window store, and the grid count or the thread's dropped count
+template <typename T>
+__device__ __forceinline__ void scope5_point(const Scope5Out& sc, cx<T>* __restrict__ iq_frame, uint32_t* __restrict__ grid,
+                                            unsigned& dropped, int i, cx<T> ye) {
+  if (iq_frame) {
+    const int w = i - sc.iq_first;
+    if ((unsigned)w < (unsigned)sc.iq_count) iq_frame[w] = ye;
+  }
+  if (sc.bins && i >= sc.skip) {
+    const int col = scope_bin((double)ye.x, sc.half_width, sc.scale, sc.bins);
+    const int row = scope_bin((double)ye.y, sc.half_width, sc.scale, sc.bins);
+    if (col < 0 || row < 0) ++dropped;
+    else atomicAdd(&grid[row * sc.bins + col], 1u);
+  }
+}
+// the workgroup's grid, zeroed by its nthr threads (in front of a workgroup barrier that precedes the first point)
+__device__ __forceinline__ uint32_t* scope5_grid_init(const Scope5Out& sc, unsigned char* smem, int tid, int nthr) {
+  uint32_t* const grid = (uint32_t*)(smem + sc.lds_off);
+  for (int i = tid; i < sc.bins * sc.bins; i += nthr) grid[i] = 0;
+  return grid;
+}
+// the workgroup's counts -> the point's accumulators (behind a workgroup barrier that follows the workgroup's last point; every
+// thread calls it with whole wavefronts)
+__device__ __forceinline__ void scope5_grid_flush(const Scope5Out& sc, const uint32_t* __restrict__ grid, unsigned dropped, int tid,
+                                                 int nthr) {
+  if (!sc.bins) return;
+  for (int i = tid; i < sc.bins * sc.bins; i += nthr) {
+    const uint32_t v = grid[i];
+    if (v) atomicAdd(&sc.density[i], (unsigned long long)v);
+  }
+  unsigned long long d = dropped;
+  for (int off = 32; off > 0; off >>= 1) d += __shfl_xor(d, off, 64);
+  if ((tid & 63) == 0 && d) atomicAdd(sc.dropped, d);
 }
 template <typename T>
 __device__ __forceinline__ void mer_add(cx<T> p, cx<T> ye, double& s1, double& s2) {
@@ -691,6 +759,7 @@ struct FastPlanView {
   int* omp_out = nullptr;                     // set to the kernel the OMP stage ran: OMP_ROUTE_BATCH (the fused launch included) or OMP_ROUTE_WIDE
   const ChainRoute* route = nullptr;          // the receiver's route of this call (chain_route.hpp); null outside rx_chain_task5_run
                                               // (the launchers that read it refuse a view without one: OFDM_NEEDS_ROUTE)
+  const struct ScopeCall* scope = nullptr;    // the constellation capture of this call (the symbol stage then runs its Scope variant), or null
   bool mmse() const { return d_wt != nullptr || mmse_ls != 0; }   // the symbol stages take H from ws_h
 };
 
@@ -720,7 +789,8 @@ inline int omp_stage_run(const FastParams<T>& P, int nfft, int64_t F, int route 
   return r == OMP_ROUTE_WIDE ? omp_wide_run<T>(P, nfft, F) : omp_batch_run<T>(P, lay, by_fft, F);
 }
 
-// constellation capture of one eq_demap_run call (the SCOPE variant of eq_demap_kernel; checked by scope_plan.hpp's functions):
+// constellation capture of one receiver call -- eq_demap_run (the SCOPE variant of eq_demap_kernel) or rx_chain_task5_run (the
+// Scope variant of the route's symbol stage); checked by scope_plan.hpp's functions:
 // iq != null: the window iq_first .. iq_first + iq_count - 1 of every frame's points -> iq[n_frames][iq_count];
 // bins != 0: the points from IQ index skip on counted into density[bins][bins] (non-finite ones in *dropped), both device
 // accumulators that the caller has zeroed
@@ -732,6 +802,12 @@ struct ScopeCall {
   double half_width = 0.0, scale = 0.0;
   unsigned long long *density = nullptr, *dropped = nullptr;
 };
+// the kernel argument of a Task-5 symbol stage's Scope variant: the grid behind the stage's stage_lds bytes of dynamic LDS
+// (scope5_grid_offset; the launch asks for scope5_lds_total(stage_lds, bins) bytes)
+inline Scope5Out scope5_out(const ScopeCall& c, size_t stage_lds) {
+  return Scope5Out{(int)c.iq_first, (int)c.iq_count, c.iq, c.bins, (int)c.skip, c.half_width, c.scale,
+                  (unsigned)scope5_grid_offset(stage_lds), c.density, c.dropped};
+}
 template <typename T>
 int eq_demap_run(const FastPlanView& pv, const FastParams<T>& P, const cx<T>* xk, int x_stride, bool hext, int64_t n_frames,
                  void* bits, const void* ref, void* errs, void* h_out, void* idx_out, const double* fine_est, int time_desync,

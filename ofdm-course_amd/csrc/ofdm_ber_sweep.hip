@@ -264,14 +264,80 @@ static int txf_sweep_prelude(ofdm_rx_plan* pl, TxfCall& c, TxfShape& s, const vo
   return txf_refused(prelude(c, ch, fade.gains, why), why);
 }
 
-// the body of both Task-5 sweep entries: the checks of txf_task5_prelude, then c's static channel, or the delay line of a
-// channel per frame; nmse_sums_out / frame_nmse_out (fading only): the channel-estimate error sums
+// the constellation density of a Task-5 sweep's points (ofdm_ber_sweep_task5_scope)
+struct SweepScope {
+  bool on = false;
+  int bins = 0;
+  double half_width = 0.0;
+  int64_t skip = 0;
+  uint64_t *density_out = nullptr, *dropped_out = nullptr;
+};
+
+// The density grids [n_points][bins][bins] and the dropped counters [n_points] are accumulators of the symbol stages' global
+// atomics: the caller's device outputs themselves; host outputs, and dropped counters nobody asked for, in a buffer of the
+// plan's own (pl->ws_scope -- not the generator workspace, whose regions are per chunk).  Zeroed on the launch stream
+// before the first chunk; host outputs are copied back in front of st.finish()'s synchronisation (finish()).
+struct SweepScopeAcc {
+  unsigned long long *dens = nullptr, *drop = nullptr;
+  size_t grid_elems = 0;
+  int begin(ofdm_rx_plan* pl, const SweepScope& a, bool device_mode, int64_t n_points) {
+    hipStream_t stream = ctx().stream;
+    grid_elems = (size_t)a.bins * (size_t)a.bins;
+    const size_t own = sizeof(uint64_t) * (device_mode ? (a.dropped_out ? 0 : (size_t)n_points) : (size_t)n_points * (grid_elems + 1));
+    if (pl->ws_scope_bytes < own) {
+      OFDM_HIP(hipStreamSynchronize(stream));
+      if (pl->ws_scope) { (void)hipFree(pl->ws_scope); pl->ws_scope = nullptr; pl->ws_scope_bytes = 0; }
+      OFDM_HIP(hipMalloc(&pl->ws_scope, own));
+      pl->ws_scope_bytes = own;
+    }
+    if (device_mode) {
+      dens = (unsigned long long*)a.density_out;
+      drop = a.dropped_out ? (unsigned long long*)a.dropped_out : (unsigned long long*)pl->ws_scope;
+    } else {
+      dens = (unsigned long long*)pl->ws_scope;
+      drop = dens + (size_t)n_points * grid_elems;
+    }
+    OFDM_HIP(hipMemsetAsync(dens, 0, sizeof(uint64_t) * (size_t)n_points * grid_elems, stream));
+    OFDM_HIP(hipMemsetAsync(drop, 0, sizeof(uint64_t) * (size_t)n_points, stream));
+    return OFDM_OK;
+  }
+  // the capture of a receiver call on frames of point p (a chunk holds frames of one point: one grid per call)
+  ScopeCall call(const SweepScope& a, int64_t p) const {
+    ScopeCall sc;
+    sc.bins = a.bins; sc.skip = a.skip; sc.half_width = a.half_width;
+    sc.scale = scope_scale(a.bins, a.half_width);
+    sc.density = dens + (size_t)p * grid_elems; sc.dropped = drop + p;
+    return sc;
+  }
+  int finish(const SweepScope& a, bool device_mode, int64_t n_points) const {
+    if (device_mode) return OFDM_OK;
+    hipStream_t stream = ctx().stream;
+    OFDM_HIP(hipMemcpyAsync(a.density_out, dens, sizeof(uint64_t) * (size_t)n_points * grid_elems, hipMemcpyDeviceToHost, stream));
+    if (a.dropped_out) OFDM_HIP(hipMemcpyAsync(a.dropped_out, drop, sizeof(uint64_t) * (size_t)n_points, hipMemcpyDeviceToHost, stream));
+    return OFDM_OK;
+  }
+};
+
+// the body of the Task-5 sweep entries: the checks of txf_task5_prelude, then c's static channel, or the delay line of a
+// channel per frame; nmse_sums_out / frame_nmse_out (fading only): the channel-estimate error sums; sw: the density of
+// ofdm_ber_sweep_task5_scope
 static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t* frame_errors_out, double* mer_sums_out,
-                    double* frame_mer_sums_out, double* nmse_sums_out, double* frame_nmse_out, int flags) {
+                    double* frame_mer_sums_out, double* nmse_sums_out, double* frame_nmse_out, int flags,
+                    const SweepScope& sw = SweepScope{}) {
   TxfShape s{};
   TxfChannel ch;
   TxfFade fade;
   OFDM_TRY(txf_sweep_prelude(pl, c, s, errors_out, flags, txf_task5_prelude, ch, fade));
+  const int64_t decisions = (int64_t)s.nd * s.n_symb;
+  if (sw.on) {                                                  // behind every check of the entry without a density
+    int stage = SYM_EQ_DEMAP;
+    size_t stage_lds = 0;
+    // (a plan the receiver refuses has no stage: the first receiver call says so in the receiver's words)
+    const bool routed = rx_chain_task5_scope_stage(pl, &stage, &stage_lds);
+    ScopeWhy why;
+    OFDM_TRY(scope_refused(scope5_density_check(stage, routed ? stage_lds : 0, sw.bins, sw.half_width, sw.skip, decisions,
+                                                sw.density_out != nullptr, why), why));
+  }
   const TxfPoints pt{c.snr_db, c.seeds, c.n_points, c.n_frames, c.frame0};
   const int64_t n_points = pt.n_points, frames_per_point = pt.frames_per_point;
   if (n_points == 0) return OFDM_OK;
@@ -282,8 +348,11 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   void *dns, *dfn;
   OFDM_TRY(st.out(nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
   OFDM_TRY(st.out(frame_nmse_out, sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
+  SweepScopeAcc acc;
+  if (sw.on) OFDM_TRY(acc.begin(pl, sw, st.device_mode(), n_points));
   if (frames_per_point == 0) {
     if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, ctx().stream));
+    if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
     return st.finish();
   }
   if (dns && !dfn) OFDM_TRY(st.scratch(sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
@@ -292,7 +361,10 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   u.sweep = true;
   u.fade_taps = c.fading ? (int)ch.delay.size() : 0;
   u.hest = dfn != nullptr;
-  const int64_t CH = txf_chunk(s, u, frames_per_point, c.max_chunk);
+  int64_t CH = txf_chunk(s, u, frames_per_point, c.max_chunk);
+  // a density: a chunk holds at most 2^32 - 1 points, so that no uint32 bin of a workgroup's grid can wrap (counts are integers:
+  // the result does not depend on the chunking)
+  if (sw.on) CH = std::max<int64_t>(1, std::min<int64_t>(CH, (int64_t)(0xffffffffull / (unsigned long long)decisions)));
   const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
   TxfDelays dl{};
   if (c.fading) dl = txf_delays(ch);
@@ -300,9 +372,12 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, nullptr, c.fading ? &fade : nullptr, u,
                             [&](const TxfBuffers& b, int64_t nf, int64_t k) {
                               const double inv_snr = 1.0 / std::pow(10.0, pt.snr_db[k / frames_per_point] * 0.1);
+                              ScopeCall sc;
+                              if (sw.on) sc = acc.call(sw, k / frames_per_point);
                               OFDM_TRY(rx_chain_task5_run(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
                                                           (uint32_t*)o.fe + k, b.hest, nullptr,
-                                                          o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags, inv_snr));
+                                                          o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags, inv_snr,
+                                                          sw.on ? &sc : nullptr));
                               if (!dfn) return (int)OFDM_OK;
                               return txf_frame_nmse(pl, b.amp, b.hest, dl, (int64_t)dl.n, nf, (double*)dfn + k);
                             }));
@@ -311,6 +386,7 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   OFDM_TRY(check_launch("ber_point_reduce_kernel"));
   OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
   OFDM_TRY(txf_point_sums<1>(dfn, n_points, frames_per_point, dns));
+  if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
   return st.finish();
 }
 
@@ -480,6 +556,31 @@ extern "C" int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* pl, const int32_t* tap_
   return t5_sweep(pl, TxfCall("ber_sweep_task5_fading", frame0, frames_per_point, scr_reg15)
                           .with_fading(tap_delay, tap_power, n_taps).with_points(snr_db, seeds, n_points, max_frames_per_chunk),
                   errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out, flags);
+}
+
+extern "C" int ofdm_ber_sweep_task5_scope(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
+                                          const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                          int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
+                                          int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
+                                          double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
+                                          double* frame_nmse_out, const void* h, int h_len, uint64_t* density_out,
+                                          uint64_t* density_dropped_out, int bins, double half_width, int64_t scope_skip,
+                                          int flags) {
+  OFDM_TRY(ensure_init());
+  // one channel: the static h / h_len (h = NULL: none), or the delay line of n_taps > 0 taps
+  OFDM_ARG(!(n_taps > 0 && (h || h_len)), "ber_sweep_task5_scope: give the static channel h / h_len or the tap-delay line (n_taps > 0), not both");
+  OFDM_ARG(n_taps >= 0, "ber_sweep_task5_scope: n_taps must be >= 0 (%d)", n_taps);
+  SweepScope sw;
+  sw.on = true; sw.bins = bins; sw.half_width = half_width; sw.skip = scope_skip;
+  sw.density_out = density_out; sw.dropped_out = density_dropped_out;
+  if (n_taps > 0)
+    return t5_sweep(pl, TxfCall("ber_sweep_task5_fading", frame0, frames_per_point, scr_reg15)
+                            .with_fading(tap_delay, tap_power, n_taps).with_points(snr_db, seeds, n_points, max_frames_per_chunk),
+                    errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out, flags, sw);
+  OFDM_ARG(!nmse_sums_out && !frame_nmse_out, "ber_sweep_task5_scope: the NMSE outputs need the tap-delay line (n_taps > 0)");
+  return t5_sweep(pl, TxfCall("ber_sweep_task5", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
+                          .with_points(snr_db, seeds, n_points, max_frames_per_chunk),
+                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nullptr, nullptr, flags, sw);
 }
 
 extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,

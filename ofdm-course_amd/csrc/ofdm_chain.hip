@@ -105,6 +105,8 @@ static void chain_layout(ChainParams<T>& P, int nfft, int bps) {
 
 // Mer (MerSums, chain_fast_core.hpp): the MER variant -- the sums of MER_func.m:19-23 over the frame's data points in double,
 // reduced over the frame's group by group_sum (fixed order).  An empty Mer is the kernel as it always was.
+// A Scope5Out behind the MerSums: the Scope variant on top of the MER one (constellation capture, chain_fast_core.hpp); the
+// workgroup's groups share one grid behind their regions.
 template <typename T, int N, typename... Mer>
 __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams<T> P, const cx<T>* __restrict__ rx,
                                                                      int64_t n_frames,
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
                                                                      uint32_t* __restrict__ errors_out,
                                                                      cx<T>* __restrict__ h_out,
                                                                      int32_t* __restrict__ index_out, Mer... mer) {
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = sizeof...(Mer) >= 1, SCOPE = sizeof...(Mer) == 2;
   constexpr int TPX = N / 8;
   constexpr int FPW = fft_xforms_per_wg(N);
   constexpr int WGW = fft_wg_threads(N) / 64;
@@ -144,6 +146,14 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
     __shared__ T mer_tab[32];
     mer_tab_fill<T>(P.tab, mer_tab, threadIdx.x);                      // (read after the barriers of symbol 1)
     mt = mer_tab;
+  }
+  const Scope5Out sc = scope5_out_of(mer...);                            // SCOPE: the capture, the workgroup's grid (zeroed in front of
+  uint32_t* grid = nullptr;                                            // the barriers of symbol 1), this thread's dropped points
+  unsigned sc_dropped = 0;
+  cx<T>* iq_frame = nullptr;
+  if constexpr (SCOPE) {
+    grid = scope5_grid_init(sc, smem, threadIdx.x, fft_wg_threads(N));
+    if (sc.iq && live) iq_frame = (cx<T>*)sc.iq + frame * sc.iq_count;
   }
 
   // ================= symbol 1: demodulate, pilots, OMP ==========================================
@@ -303,6 +313,7 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
           const int code = demap_decide(P.tab, z);
           codes[s * P.nd + d] = (uint8_t)code;
           if constexpr (MER) mer_add(mer_ideal<T, 0>(P.tab, mt, code), z, s1, s2);
+          if constexpr (SCOPE) { if (live) scope5_point<T>(sc, iq_frame, grid, sc_dropped, s * P.nd + d, z); }
         }
       }
     }
@@ -337,6 +348,7 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void rx_chain_kernel(ChainParams
     s2 = group_sum<TPX>(s2, sh_sum);
     if (live && j == 0) *(double2*)(mer_out + 2 * frame) = make_double2(s1, s2);
   }
+  if constexpr (SCOPE) scope5_grid_flush(sc, grid, sc_dropped, threadIdx.x, fft_wg_threads(N));   // (behind the barrier in front of the pack stage)
 }
 
 
@@ -396,6 +408,7 @@ int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* re
 using namespace ofdm;
 
 namespace ofdm {
+int scope_refused(int id, const ScopeWhy& w);                                              // ofdm_chain_t4.hip
 int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t* pilot_loc, int np, int n_carrier,
                         int m_pad, std::vector<c64>& wt);                                  // ofdm_chain_mmse.hip
 int chain_split_run(const FastPlanView& pv, const void* tw, const void* rx, int64_t n_frames, void* bits,
@@ -430,7 +443,8 @@ static ChainShape chain_shape(const ofdm_rx_plan* pl, bool want_mer) {
 
 template <typename T, int N>
 static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, int64_t n_frames, void* bits,
-                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer, size_t route_lds) {
+                        const void* ref, void* errs, void* h_out, void* idx_out, double* mer, size_t route_lds,
+                        const ScopeCall* scope) {
   ChainParams<T> P;
   P.n_symb = pl->n_symb; P.t_guard = pl->t_guard; P.n_carrier = pl->n_carrier; P.np = pl->np; P.nd = pl->nd;
   P.k_atoms = pl->k_atoms; P.taps = pl->taps;
@@ -444,6 +458,14 @@ static int launch_chain(const ofdm_rx_plan* pl, const void* tw, const void* rx, 
   const size_t dyn = (size_t)P.group_bytes * FPW;
   OFDM_ARG(dyn == route_lds && dyn <= GENERIC_LDS_LIMIT, "rx_chain_task5: internal: chain_layout asks for %zu bytes of LDS, the route counted %zu",
            dyn, route_lds);                              // (generic_lds_bytes of chain_route.hpp mirrors chain_layout; the route refused a frame beyond the limit)
+  if (scope) {                                                         // the Scope variant: with a density the grid behind the groups' regions
+    const size_t dyn_s = scope5_lds_total(dyn, scope->bins);
+    OFDM_HIP(hipFuncSetAttribute((const void*)rx_chain_kernel<T, N, MerSums, Scope5Out>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_s));
+    hipLaunchKernelGGL((rx_chain_kernel<T, N, MerSums, Scope5Out>), dim3(cdiv_u(n_frames, FPW)), dim3(fft_wg_threads(N)), dyn_s, ctx().stream,
+                       P, (const cx<T>*)rx, n_frames, (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs,
+                       (cx<T>*)h_out, (int32_t*)idx_out, MerSums{mer}, scope5_out(*scope, dyn));
+    return check_launch("rx_chain_kernel");
+  }
   if (mer) {                                                           // the MER variant
     OFDM_HIP(hipFuncSetAttribute((const void*)rx_chain_kernel<T, N, MerSums>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     hipLaunchKernelGGL((rx_chain_kernel<T, N, MerSums>), dim3(cdiv_u(n_frames, FPW)), dim3(fft_wg_threads(N)), dyn, ctx().stream,
@@ -688,8 +710,21 @@ int ofdm_rx_plan_last_task4_ms(ofdm_rx_plan* pl, float* ms5) {
 
 int64_t ofdm_rx_plan_frame_bytes(const ofdm_rx_plan* pl) { return pl ? (int64_t)pl->frame_words * 4 : 0; }
 
+// The route a constellation capture of this plan takes -- that of the call with the MER sums wanted -- as what the density
+// check needs of it: the symbol stage (SYM_*) and its dynamic LDS without a grid.  False where the receiver itself refuses
+// the plan (it then says so in its own words).
+extern "C++" bool ofdm::rx_chain_task5_scope_stage(const ofdm_rx_plan* pl, int* stage, size_t* stage_lds) {
+  ChainRoute route;
+  const char* why = nullptr;
+  if (chain_route_choose(chain_shape(pl, true), route, &why) != ROUTE_OK) return false;
+  *stage = route.symbols;
+  *stage_lds = scope5_stage_lds(route, pl->nd, pl->n_symb);
+  return true;
+}
+
 extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
-                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr) {
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr,
+                           const ScopeCall* scope) {
   OFDM_TRY(ensure_init());
   OFDM_ARG(pl && rx && n_frames >= 0, "rx_chain_task5: bad arguments");
   OFDM_PLAN_DEVICE(pl);
@@ -701,7 +736,8 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   // stage that refuses used to leave them
   ChainRoute route;
   const char* why = nullptr;
-  const int refusal = chain_route_choose(chain_shape(pl, mer_sums_out != nullptr), route, &why);
+  // (a capture takes the route of the same call with the MER sums wanted: its kernels are Scope variants of the MER builds)
+  const int refusal = chain_route_choose(chain_shape(pl, mer_sums_out != nullptr || scope != nullptr), route, &why);
   const bool generic = route.entry == ENTRY_GENERIC;
   if (refusal != REFUSE_MMSE_ENTRY) {
     pl->last_fast = generic ? 0 : 1;
@@ -731,6 +767,15 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
     default:
       OFDM_ARG(false, "rx_chain_task5: internal: refusal %d of the route has no message", refusal);
   }
+  // the capture of the call, behind every check and refusal of the call without one: the window's own arguments, and -- a
+  // uint32 bin of a workgroup's grid must not wrap -- at most 2^32 - 1 points in one call (the sweep caps its chunk)
+  if (scope && scope->iq) {
+    ScopeWhy sw;
+    OFDM_TRY(scope_refused(scope5_iq_check(scope->iq_first, scope->iq_count, (int64_t)pl->nd * pl->n_symb, sw), sw));
+  }
+  if (scope && scope->bins)
+    OFDM_ARG(n_frames <= (int64_t)(0xffffffffull / (unsigned long long)((int64_t)pl->nd * pl->n_symb)),
+             "rx_chain_task5: internal: a density over %lld frames could wrap a 32-bit bin", (long long)n_frames);
   const size_t cs = csize(flags);
   const size_t frame_samples = (size_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   const size_t fb = (size_t)pl->frame_words * 4;
@@ -744,6 +789,15 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   OFDM_TRY(st.out(index_out, sizeof(int32_t) * (size_t)pl->taps * n_frames, &didx));
   void* dmer;
   OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * (size_t)n_frames, &dmer));
+  // a capture without the MER sums: the Scope variants sit on the MER builds, whose sums then go to scratch.  The window is
+  // staged like every other output; the density's accumulators are device memory whatever the flags (the sweep owns them)
+  ScopeCall sc;
+  if (scope) {
+    sc = *scope;
+    if (!dmer) OFDM_TRY(st.scratch(sizeof(double) * 2 * (size_t)n_frames, &dmer));
+    if (sc.iq) OFDM_TRY(st.out(scope->iq, cs * (size_t)sc.iq_count * (size_t)n_frames, &sc.iq));
+  }
+  const ScopeCall* dsc = scope ? &sc : nullptr;
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
   // DeScrambler of the plan: fused into the pack stage of the wave-per-frame symbol kernel; every other path -- and the wave
@@ -760,6 +814,7 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
     FastPlanView pv;
     make_plan_view(pl, pv, ls_inv_snr);
     pv.route = &route;
+    pv.scope = dsc;
     if (descr_pass) pv.descr = 0;
     if (route.entry == ENTRY_FAST) OFDM_TRY(chain_fast_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, mer));
     else OFDM_TRY(chain_split_run(pv, tw, drx, n_frames, cb, cr, ce, dh, didx, (const int32_t*)pl->d_pc0, mer));
@@ -768,8 +823,8 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
   }
   if (pl->timing) OFDM_HIP(hipEventRecord(pl->ev[0], ctx().stream));
 #define CALL(NN)                                                                                        \
-  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds)));  \
-  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds)));
+  if (pl->f64) OFDM_TRY((launch_chain<double, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds, dsc)));  \
+  else OFDM_TRY((launch_chain<float, NN>(pl, tw, drx, n_frames, cb, cr, ce, dh, didx, mer, route.generic_lds, dsc)));
   OFDM_FFT_DISPATCH(pl->nfft, CALL)
 #undef CALL
   if (descr_pass) OFDM_TRY(descr_pass_run(pl, craw, dbits, dref, derr, n_frames));
@@ -780,6 +835,15 @@ extern "C++" int ofdm::rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int6
 int ofdm_rx_chain_task5_ex(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
                            uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags) {
   return rx_chain_task5_run(pl, rx, n_frames, bits_out, ref_bits, errors_out, h_out, index_out, mer_sums_out, flags, -1.0);
+}
+
+int ofdm_rx_chain_task5_iq(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
+                           uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int64_t iq_first,
+                           int64_t iq_count, void* iq_out, int flags) {
+  ScopeCall sc;
+  sc.iq_first = iq_first; sc.iq_count = iq_count; sc.iq = iq_out;
+  return rx_chain_task5_run(pl, rx, n_frames, bits_out, ref_bits, errors_out, h_out, index_out, mer_sums_out, flags, -1.0,
+                            iq_out ? &sc : nullptr);
 }
 
 int ofdm_rx_chain_task5(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out,

@@ -49,6 +49,7 @@ __device__ __forceinline__ cx<float> cp_w32(int m) {
 
 // Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the lane decides, the
 // wave butterfly, the four wave partials in index order.  An empty Mer is the kernel as it always was.
+// A Scope5Out behind the MerSums: the Scope variant on top of the MER one (constellation capture, chain_fast_core.hpp).
 template <int BA, bool HEXT, typename... Mer>
 __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<float> P, unsigned codes_bytes,
                                                                   const cx<float>* __restrict__ rx, int64_t n_frames,
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
                                                                   int32_t* __restrict__ index_out, DemapTable<float> tab,
                                                                   Mer... mer) {
   using T = float;
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = sizeof...(Mer) >= 1, SCOPE = sizeof...(Mer) == 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int tap_i[FAST_MAXT];
   const int lane = threadIdx.x & 63;
@@ -106,6 +107,10 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
     mt = mer_tab;
     mw = &mer_w[0][0];
   }
+  const Scope5Out sc = scope5_out_of(mer...);                            // SCOPE: the capture, the workgroup's grid, this thread's
+  uint32_t* grid = nullptr;                                            // dropped points
+  unsigned sc_dropped = 0;
+  if constexpr (SCOPE) grid = scope5_grid_init(sc, smem, threadIdx.x, 256);
   __syncthreads();
   bool any_data = false;
 #pragma unroll
@@ -183,6 +188,8 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     __syncthreads();                                                   // the previous frame's last pack / exchange reads are done
     cx<T> geq[8];
+    cx<T>* iq_frame = nullptr;
+    if constexpr (SCOPE) { if (sc.iq) iq_frame = (cx<T>*)sc.iq + f * sc.iq_count; }
     // ---- G = 1 ./ H on this lane's carriers
     if constexpr (HEXT) {
 #pragma unroll
@@ -243,6 +250,7 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
         const int code = slice_symbol<T, BA>(tab, z);
         codes0[d] = (uint8_t)code;
         if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+        if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, d, z);
       }
     }
     unsigned err = 0;
@@ -287,6 +295,7 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
             const int code = slice_symbol<T, BA>(tab, z);
             cslot[d] = (uint8_t)code;
             if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+            if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, sy * nd + d, z);
           }
         }, [&](int kb) { if (fetch) load_quarter(nsrc, kb); });
       }
@@ -308,13 +317,18 @@ __global__ __launch_bounds__(256, 2) void rx_symbols_coop4_kernel(FastParams<flo
         *(double2*)(mer_out + 2 * f) = make_double2(((mw[0] + mw[2]) + mw[4]) + mw[6], ((mw[1] + mw[3]) + mw[5]) + mw[7]);
     }
   }
+  if constexpr (SCOPE) {
+    __syncthreads();                                                   // every wavefront's last point is counted
+    scope5_grid_flush(sc, grid, sc_dropped, threadIdx.x, 256);
+  }
 }
 
 int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                            const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   OFDM_NEEDS_ROUTE(pv);
   const unsigned codes_bytes = (unsigned)((pv.nd + 63) & ~31);
-  const unsigned lds = (unsigned)pv.route->symbol_lds;              // CP_OFF_CODES + 2 * codes_bytes
+  const ScopeCall* scope = pv.scope;                                // (with a density the grid lies behind the stage's regions)
+  const unsigned lds = (unsigned)scope5_lds_total(pv.route->symbol_lds, scope ? scope->bins : 0);   // CP_OFF_CODES + 2 * codes_bytes
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const bool mmse = pv.mmse();
@@ -330,6 +344,7 @@ int chain_coop_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
     return with_bool(mmse, [&](auto HX) {
       constexpr int B = decltype(BA)::value;
       constexpr bool H = decltype(HX)::value;
+      if (scope) return launch(rx_symbols_coop4_kernel<B, H, MerSums, Scope5Out>, MerSums{mer}, scope5_out(*scope, pv.route->symbol_lds));
       if (mer) return launch(rx_symbols_coop4_kernel<B, H, MerSums>, MerSums{mer});
       return launch(rx_symbols_coop4_kernel<B, H>);
     });

@@ -190,6 +190,7 @@ __global__ __launch_bounds__(256) void omp_batch_kernel(FastParams<T> P, OmpLayo
 // 256-thread workgroups per CU for the pruned Nfft <= 2048 instantiations, which is where the benchmark runs)
 // Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the lane decides, the
 // wave butterfly, the NW wave partials in index order.  An empty Mer is the kernel as it always was.
+// A Scope5Out behind the MerSums: the Scope variant on top of the MER one (constellation capture, chain_fast_core.hpp).
 template <typename T, int NW, bool PRUNE2, int BA, bool HEXT = false, typename... Mer>
 __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 4) : 3) : 2) void rx_symbols_kernel(FastParams<T> P, const cx<T>* __restrict__ rx,
                                                              int64_t n_frames, uint32_t* __restrict__ bits_out,
@@ -198,7 +199,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
                                                              cx<T>* __restrict__ h_out, int32_t* __restrict__ index_out,
                                                              DemapTable<T> tab, Mer... mer) {
   constexpr int N = 512 * NW;
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = sizeof...(Mer) >= 1, SCOPE = sizeof...(Mer) == 2;
   constexpr int NOUT = PRUNE2 ? 2 : 8;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cx<T>* lwv = (cx<T>*)smem;                                           // [NW][WAVE_LDS_ELEMS]
@@ -243,10 +244,16 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
     mt = mer_tab;
     mw = &mer_w[0][0];
   }
+  const Scope5Out sc = scope5_out_of(mer...);                            // SCOPE: the capture, the workgroup's grid, this thread's
+  uint32_t* grid = nullptr;                                            // dropped points
+  unsigned sc_dropped = 0;
+  if constexpr (SCOPE) grid = scope5_grid_init(sc, smem, gid, 64 * NW);
   __syncthreads();
   cx<T> v[8], nx[8];
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     const cx<T>* frx = rx + f * (int64_t)Lsym * P.n_symb;
+    cx<T>* iq_frame = nullptr;
+    if constexpr (SCOPE) { if (sc.iq) iq_frame = (cx<T>*)sc.iq + f * sc.iq_count; }
     if (P.n_symb > 1) frame_load<T, NW>(nx, frx + Lsym + P.t_guard, gid, lane);
     if (gid == 0) sh_err = 0;
     // ---- H = fft(h)(1..N_carrier) from the taps; G = 1 ./ H           (OMP_estimate.m:36, equalize_signal.m:6)
@@ -302,6 +309,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
         const int code = slice_symbol<T, BA>(tab, z);
         codes[dd[t]] = (uint8_t)code;
         if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+        if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, dd[t], z);
       }
     // ---- symbols 2..S: the next symbol's samples are in flight while this one is transformed.  Measured and
     //      rejected: alternating two register sets instead of copying (-1 workgroup of occupancy), two symbols in
@@ -326,6 +334,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
             const int code = slice_symbol<T, BA>(tab, z);
             codes[s * nd + dd[t]] = (uint8_t)code;
             if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+            if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, s * nd + dd[t], z);
           }
       }
     }
@@ -354,6 +363,7 @@ __global__ __launch_bounds__(64 * NW, sizeof(T) == 4 ? (PRUNE2 ? (NW <= 4 ? 5 : 
     }
     __syncthreads();                     // codes / sh_err are reused by the next frame
   }
+  if constexpr (SCOPE) scope5_grid_flush(sc, grid, sc_dropped, gid, 64 * NW);   // (the last frame ended on a barrier)
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -466,7 +476,8 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
     }
   }
   {
-    const size_t dyn = route.symbol_lds;                           // (within its 150 KiB: the route refuses a frame beyond)
+    const ScopeCall* scope = pv.scope;                             // (with a density the grid lies behind the stage's regions)
+    const size_t dyn = scope5_lds_total(route.symbol_lds, scope ? scope->bins : 0);   // (within its 150 KiB: the route refuses a frame beyond)
     // persistent grid = CUs x resident workgroups per CU (from the occupancy API: registers + LDS);
     // workgroups are independent, so an optimistic answer only queues a few of them.
     auto launch = [&](auto kern, auto... mer_arg) -> int {          // (mer_arg: MerSums for a MER variant)
@@ -481,6 +492,7 @@ static int launch_fast(const FastPlanView& pv, const void* tw, const void* rx, i
       return with_bool(mmse, [&](auto HX) {
         constexpr int B = decltype(BA)::value;
         constexpr bool H = decltype(HX)::value;
+        if (scope) return launch(rx_symbols_kernel<T, NW, PRUNE2, B, H, MerSums, Scope5Out>, MerSums{mer}, scope5_out(*scope, route.symbol_lds));
         if (mer) return launch(rx_symbols_kernel<T, NW, PRUNE2, B, H, MerSums>, MerSums{mer});
         return launch(rx_symbols_kernel<T, NW, PRUNE2, B, H>);
       });

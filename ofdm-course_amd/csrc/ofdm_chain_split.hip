@@ -484,6 +484,7 @@ static int demod_keep8192_run(const void* y, void* x, int64_t n_symb, int t_guar
 // Sixteen wavefronts per CU (two 512-thread workgroups, 128 VGPRs) against the eight of rx_symbols_coop4_kernel (250 VGPRs, 79 KB).
 // Mer (MerSums, chain_fast_core.hpp): the MER variant -- lane partials in double over the data points the thread decides, the
 // wave butterfly, the eight wave partials in index order.  An empty Mer is the kernel as it always was.
+// A Scope5Out behind the MerSums: the Scope variant on top of the MER one (constellation capture, chain_fast_core.hpp).
 template <int BA, bool HEXT, typename... Mer>
 __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float> P, const cx<float>* __restrict__ rx,
                                                                const cx<float>* __restrict__ tw4096, const cx<float>* __restrict__ tw8192,
@@ -493,7 +494,7 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
                                                                DemapTable<float> tab, Mer... mer) {
   using T = float;
   constexpr int NW = 8, N = 8192, NOUT = 2;
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = sizeof...(Mer) >= 1, SCOPE = sizeof...(Mer) == 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   cx<T>* lwv = (cx<T>*)smem;                                   // [NW][WAVE_LDS_ELEMS]
   cx<T>* const ex = lwv;
@@ -539,9 +540,15 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
     mt = mer_tab;
     mw = &mer_w[0][0];
   }
+  const Scope5Out sc = scope5_out_of(mer...);                        // SCOPE: the capture, the workgroup's grid, this thread's
+  uint32_t* grid = nullptr;                                        // dropped points
+  unsigned sc_dropped = 0;
+  if constexpr (SCOPE) grid = scope5_grid_init(sc, smem, gid, 512);
   __syncthreads();
   for (int64_t f = blockIdx.x; f < n_frames; f += gridDim.x) {
     const cx<T>* frx = rx + f * (int64_t)Lsym * P.n_symb;
+    cx<T>* iq_frame = nullptr;
+    if constexpr (SCOPE) { if (sc.iq) iq_frame = (cx<T>*)sc.iq + f * sc.iq_count; }
     if (gid == 0) sh_err = 0;
     if (!HEXT && gid < taps) {
       const int idx = P.tap_idx[f * taps + gid];
@@ -585,6 +592,7 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
         const int code = slice_symbol<T, BA>(tab, z);
         codes[dd[t]] = (uint8_t)code;
         if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+        if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, dd[t], z);
       }
     // ---- symbols 2..S
     for (int s = 1; s < P.n_symb; ++s) {
@@ -613,6 +621,7 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
             const int code = slice_symbol<T, BA>(tab, z);
             codes[s * nd + dd[2 * t]] = (uint8_t)code;
             if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+            if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, s * nd + dd[2 * t], z);
           }
       }
       // odd bins
@@ -630,6 +639,7 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
             const int code = slice_symbol<T, BA>(tab, z);
             codes[s * nd + dd[2 * t + 1]] = (uint8_t)code;
             if constexpr (MER) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+            if constexpr (SCOPE) scope5_point<T>(sc, iq_frame, grid, sc_dropped, s * nd + dd[2 * t + 1], z);
           }
       }
     }
@@ -655,12 +665,14 @@ __global__ __launch_bounds__(512, 4) void rx_symbols_r2_kernel(FastParams<float>
     }
     __syncthreads();                     // codes / sh_err are reused by the next frame
   }
+  if constexpr (SCOPE) scope5_grid_flush(sc, grid, sc_dropped, gid, 512);   // (the last frame ended on a barrier)
 }
 
 static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>& P, const void* rx, int64_t n_frames, void* bits,
                                 const void* ref, void* errs, void* h_out, void* idx_out, double* mer) {
   OFDM_NEEDS_ROUTE(pv);
-  const size_t lds = pv.route->symbol_lds;
+  const ScopeCall* scope = pv.scope;                             // (with a density the grid lies behind the stage's regions)
+  const size_t lds = scope5_lds_total(pv.route->symbol_lds, scope ? scope->bins : 0);
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const void *tw4 = nullptr, *tw8 = nullptr;
@@ -680,6 +692,7 @@ static int chain_r2_symbols_run(const FastPlanView& pv, const FastParams<float>&
     return with_bool(mmse, [&](auto HX) {
       constexpr int B = decltype(BA)::value;
       constexpr bool H = decltype(HX)::value;
+      if (scope) return launch(rx_symbols_r2_kernel<B, H, MerSums, Scope5Out>, MerSums{mer}, scope5_out(*scope, pv.route->symbol_lds));
       if (mer) return launch(rx_symbols_r2_kernel<B, H, MerSums>, MerSums{mer});
       return launch(rx_symbols_r2_kernel<B, H>);
     });
@@ -818,7 +831,7 @@ static int split_run(const FastPlanView& pv, const void* tw, const void* rx, int
   else OFDM_TRY(omp_stage_run<T>(P, pv.nfft, n_frames, route.omp_taken, pv.omp_out));
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[2], st));
   OFDM_TRY(eq_demap_run<T>(pv, P, xk, pv.n_carrier, mmse, n_frames, bits, ref, errs, h_out, idx_out, nullptr, 0, 0, 0,
-                           mer));                                      // (+ the MER_func sums of the whole RX_IQ: skip 0)
+                           mer, pv.scope));                            // (+ the MER_func sums of the whole RX_IQ: skip 0)
   if (pv.ev) OFDM_HIP(hipEventRecord(pv.ev[3], st));
   return OFDM_OK;
 }

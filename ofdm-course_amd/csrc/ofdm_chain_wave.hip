@@ -77,7 +77,9 @@ __device__ __forceinline__ int slice_wave(const DemapTable<float>& tab, const fl
 // Mer (MerSums, chain_fast_core.hpp): the MER variant -- the sums of MER_func.m:19-23 over every data point the kernel decides,
 // lane partials in double, the wave butterfly at the end of a frame, lane 0 stores the frame's pair.  It is built for two
 // workgroups per CU (<= 256 VGPRs): at the 168 of three the four live doubles spilled ~230 registers.  An empty Mer is the
-// kernel as it always was.
+// kernel as it always was.  A Scope5Out behind the MerSums: the Scope variant on top of the MER one (constellation capture,
+// chain_fast_core.hpp) -- the grid is shared by the workgroup's wavefronts, and the kernel's second workgroup barrier stands in
+// front of its flush, after every wavefront's last frame.
 template <int BA, bool HEXT, int WPB = WV_WPB, int ABL = 0, bool WBUF = true, int LUT = 2, int SKIP = 0, bool DESCR = false,
           typename... Mer>
 __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) void rx_symbols_wave_kernel(FastParams<float> P, WaveLayout lay,
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
                                                                   int32_t* __restrict__ index_out, DemapTable<float> tab,
                                                                   Mer... mer) {
   using T = float;
-  constexpr bool MER = sizeof...(Mer) == 1;
+  constexpr bool MER = sizeof...(Mer) >= 1, SCOPE = sizeof...(Mer) == 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // Compile-time LDS layout (WV_OFF_*): every address below is one of four per-lane registers (lane8, trl, t1r, t2w) plus
   // an immediate offset of the DS instruction -- run-time table offsets cost a VGPR each, and the kernel has none to spare.
@@ -138,7 +140,11 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
     mer_tab_fill<T>(tab, mer_tab, threadIdx.x);
     mt = mer_tab;
   }
-  __syncthreads();                                                     // the only workgroup barrier of the kernel
+  const Scope5Out sc = scope5_out_of(mer...);                            // SCOPE: the capture, the workgroup's grid, this lane's
+  uint32_t* grid = nullptr;                                            // dropped points
+  unsigned sc_dropped = 0;
+  if constexpr (SCOPE) grid = scope5_grid_init(sc, smem, threadIdx.x, 64 * WPB);
+  __syncthreads();                                                     // the only workgroup barrier of the kernel (SCOPE: but one)
   // wave-private region: transposes [576 complex] | 64 spare 8-byte slots | codes
   const unsigned wbase = WV_OFF_WAVE + (unsigned)wave * lay.wave_bytes;
   unsigned char* const trl = smem + wbase + lane8;
@@ -152,6 +158,11 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
   auto mer_take = [&](int t, int code, cx<T> z, double& s1, double& s2) __attribute__((always_inline)) {
     const unsigned d = (*(const unsigned*)(smem + WV_OFF_DD + 512 * (t >> 1) + lane8) >> (16 * (t & 1))) & 0xffffu;
     if (d != 0xffffu) mer_add(mer_ideal<T, BA>(tab, mt, code), z, s1, s2);
+  };
+  // SCOPE: the same point by its IQ index i0 + data position (i0 = symbol * nd)
+  auto scope_take = [&](int t, cx<T>* iq_frame, int i0, cx<T> z) __attribute__((always_inline)) {
+    const unsigned d = (*(const unsigned*)(smem + WV_OFF_DD + 512 * (t >> 1) + lane8) >> (16 * (t & 1))) & 0xffffu;
+    if (d != 0xffffu) scope5_point<T>(sc, iq_frame, grid, sc_dropped, i0 + (int)d, z);
   };
   // LDS addresses of the two transposes
   cx<T>* const t1w = (cx<T>*)trl;                                                              // + 72 c
@@ -230,12 +241,15 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
     }
     // ---- symbol 1 from the stash of the pilot stage
     double s1 = 0, s2 = 0;                                             // MER sums of this lane's points
+    cx<T>* iq_frame = nullptr;
+    if constexpr (SCOPE) { if (sc.iq) iq_frame = (cx<T>*)sc.iq + f * sc.iq_count; }
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
       const cx<T> z = (kk_of(t) < n_carrier ? P.stash[f * n_carrier + kk_of(t)] : mk<T>(0, 0)) * geq[t];
       const int code = slice_wave<BA, LUT>(tab, lut, z);
       *code_ptr(codes, t) = (uint8_t)code;
       if constexpr (MER) mer_take(t, code, z, s1, s2);
+      if constexpr (SCOPE) scope_take(t, iq_frame, 0, z);
     }
     unsigned err = 0;
     int slot = 1;                                                      // symbols in the codes buffer
@@ -324,6 +338,7 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
               const int code = slice_wave<BA, LUT>(tab, lut, z);
               *code_ptr(cslot, 2 * r + kb) = (uint8_t)code;
               if constexpr (MER) mer_take(2 * r + kb, code, z, s1, s2);
+              if constexpr (SCOPE) scope_take(2 * r + kb, iq_frame, s * nd, z);
             }
           }
         }
@@ -383,6 +398,10 @@ __global__ __launch_bounds__(64 * WPB, sizeof...(Mer) ? 2 : (WPB == 8 ? 4 : 3)) 
       f += n_waves;
     }
   }
+  if constexpr (SCOPE) {
+    __syncthreads();                                                   // every wavefront is done with its frames
+    scope5_grid_flush(sc, grid, sc_dropped, threadIdx.x, 64 * WPB);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -400,12 +419,14 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
   DemapTable<float> tab;
   fill_demap_table<float>(*pv.dict, *pv.cinfo, tab);
   const bool mmse = pv.mmse();
-  auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant)
-    int per_cu = resident_blocks_per_cu((const void*)kern, 64 * wpb, lay.total);
+  const ScopeCall* scope = pv.scope;                                // (with a density the grid lies behind the stage's regions)
+  const size_t dyn = scope5_lds_total(lay.total, scope ? scope->bins : 0);
+  auto launch = [&](auto kern, auto... mer_arg) -> int {            // (mer_arg: MerSums for a MER variant, + Scope5Out for a Scope one)
+    int per_cu = resident_blocks_per_cu((const void*)kern, 64 * wpb, dyn);
     if (const char* e = getenv("OFDM_WAVE_WG_PER_CU")) per_cu = std::max(1, atoi(e));
     const int64_t want = (n_frames + wpb - 1) / wpb;
     const unsigned grid = (unsigned)std::min<int64_t>(want, (int64_t)ctx().num_cu * per_cu);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), lay.total, ctx().stream, P, lay, (const cx<float>*)rx, n_frames,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpb), dyn, ctx().stream, P, lay, (const cx<float>*)rx, n_frames,
                        (uint32_t*)bits, (const uint32_t*)ref, (uint32_t*)errs, (cx<float>*)h_out, (int32_t*)idx_out, tab,
                        mer_arg...);
     return OFDM_OK;
@@ -424,6 +445,12 @@ int chain_wave_symbols_run(const FastPlanView& pv, const FastParams<float>& P, c
     if (mer) return with_bool(mmse, [&](auto HX) {
       constexpr bool H = decltype(HX)::value;
       const MerSums ms{mer};
+      if (scope) {
+        const Scope5Out so = scope5_out(*scope, lay.total);
+        if (skip0) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 1, false, MerSums, Scope5Out>, ms, so);
+        if (skip02) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 5, false, MerSums, Scope5Out>, ms, so);
+        return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 0, false, MerSums, Scope5Out>, ms, so);
+      }
       if (skip0) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 1, false, MerSums>, ms);
       if (skip02) return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 5, false, MerSums>, ms);
       return launch(rx_symbols_wave_kernel<B, H, 4, 0, true, 2, 0, false, MerSums>, ms);

@@ -77,8 +77,11 @@ struct ofdm_rx_plan {
 // ofdm_chain.hip: DeScrambler as a pass over the packed decisions (every path but the wave-per-frame symbol kernel)
 namespace ofdm {
 // ofdm_chain.hip: the body of ofdm_rx_chain_task5_ex; ls_inv_snr as in make_plan_view (the BER sweeps: the point's SNR)
+// scope = the constellation capture of the call (ofdm_rx_chain_task5_iq, ofdm_ber_sweep_task5_scope), or null
 int rx_chain_task5_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
-                       uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr);
+                       uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out, int flags, double ls_inv_snr,
+                       const ScopeCall* scope = nullptr);
+bool rx_chain_task5_scope_stage(const ofdm_rx_plan* pl, int* stage, size_t* stage_lds);
 // ofdm_chain_t4.hip: the body of ofdm_rx_chain_task4_ex / _iq; scope = the constellation capture of the call, or null
 int rx_chain_task4_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int time_desync, int freq_desync, int mp_desync,
                        uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,

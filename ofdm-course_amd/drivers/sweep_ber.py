@@ -41,6 +41,14 @@ rate.  The plan's pilots are a sorted random mask of NP carriers in 1..N_carrier
 (`RxPlan.set_omp_route`): omp_batch_kernel while its state fits the LDS, else omp_wide_kernel.  The JSON line carries "pilots":
 "random", "n_pilots", "mask_seed", "K" and "omp_route", the kernel the OMP stage ran.
 
+--fused --density BINS [--half-width L] (C5 / M): per point the constellation of the receiver as a density, a BINS x BINS grid
+on [-L, L)^2 of every equalised point RX_IQ of the point's frames (rows: im, columns: re; the scatter of
+T5/Main_model_Task_5.m:248-251 over the points MER_func sums at :282), accumulated on the device by the symbol stage
+(`RxPlan.ber_sweep(density=...)`, ofdm_ber_sweep_task5_scope).  L defaults to 1.5 max|dict|.  The JSON line adds `density`
+(one grid per point), `density_dropped` (points with a non-finite coordinate, not binned), `density_points` (the points counted
+per SNR), `density_bins` and `half_width`; the grids are integers and travel in the int64 all-reduce.  With --fading,
+--estimator mmse-ls and --random-pilots as without it.  (The Task-4 receiver's density is `task4_mer --density`.)
+
     python -m ofdm_course_amd.drivers.sweep_ber --config C5 --batches 4 --frames-per-tile 64
     python -m ofdm_course_amd.drivers.sweep_ber --config C3 --batches 4 --frames-per-tile 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \\
@@ -88,6 +96,18 @@ def check_pilots(config, estimator, fused, random_pilots, dictionary):
     return None
 
 
+def check_density(config, fused, density, half_width):
+    """What --density / --half-width need; the text of the refusal, or None."""
+    if half_width is not None and density is None:
+        return "--half-width needs --density"
+    if density is None:
+        return None
+    if config == "C3" or not fused:
+        return ("--density needs --fused at config C5 or M (the Task-5 receiver's sweep); the Task-4 receiver's density is "
+                "`python -m ofdm_course_amd.drivers.task4_mer --density`")
+    return None
+
+
 def apply_pilots(cfg, random_pilots, mask_seed, dictionary):
     """The frame configuration with the random mask (T5/Task5_part2.m:58-64) and / or the dictionary of all Nfft delays."""
     from ofdm_course_amd.drivers.task5_part2 import random_pilot_layout
@@ -111,8 +131,9 @@ def make_sweep_plan(cfg, lib, precision, device_index, dictionary="comb"):
 
 def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32", seed=7, estimator="omp",
         rank=0, world=1, device_index=0, backend="nccl", fused=False, mer=False, fading=None, nmse=False,
-        random_pilots=None, mask_seed=1, dictionary="comb"):
-    """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}.
+        random_pilots=None, mask_seed=1, dictionary="comb", density=None, half_width=None):
+    """Returns (on every rank) the reduced table {"SNRs", "errors", "bits", "BER", ...}; with density=BINS also density
+    [n, BINS, BINS] (rows: im, columns: re), density_dropped [n], density_points, density_bins and half_width.
     Per batch of the tiles this rank holds, one call decodes one tile (rx_chain_task5 on make_frames_device frames, or
     ber_sweep for an MMSE plan, which is built for one SNR) or all of the batch's points (ber_sweep with --fused,
     ber_sweep_task4 at C3)."""
@@ -122,7 +143,8 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     from ofdm_course_amd import sweep
     from ofdm_course_amd.drivers.common import fading_profile
 
-    bad = check_fading(config, estimator, fused, fading, nmse) or check_pilots(config, estimator, fused, random_pilots, dictionary)
+    bad = check_fading(config, estimator, fused, fading, nmse) or check_pilots(config, estimator, fused, random_pilots, dictionary) or \
+        check_density(config, fused, density, half_width)
     if bad:
         raise ValueError(bad)
     ofdm.init(device_index)
@@ -140,7 +162,14 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
     # int64 columns: bit errors (+ C3: frames with receiver status 0, 1, -1, -2); float64 columns: (C3: the sum of
     # |FreqOffset + IFO - Freq_Shift|) (+ mer: the MER_func sums s1, s2) (+ nmse: the channel-estimate error sums) -- one
     # device table each, read once
-    cnt = torch.zeros((n, 5 if task4 else 1), dtype=torch.int64, device=dev)
+    # (+ density: the bins x bins grid of the point and its dropped points, behind them)
+    c_dens = 5 if task4 else 1
+    n_dens = 0
+    if density is not None:
+        density = int(density)
+        n_dens = max(density, 0) ** 2
+        half_width = 1.5 * float(np.max(np.abs(ofdm.constellation_func(cfg.Constellation)[0]))) if half_width is None else float(half_width)
+    cnt = torch.zeros((n, c_dens + (n_dens + 1 if density is not None else 0)), dtype=torch.int64, device=dev)
     c_mer = int(task4)
     c_nmse = c_mer + (2 if mer else 0)
     flt = torch.zeros((n, c_nmse + int(nmse)), dtype=torch.float64, device=dev)
@@ -170,8 +199,13 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
                 if estimator == "mmse":
                     plan.set_mmse(hh, float(snrs[pts[0]]))
                 chan = dict(fading=profile, want_nmse=nmse) if fading else dict(h=h)
+                if density is not None:
+                    chan["density"] = dict(bins=density, half_width=half_width, skip=0)
                 out = plan.ber_sweep(snrs[pts], frames_per_tile, seeds=seeds, frame0=stream0, device=dev, want_mer=mer, **chan)
                 errors, mer_sums = out["errors"], out.get("mer_sums")
+                if density is not None:
+                    cnt[pts, c_dens:c_dens + n_dens] += out["density"].view(torch.int64).reshape(len(pts), n_dens)
+                    cnt[pts, c_dens + n_dens] += out["density_dropped"].view(torch.int64)
                 if nmse:
                     flt[pts, c_nmse] += out["nmse_sums"]
             else:
@@ -221,6 +255,11 @@ def run(config="C5", snrs=None, batches=2, frames_per_tile=32, precision="fp32",
         m = sums[:, c_mer:c_mer + 2]
         res["mer_sums"] = m.tolist()
         res["MER_dB"] = (10.0 * np.log10(m[:, 0] / m[:, 1])).tolist()
+    if density is not None:
+        res.update(density=total.errors[:, c_dens:c_dens + n_dens].reshape(n, density, density).tolist(),
+                   density_dropped=total.errors[:, c_dens + n_dens].tolist(),
+                   density_points=batches * frames_per_tile * plan.frame_bits // plan.bps, density_bins=density,
+                   half_width=half_width)
     return res
 
 
@@ -245,6 +284,9 @@ def parser():
     ap.add_argument("--mask-seed", type=int, default=1, help="seed of the random pilot mask")
     ap.add_argument("--dictionary", choices=["comb", "full"], default="comb",
                     help="full: K = Nfft, all delays (Task5_part2.m:181-184); the plan's OMP route is then 'auto'")
+    ap.add_argument("--density", type=int, default=None, metavar="BINS",
+                    help="with --fused at C5 / M: per point a BINS x BINS density of the equalised points (8, 16, 32, 64 or 128)")
+    ap.add_argument("--half-width", type=float, default=None, metavar="L", help="with --density: the grid spans [-L, L)^2 (default 1.5 max|dict|)")
     ap.add_argument("--json", default=None)
     return ap
 
@@ -254,7 +296,8 @@ def parse_args(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     bad = check_fading(a.config, a.estimator, a.fused, a.fading, a.nmse) or \
-        check_pilots(a.config, a.estimator, a.fused, a.random_pilots, a.dictionary)
+        check_pilots(a.config, a.estimator, a.fused, a.random_pilots, a.dictionary) or \
+        check_density(a.config, a.fused, a.density, a.half_width)
     if bad:
         ap.error(bad)
     return a
@@ -276,7 +319,8 @@ def main():
             dist.init_process_group(a.backend)
     res = run(a.config, a.snrs, a.batches, a.frames_per_tile, a.precision, estimator=a.estimator, rank=rank, world=world,
               device_index=dev_index, backend=a.backend, fused=a.fused, mer=a.mer, fading=a.fading, nmse=a.nmse,
-              random_pilots=a.random_pilots, mask_seed=a.mask_seed, dictionary=a.dictionary)
+              random_pilots=a.random_pilots, mask_seed=a.mask_seed, dictionary=a.dictionary, density=a.density,
+              half_width=a.half_width)
     if rank == 0:
         text = json.dumps(res)
         if a.json:
