@@ -665,6 +665,33 @@ int ofdm_rx_chain_task5_ex(ofdm_rx_plan* plan, const void* rx, int64_t n_frames,
 int ofdm_rx_chain_task5_iq(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, uint8_t* bits_out, const uint8_t* ref_bits,
                            uint32_t* errors_out, void* h_out, int32_t* index_out, double* mer_sums_out /* [n_frames][2] */,
                            int64_t iq_first, int64_t iq_count, void* iq_out /* [n_frames][iq_count] */, int flags);
+/* The PAPR / CCDF study of T2/Main_model_Task_2.m:69-97 over n_signals signals as one device-resident call.  A signal is
+ * frames_per_signal consecutive frames of the plan's geometry, concatenated (T2:64-68): payload -> [Scrambler per frame, register
+ * reset, T2:36-51] -> mapping -> OFDM_map_carriers -> OFDM_modulator (T2:53-68) -- the bit and symbol stages of
+ * ofdm_tx_frames_fused, no Noise and no channel.  Frame g of the call draws its payload from Philox stream frame0 + g, key `seed`,
+ * as the generator does; payload_bits, when given, replace the draw.  Every window of `window` samples of every signal
+ * (calculate_window_PAPR.m:8-14; windows never cross a signal's end) is counted by its value v = 10 log10(max |x|^2 / mean |x|^2)
+ * (calculatePAPR.m:4-10):
+ *   hist_out[n_bins]: bin floor((v - lo_db) * n_bins / (hi_db - lo_db)) for lo_db <= v < hi_db;
+ *   tails_out[3]: v < lo_db; v >= hi_db (+Inf included); NaN (the 0 / 0 of an all-zero window) -- the curves of
+ *   calculateCCDF.m:2-6 (T2:79,:82) follow from the counts;
+ *   signal_out[n_signals][2] (optional): max |x|^2 and sum |x|^2 of each signal, calculatePAPR's two figures (T2:72-73);
+ *   tx_out (optional, the plan's precision): the signals themselves, frame after frame.
+ * The outputs are overwritten, not accumulated: sum(hist) + sum(tails) = n_signals * (frames_per_signal * frame_samples - window
+ * + 1).  window: a power of two, 256 .. 8192, at most the signal's length; n_bins 1 .. 4096; lo_db < hi_db, finite.  The signals
+ * are generated in chunks of whole signals in the plan-owned workspace (max_frames_per_chunk > 0 caps the frames of a chunk,
+ * rounded down to whole signals, at least one); counts are integers, the maximum is order-free and the sums are taken in index
+ * order, so no output depends on the chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of
+ * the workspace.  hist_out, tails_out, signal_out, tx_out and payload_bits live where `flags` says. */
+int ofdm_papr_study(ofdm_rx_plan* plan, uint64_t seed, int64_t frame0, int64_t n_signals, int frames_per_signal,
+                    const uint8_t* scr_reg15,          /* HOST uint8[15] or NULL */
+                    const uint8_t* payload_bits,       /* optional: [n_signals*frames_per_signal][frame_bits], one byte per bit, where flags says */
+                    int window, int n_bins, double lo_db, double hi_db, int64_t max_frames_per_chunk,
+                    uint64_t* hist_out,                /* [n_bins] */
+                    uint64_t* tails_out,               /* [3]: below lo, at or above hi, NaN */
+                    double* signal_out,                /* optional [n_signals][2]: max |x|^2, sum |x|^2 */
+                    void* tx_out,                      /* optional [frame_samples x frames]: the signals themselves */
+                    int flags);
 
 #ifdef __cplusplus
 }

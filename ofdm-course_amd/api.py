@@ -880,6 +880,74 @@ class RxPlan:
             out["Time_Delay"], out["Freq_Shift"] = sto, cfo
         return out
 
+    def papr_study(self, n_signals, frames_per_signal=1, seed=1, frame0=0, Register=None, payload_bits=None, window=None,
+                   bins=dict(n=600, lo=0.0, hi=30.0), device=None, want_tx=False, max_frames_per_chunk=0):
+        """The PAPR / CCDF study of T2/Main_model_Task_2.m:69-97 over n_signals signals in one device-resident call
+        (ofdm_papr_study).  A signal is frames_per_signal consecutive frames of this plan, concatenated (T2:64-68): payload ->
+        [Scrambler(Register, .) per frame, T2:36-51] -> mapping -> OFDM_map_carriers -> OFDM_modulator, the frames of
+        tx_frames_fused(seed, frame0) before Noise.  payload_bits [n_signals * frames_per_signal, frame_bits] (0 / 1) replace the
+        Philox payload.  Every window of `window` samples (default Nfft; a power of two 256 .. 8192) of every signal is counted by
+        its calculate_window_PAPR value on the grid bins=dict(n=, lo=, hi=) in dB.
+        Returns dict(hist=[n] int64 (bin i: lo + i (hi - lo) / n <= v < the next edge), below, above (v >= hi), dropped (NaN: an
+        all-zero window), windows = the windows counted = hist.sum() + below + above + dropped, edges=[n + 1],
+        CCDF=[n + 1] = the share of the non-NaN windows with v >= edges[i] (calculateCCDF.m:2-6 on the grid), peak=[n_signals]
+        max |x|^2, power_sum=[n_signals] sum |x|^2, PAPR_dB=[n_signals] = calculatePAPR of each signal (T2:72-73)
+        (+ tx=[frames_per_signal * frame_samples, n_signals] with want_tx)); torch tensors on `device` (no host synchronisation;
+        below / above / dropped / windows then 0-d tensors) when it is given, numpy arrays and ints otherwise.  No output depends
+        on max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace, rounded down to whole signals)."""
+        try:
+            extra = set(bins) - {"n", "lo", "hi"}
+            nb, lo, hi = int(bins["n"]), float(bins["lo"]), float(bins["hi"])
+        except (TypeError, KeyError, ValueError, AttributeError):
+            raise OfdmError("papr_study: bins must be dict(n=, lo=, hi=)") from None
+        if extra:
+            raise OfdmError(f"papr_study: unknown bins keys {sorted(extra)}")
+        ns, fps = int(n_signals), int(frames_per_signal)
+        window = self.Nfft if window is None else int(window)
+        n_alloc, f_alloc, b_alloc = max(ns, 0), max(fps, 0), min(max(nb, 0), 4096)    # (a bad count is the library's refusal)
+        (hist, tails, sig, tx), ptrs, flags = self._outputs(
+            device, ((b_alloc,), np.uint64), ((3,), np.uint64), ((n_alloc, 2), np.float64),
+            ((n_alloc, f_alloc * self.frame_samples), np.complex128 if self.f64 else np.complex64) if want_tx else None)
+        keep, _, _, pr = self._fused_args(None, Register, "papr_study")
+        pb = None
+        if payload_bits is not None:
+            want = n_alloc * f_alloc * self.frame_bits
+            if int(np.prod(tuple(payload_bits.shape))) != want:
+                raise OfdmError(f"papr_study: payload_bits must hold n_signals * frames_per_signal * frame_bits = {want} bits")
+            if device is not None:
+                bt = payload_bits if _is_torch(payload_bits) else torch.as_tensor(np.asarray(payload_bits))
+                bt = (bt != 0).to(device=torch.device(device), dtype=torch.uint8).contiguous()
+                pb = C.c_void_p(bt.data_ptr())
+            else:
+                bt = np.ascontiguousarray(np.asarray(payload_bits.cpu().numpy() if _is_torch(payload_bits) else payload_bits) != 0,
+                                          dtype=np.uint8)
+                pb = bt.ctypes.data_as(C.c_void_p)
+        L.check(self.lib.ofdm_papr_study(self.handle, int(seed), int(frame0), ns, fps, pr, pb, window, nb, lo, hi,
+                                         int(max_frames_per_chunk), *ptrs, flags), "papr_study")
+        n_sig = fps * self.frame_samples
+        if device is not None:
+            xp, edges = torch, torch.from_numpy(np.linspace(lo, hi, nb + 1)).to(hist.device)
+            below, above, dropped = tails[0], tails[1], tails[2]
+            counted = hist.sum()
+            tail_cum = torch.flip(torch.cumsum(torch.flip(hist, (0,)), 0), (0,))
+            exceed = (torch.cat([tail_cum, torch.zeros(1, dtype=hist.dtype, device=hist.device)]) + above).double()
+        else:
+            hist, tails = hist.view(np.int64), tails.view(np.int64)          # int64 views: a count of 2^63 is out of reach
+            xp, edges = np, np.linspace(lo, hi, nb + 1)
+            below, above, dropped = int(tails[0]), int(tails[1]), int(tails[2])
+            counted = int(hist.sum())
+            exceed = (np.concatenate([np.cumsum(hist[::-1])[::-1], [0]]) + above).astype(np.float64)
+        valid = counted + below + above
+        with np.errstate(divide="ignore", invalid="ignore"):                 # no window counted: NaN, like ecdf of nothing
+            ccdf = exceed / (valid.double() if device is not None else np.float64(valid))
+        peak, power_sum = sig[:, 0], sig[:, 1]
+        out = dict(hist=hist, below=below, above=above, dropped=dropped, windows=valid + dropped, edges=edges,
+                   CCDF=ccdf, peak=peak, power_sum=power_sum,
+                   PAPR_dB=10.0 * xp.log10(peak / (power_sum / n_sig)))      # calculatePAPR.m:4-10
+        if want_tx:
+            out["tx"] = tx.t() if device is not None else tx.T
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):

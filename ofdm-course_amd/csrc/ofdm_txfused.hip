@@ -329,6 +329,20 @@ static int launch_symbols(const ofdm_rx_plan* pl, const void* tw, void* tx, doub
   return check_launch("tx_symbols_fused_kernel");
 }
 
+// the symbol stage of a chunk of nf frames: tx_symbols_fused_kernel in the plan's precision and Nfft (sc_bits: the frames' bits,
+// one byte each, in place of the Philox payload; null: the payload draw)
+int txf_symbols(const ofdm_rx_plan* pl, void* tx, double* partial, const uint8_t* sc_bits, uint32_t k0, uint32_t k1,
+                uint32_t stream0, int64_t nf) {
+  const void* tw = nullptr;
+  OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
+#define CALL(NN)                                                                                       \
+  if (pl->f64) OFDM_TRY((launch_symbols<double, NN>(pl, tw, tx, partial, sc_bits, k0, k1, stream0, nf))); \
+  else OFDM_TRY((launch_symbols<float, NN>(pl, tw, tx, partial, sc_bits, k0, k1, stream0, nf)));
+  OFDM_FFT_DISPATCH(pl->nfft, CALL)
+#undef CALL
+  return OFDM_OK;
+}
+
 // the channel pass txf_channel_pass chose: with imp the chunk's draws imp->sto / imp->cfo, with fade its amplitudes fade->amp
 template <typename T>
 static int launch_channel(const ofdm_rx_plan* pl, const TxfChannel& ch, const void* tx, void* rx, const double* partial,
@@ -394,14 +408,7 @@ int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_
     OFDM_TRY(ofdm_Scrambler_frames(scr_reg15, b.b0, frame_bits, nf, b.b1, OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0)));
     if (scref) OFDM_TRY(tx_pack_bits_device(pl, b.b1, scref, nf));
   }
-  const void* tw = nullptr;
-  OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &tw));
-  const uint8_t* sc = scr_reg15 ? b.b1 : nullptr;
-#define CALL(NN)                                                                                       \
-  if (pl->f64) OFDM_TRY((launch_symbols<double, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf))); \
-  else OFDM_TRY((launch_symbols<float, NN>(pl, tw, b.tx, b.partial, sc, k0, k1, stream0, nf)));
-  OFDM_FFT_DISPATCH(pl->nfft, CALL)
-#undef CALL
+  OFDM_TRY(txf_symbols(pl, b.tx, b.partial, scr_reg15 ? b.b1 : nullptr, k0, k1, stream0, nf));
   if (imp)
     OFDM_TRY(tx_draw_device(pl, imp->sto, imp->cfo, imp->sto_mode, imp->sto_value, imp->cfo_mode, imp->cfo_value, k0, k1,
                             stream0, nf));

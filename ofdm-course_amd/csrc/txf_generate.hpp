@@ -51,6 +51,11 @@ int txf_refused(int id, const TxfWhy& w);
 // grows pl->ws_txf to txf_layout(ch frames) and carves b from it
 int txf_workspace(ofdm_rx_plan* pl, int64_t ch, const TxfUse& u, TxfBuffers& b);
 
+// the symbol stage alone (tx_symbols_fused_kernel): the TX samples of nf frames and their per-symbol sums |x|^2; sc_bits: the
+// frames' bits, one byte each, in place of the Philox payload (null: the payload draw).  The PAPR study's stage 1.
+int txf_symbols(const ofdm_rx_plan* pl, void* tx, double* partial, const uint8_t* sc_bits, uint32_t k0, uint32_t k1,
+                uint32_t stream0, int64_t nf);
+
 // one chunk of nf frames (streams stream0 ..): rx, the packed payload bits (ref) and the packed scrambled bits (scref)
 // imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
 // fade (optional): a channel per frame -- the draws into fade->amp (and fade->taps_out), the channel pass of
