@@ -692,6 +692,51 @@ int ofdm_papr_study(ofdm_rx_plan* plan, uint64_t seed, int64_t frame0, int64_t n
                     double* signal_out,                /* optional [n_signals][2]: max |x|^2, sum |x|^2 */
                     void* tx_out,                      /* optional [frame_samples x frames]: the signals themselves */
                     int flags);
+/* The amplitude spectrum of received frames, the second picture of every impairment in the reference's reports:
+ * abs(fft(Rx_OFDM_Signal(T_Guard+1 : Nfft+T_Guard))) (T3/Main_model_Task_3.m:138, T5/Main_model_Task_5.m:131), the useful part of
+ * symbol 2 (T4/Main_model_Task_4.m:268) and, on a clean stream, abs(RX_OFDM_mapped_carriers(:,1)) (T1/Main_model.m:77).
+ * rx: [frame_samples x n_frames] complex in the plan's precision, where `flags` says.  Window w = 0 .. n_windows - 1 of frame f is
+ * its samples first + w (Nfft + T_guard) .. + Nfft - 1 (0-based); S = fft(window), forward and unscaled like MATLAB's fft, in the
+ * plan's precision (the workgroup transform of csrc/fft_core.hpp):
+ *   amp_out[n_frames][n_windows][Nfft] (real, the plan's precision) = |S(k)|, the reference's plot;
+ *   power_out[n_frames][Nfft] (double) = sum_w (re^2 + im^2), re and im widened to double before squaring, summed in window order.
+ * first = T_guard, n_windows = 1 is the line of T3:138; first = T_guard + s (Nfft + T_guard) the useful part of symbol s + 1.  The
+ * window may start anywhere (an odd sample, 0, the last start that fits) and straddle a symbol boundary and a cyclic prefix.
+ * OFDM_ERR_ARG, before anything is launched or written, in this order: plan or rx missing; the plan (device: OFDM_ERR_STATE;
+ * precision flag; data carriers; pilots in band; Nfft 64 .. 8192); n_frames 0 .. 2^31 - 1; first >= 0; n_windows >= 1; the last
+ * window ends at or before frame_samples; amp_out or power_out is given (each is optional).  A non-finite sample gives non-finite
+ * rows.  amp_out and power_out live where `flags` says. */
+int ofdm_rx_spectrum(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int64_t first, int64_t n_windows,
+                     void* amp_out,                    /* optional [n_frames][n_windows][Nfft], real */
+                     double* power_out,                /* optional [n_frames][Nfft] */
+                     int flags);
+/* The averaged periodogram of a sweep as one device-resident call: for every point p the frames frame0 .. frame0 +
+ * frames_per_point - 1 of ofdm_tx_frames_fused_ex(h, h_len, snr_db[p], seeds[p], scr_reg15, sto_mode, sto_value, cfo_mode,
+ * cfo_value) -- or, with tap_delay / tap_power / n_taps in place of h, of ofdm_tx_frames_fading_ex --, bit for bit, and of each frame
+ * the power row of ofdm_rx_spectrum(first, n_windows).  No receiver runs.  (T3/Main_model_Task_3.m:138,:155: the spectra of the
+ * report's figures, over as many frames as a sweep point has.)
+ *   power_sums_out[n_points][Nfft] (double): the point's power rows summed in frame order, ((0 + P_0) + P_1) + ..;
+ *   power_peak_out[n_points][Nfft] (double, optional): the maximum (fmax) over the point's frames and windows of re^2 + im^2;
+ *   frame_power_out[n_points][frames_per_point][Nfft] (double, optional): the power rows themselves.
+ * The outputs are overwritten.  The frames are generated in chunks of one point's frames in the plan-owned workspace, budgeted with
+ * the chunk's power rows beside it (max_frames_per_chunk > 0 caps the frames of a chunk); the sums are taken by one thread per bin in
+ * frame order and the maximum is order-free (no atomics on doubles), so every output is bitwise independent of the chunking.  With
+ * OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the workspace.  OFDM_ERR_ARG, before anything is
+ * launched or written, in this order: plan missing, a negative n_points, frames_per_point or max_frames_per_chunk; snr_db / seeds;
+ * too many points; the plan (as above, with the streams of one point); sto_mode / cfo_mode; register entries; h and taps together;
+ * the channel (as the generator refuses it); first >= 0; n_windows >= 1; the last window ends at or before frame_samples;
+ * power_sums_out is given.  The outputs live where `flags` says. */
+int ofdm_spectrum_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                        const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                        int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                        const uint8_t* scr_reg15,      /* HOST uint8[15] or NULL */
+                        const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                        int64_t n_points, int64_t frames_per_point, int64_t frame0, int64_t max_frames_per_chunk,
+                        int64_t first, int64_t n_windows,
+                        double* power_sums_out,        /* [n_points][Nfft] */
+                        double* power_peak_out,        /* optional [n_points][Nfft] */
+                        double* frame_power_out,       /* optional [n_points][frames_per_point][Nfft] */
+                        int flags);
 
 #ifdef __cplusplus
 }

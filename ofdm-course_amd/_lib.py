@@ -111,6 +111,9 @@ SIGNATURES = {
     "ofdm_ber_sweep_task4_fading": [_vp, _vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp,
                                     _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i],
     "ofdm_papr_study": [_vp, C.c_uint64, _i64, _i64, _i, _vp, _vp, _i, _i, _d, _d, _i64, _vp, _vp, _vp, _vp, _i],
+    "ofdm_rx_spectrum": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i],
+    "ofdm_spectrum_study": [_vp, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _d, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp,
+                            _vp, _vp, _i],
 }
 _RESTYPES = {"ofdm_last_error_string": C.c_char_p, "ofdm_rx_plan_frame_bytes": C.c_int64}
 

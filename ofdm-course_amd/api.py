@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -948,6 +948,47 @@ class RxPlan:
             out["tx"] = tx.t() if device is not None else tx.T
         return out
 
+    def spectrum_study(self, SNRs, frames_per_point, h=None, fading=None, Time_Delay=None, Freq_Shift=None, seeds=None, seed=1,
+                       frame0=0, Register=None, first=None, n_windows=1, device=None, want_peak=False, want_frame_power=False,
+                       max_frames_per_chunk=0):
+        """The averaged periodogram of a sweep in one device-resident call (ofdm_spectrum_study): for every SNR of `SNRs` the frames
+        frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay, Freq_Shift),
+        bit for bit, and of each frame the power row of rx_spectrum(first, n_windows): per bin the sum over the windows
+        first + w (Nfft + T_guard) .. + Nfft - 1 of |fft|^2, in double.  first defaults to T_guard (the
+        abs(fft(Rx_OFDM_Signal(T_Guard+1 : Nfft+T_Guard))) of T3/Main_model_Task_3.m:138).  No receiver runs.
+        Returns dict(power_sums=[n_points, Nfft] float64, each point's power rows summed in frame order; mean_power = power_sums /
+        (frames_per_point * n_windows); amp_rms = sqrt(mean_power) (+ peak=[n_points, Nfft], the largest |fft|^2 of any frame and
+        window, with want_peak) (+ frame_power=[n_points, frames_per_point, Nfft] with want_frame_power)); torch tensors on
+        `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on max_frames_per_chunk
+        (> 0: the frames of a chunk of the plan-owned workspace)."""
+        snr, sd = self._points(SNRs, seeds, seed, "spectrum_study")
+        n, fpp = snr.size, int(frames_per_point)
+        first = self.T_guard if first is None else int(first)
+        nw = int(n_windows)
+        (sums, peak, fp), ptrs, flags = self._outputs(
+            device, ((n, self.Nfft), np.float64), ((n, self.Nfft), np.float64) if want_peak else None,
+            ((n, max(fpp, 0), self.Nfft), np.float64) if want_frame_power else None)
+        keep, ph, nh, pr = self._fused_args(h, Register, "spectrum_study")
+        pdl, ppw, nt = None, None, 0
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "spectrum_study")
+        sm, sv = _imp_mode(Time_Delay, "spectrum_study")
+        cm, cv = _imp_mode(Freq_Shift, "spectrum_study")
+        L.check(self.lib.ofdm_spectrum_study(self.handle, ph, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), pr,
+                                             snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0),
+                                             int(max_frames_per_chunk), first, nw, *ptrs, flags), "spectrum_study")
+        count = float(fpp * nw)
+        if device is not None:                                   # a tensor divisor: an IEEE division, as numpy's (a Python scalar
+            count = torch.full((1,), count, dtype=torch.float64, device=sums.device)   # would multiply by its reciprocal)
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frames: NaN, the mean of nothing
+            mean = sums / count
+        out = dict(power_sums=sums, mean_power=mean, amp_rms=mean.sqrt() if device is not None else np.sqrt(mean))
+        if want_peak:
+            out["peak"] = peak
+        if want_frame_power:
+            out["frame_power"] = fp
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1273,6 +1314,30 @@ def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, 
     if want_mer:
         out.update(MER_dB=_mer_db(mer))
     return out
+
+
+def rx_spectrum(plan: RxPlan, rx, first=None, n_windows=1, want_power=False):
+    """The amplitude spectrum of received frames (ofdm_rx_spectrum): abs(fft(Rx_OFDM_Signal(T_Guard+1 : Nfft+T_Guard))) of
+    T3/Main_model_Task_3.m:138 and T5/Main_model_Task_5.m:131 with the defaults; first = T_guard + (Nfft + T_guard) is the useful
+    part of symbol 2 (T4/Main_model_Task_4.m:268).
+
+    rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).  Window w = 0 .. n_windows - 1
+    of a frame is its samples first + w (Nfft + T_guard) .. + Nfft - 1 (0-based; first defaults to T_guard); it may start anywhere
+    and straddle a symbol boundary, and must end inside the frame.
+    Returns dict(amp=[n_frames, n_windows, Nfft] real in the plan's precision, |fft(window)| (forward, unscaled), power =
+    [n_frames, Nfft] float64 with want_power, per bin the sum over the windows of re^2 + im^2 in double, else None)."""
+    call = _Call(rx, f64=plan.f64)
+    rows, nfr = _shape2(rx)
+    if rows != plan.frame_samples:
+        raise OfdmError("rx_spectrum: rx must have (Nfft+T_guard)*N_symb rows")
+    first = plan.T_guard if first is None else int(first)
+    nw = int(n_windows)
+    rdt = np.float64 if plan.f64 else np.float32
+    n_alloc = nw if 0 <= nw <= plan.N_symb else 0                 # (a count that cannot fit is the library's refusal)
+    amp, pamp = call._out((nfr * n_alloc * plan.Nfft,), rdt, _torch_dtype(rdt) if call.dev else None)
+    power, ppow = (call._out((nfr * plan.Nfft,), np.float64, torch.float64 if call.dev else None) if want_power else (None, None))
+    L.check(call.lib.ofdm_rx_spectrum(plan.handle, call.cin(rx), nfr, first, nw, pamp, ppow, call.flags), "rx_spectrum")
+    return dict(amp=amp.reshape(nfr, n_alloc, plan.Nfft), power=None if power is None else power.reshape(nfr, plan.Nfft))
 
 
 def _mer_db(sums):
