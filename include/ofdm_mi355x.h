@@ -737,6 +737,77 @@ int ofdm_spectrum_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, c
                         double* power_peak_out,        /* optional [n_points][Nfft] */
                         double* frame_power_out,       /* optional [n_points][frames_per_point][Nfft] */
                         int flags);
+/* The coarse synchroniser's curve for a batch of frames: plot(abs(AutoCorr)) of T4/Main_model_Task_4.m:282-287 (figures 6-10 of the
+ * Task-4 report: WidthWindow 1, T_Guard / 2, T_Guard, Nfft), AutoCorr = AutoCorrFunction(frame, width_window, Nfft)
+ * (T4/AutoCorrFunction.m:3-7), with the function's TgPosition (:10-24) and FreqOffset (:27) per frame.
+ * rx: [frame_samples x n_frames] complex in the plan's precision, where `flags` says.  n_out = frame_samples - width_window - Nfft
+ * lags per frame (:3); the call at T4:278 uses width_window = T_guard.  Per frame, every output optional but one:
+ *   amp_out[n_frames][n_out] (real, the plan's precision) = |rho(n)|: sqrt(re^2 + im^2) formed in double from the stored rho, as the
+ *     search's threshold test forms it, then rounded to the plan's precision;
+ *   rho_out[n_frames][n_out] (complex, the plan's precision): AutoCorr itself, bit for bit that of ofdm_AutoCorrFunction on the frame
+ *     (the same tiles of the same prefix sums); a window of zeros stays 0 / 0 = NaN;
+ *   tg_position_out[n_frames] (1-based), status_out[n_frames]: 0, or 1 = the catch branch of :21-24 with TgPosition 65;
+ *   freq_offset_out[n_frames] = -angle(AutoCorr(TgPosition)) / (2 pi); NaN where the curve has no lag 65 to fall back to (the
+ *     reference's index error at :27, still status 1).
+ * One workgroup per frame (sync_capture_kernel, csrc/ofdm_sync_study.hip); nothing is fetched to the host beyond the outputs.
+ * OFDM_ERR_ARG, before anything is launched or written, in this order: plan or rx missing; the plan (device: OFDM_ERR_STATE;
+ * precision flag; data carriers; pilots in band; Nfft 64 .. 8192); n_frames 0 .. 2^31 - 1; width_window 1 .. 1024; n_out >= 1; an
+ * output is given.  The outputs live where `flags` says. */
+int ofdm_rx_acf(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int64_t width_window,
+                void* amp_out,                         /* optional [n_frames][n_out], real */
+                void* rho_out,                         /* optional [n_frames][n_out], complex */
+                int64_t* tg_position_out,              /* optional [n_frames] */
+                int32_t* status_out,                   /* optional [n_frames] */
+                double* freq_offset_out,               /* optional [n_frames] */
+                int flags);
+/* The coarse-sync study of a sweep as one device-resident call: the mean ACF behind figures 6-10 of the Task-4 report over as many
+ * noisy frames as a point has, where TgPosition falls, and the fractional frequency-offset error over SNR of
+ * T4/Main_model_Task_4.m:113-135 (figure 13a).  For every point p the frames frame0 .. frame0 + frames_per_point - 1 of
+ * ofdm_tx_frames_fused_ex(h, h_len, snr_db[p], seeds[p], scr_reg15, sto_mode, sto_value, cfo_mode, cfo_value) -- or, with tap_delay /
+ * tap_power / n_taps in place of h, of ofdm_tx_frames_fading_ex --, bit for bit, and of each frame the outputs of
+ * ofdm_rx_acf(width_window).  The frames never leave the device and no receiver runs behind the autocorrelation; the integer
+ * frequency offset is out of scope (remove_IFO needs the derotated stream and a transform; the cfo_abs_err of
+ * ofdm_ber_sweep_task4 covers FreqOffset + IFO - Freq_Shift).  n_out = frame_samples - width_window - Nfft.
+ *   acf_sums_out[n_points][n_out] (double): the frames' amp rows, widened to double, summed per lag in frame order,
+ *     ((0 + a_0) + a_1) + .., a value that is not finite (the zero tail add_STO leaves: 0 / 0) left out and counted in
+ *   acf_dropped_out[n_points][n_out] (optional): for every lag, frames added + dropped = frames_per_point;
+ *   acf_peak_out[n_points][n_out] (double, optional): fmax over the frames (0 where no frame has a number);
+ *   tg_hist_out[n_points][n_out] (optional): frames by TgPosition - 1; the catch branch's 65 lands in bin 64, and where n_out <= 64
+ *     such a frame is counted in fallback_out alone;
+ *   fallback_out[n_points] (optional): frames that took the catch branch;
+ *   phase_hist_out[n_points][Nfft + T_guard] (optional): frames by (TgPosition - 1 + sto) mod (Nfft + T_guard), made non-negative,
+ *     sto the frame's own Time_Delay draw (0 when off): add_STO moves every guard interval by -sto, so this histogram is as sharp
+ *     with a random delay as without one.  No "true" position is defined here: the timing error is read from the histogram;
+ *   ffo_err_out[n_points][2] (double, optional): {sum |e|, sum e^2} in frame order of the wrapped fractional error e = d - rint(d),
+ *     d = FreqOffset - (cfo - rint(cfo)), cfo the frame's own Freq_Shift draw (0 when off), ties to even; NaN once a frame's
+ *     FreqOffset is NaN;
+ *   frame_tg_out / frame_status_out / frame_fo_out[n_points][frames_per_point] (optional): the per-frame scalars.
+ * The outputs are overwritten.  The frames are generated in chunks of one point's frames in the plan-owned workspace, budgeted with
+ * the chunk's rows beside it (max_frames_per_chunk > 0 caps the frames of a chunk).  The histograms are integers summed with atomics;
+ * every double is summed by one thread in frame order, chunk after chunk in stream order, and the maximum is order-free, so every
+ * output is bitwise independent of the chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of
+ * the workspace.  OFDM_ERR_ARG, before anything is launched or written, in this order: plan missing, a negative n_points,
+ * frames_per_point or max_frames_per_chunk; snr_db / seeds; too many points; the plan (as above, with the streams of one point);
+ * sto_mode / cfo_mode; register entries; h and taps together; the channel (as the generator refuses it); width_window 1 .. 1024;
+ * n_out >= 1; acf_sums_out is given.  The outputs live where `flags` says. */
+int ofdm_sync_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                    const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                    int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                    const uint8_t* scr_reg15,          /* HOST uint8[15] or NULL */
+                    const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                    int64_t n_points, int64_t frames_per_point, int64_t frame0, int64_t max_frames_per_chunk,
+                    int64_t width_window,
+                    double* acf_sums_out,              /* [n_points][n_out] */
+                    uint64_t* acf_dropped_out,         /* optional [n_points][n_out] */
+                    double* acf_peak_out,              /* optional [n_points][n_out] */
+                    uint64_t* tg_hist_out,             /* optional [n_points][n_out] */
+                    uint64_t* fallback_out,            /* optional [n_points] */
+                    uint64_t* phase_hist_out,          /* optional [n_points][Nfft + T_guard] */
+                    double* ffo_err_out,               /* optional [n_points][2] */
+                    int64_t* frame_tg_out,             /* optional [n_points][frames_per_point] */
+                    int32_t* frame_status_out,         /* optional [n_points][frames_per_point] */
+                    double* frame_fo_out,              /* optional [n_points][frames_per_point] */
+                    int flags);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -989,6 +989,59 @@ class RxPlan:
             out["frame_power"] = fp
         return out
 
+    def sync_study(self, SNRs, frames_per_point, h=None, fading=None, Time_Delay=None, Freq_Shift=None, width=None, seeds=None,
+                   seed=1, frame0=0, Register=None, device=None, want_peak=False, want_frames=False, max_frames_per_chunk=0):
+        """The coarse synchroniser's pictures of a sweep in one device-resident call (ofdm_sync_study): for every SNR of `SNRs` the
+        frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay,
+        Freq_Shift), bit for bit, and of each frame the outputs of rx_acf(width): abs(AutoCorr) of AutoCorrFunction(frame, width,
+        Nfft) (T4/Main_model_Task_4.m:282-287, figures 6-10 of the Task-4 report), TgPosition and FreqOffset.  width defaults to
+        T_guard (T4:278).  No receiver runs behind the autocorrelation, and the integer offset of remove_IFO is out of scope.
+        Returns dict(acf_sums=[n_points, n_out] float64, n_out = frame_samples - width - Nfft: each point's amp rows summed per lag in
+        frame order, the values that are not finite (the zero tail of add_STO: 0 / 0) left out and counted in acf_dropped=[n_points,
+        n_out] int64; mean_acf = acf_sums / (frames_per_point - acf_dropped); tg_hist=[n_points, n_out] int64, the frames by
+        TgPosition - 1 (the catch branch's 65 in bin 64; with n_out <= 64 only in fallback); fallback=[n_points] int64, the frames
+        that took the catch branch; phase_hist=[n_points, Nfft + T_guard] int64, the frames by (TgPosition - 1 + the frame's own
+        Time_Delay) mod (Nfft + T_guard): sharp whatever the delay; ffo_err=[n_points, 2] float64 = {sum |e|, sum e^2} of the wrapped
+        fractional error e of FreqOffset against the frame's own Freq_Shift (T4:113-135), mean_abs_ffo_err = ffo_err[:, 0] /
+        frames_per_point (+ acf_peak=[n_points, n_out], fmax over the frames, with want_peak) (+ tg_position, status, freq_offset =
+        [n_points, frames_per_point] with want_frames)); torch tensors on `device` (no host synchronisation) when it is given,
+        numpy arrays otherwise.  No output depends on max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned
+        workspace)."""
+        snr, sd = self._points(SNRs, seeds, seed, "sync_study")
+        n, fpp = snr.size, int(frames_per_point)
+        W = self.T_guard if width is None else int(width)
+        n_out = max(self.frame_samples - W - self.Nfft, 0) if 1 <= W <= 1024 else 0     # (a bad width is the library's refusal)
+        fa = max(fpp, 0)
+        (sums, drop, peak, tgh, fall, ph, ffo, ftg, fst, ffo_f), ptrs, flags = self._outputs(
+            device, ((n, n_out), np.float64), ((n, n_out), np.uint64), ((n, n_out), np.float64) if want_peak else None,
+            ((n, n_out), np.uint64), ((n,), np.uint64), ((n, self.Nfft + self.T_guard), np.uint64), ((n, 2), np.float64),
+            ((n, fa), np.int64) if want_frames else None, ((n, fa), np.int32) if want_frames else None,
+            ((n, fa), np.float64) if want_frames else None)
+        keep, ph_, nh, pr = self._fused_args(h, Register, "sync_study")
+        pdl, ppw, nt = None, None, 0
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "sync_study")
+        sm, sv = _imp_mode(Time_Delay, "sync_study")
+        cm, cv = _imp_mode(Freq_Shift, "sync_study")
+        L.check(self.lib.ofdm_sync_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), pr,
+                                         snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0),
+                                         int(max_frames_per_chunk), W, *ptrs, flags), "sync_study")
+        if device is None:                                       # int64 views: a count of 2^63 is out of reach
+            drop, tgh, fall, ph = (a.view(np.int64) for a in (drop, tgh, fall, ph))
+            count = np.float64(fpp)
+        else:                                                    # a tensor divisor: an IEEE division, as numpy's
+            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame added: NaN, the mean of nothing
+            mean = sums / (fpp - drop).double() if device is not None else sums / (fpp - drop).astype(np.float64)
+            mae = ffo[:, 0] / count
+        out = dict(acf_sums=sums, acf_dropped=drop, mean_acf=mean, tg_hist=tgh, fallback=fall, phase_hist=ph, ffo_err=ffo,
+                   mean_abs_ffo_err=mae)
+        if want_peak:
+            out["acf_peak"] = peak
+        if want_frames:
+            out.update(tg_position=ftg, status=fst, freq_offset=ffo_f)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1338,6 +1391,32 @@ def rx_spectrum(plan: RxPlan, rx, first=None, n_windows=1, want_power=False):
     power, ppow = (call._out((nfr * plan.Nfft,), np.float64, torch.float64 if call.dev else None) if want_power else (None, None))
     L.check(call.lib.ofdm_rx_spectrum(plan.handle, call.cin(rx), nfr, first, nw, pamp, ppow, call.flags), "rx_spectrum")
     return dict(amp=amp.reshape(nfr, n_alloc, plan.Nfft), power=None if power is None else power.reshape(nfr, plan.Nfft))
+
+
+def rx_acf(plan: RxPlan, rx, width=None, want_rho=False):
+    """The coarse synchroniser's curve of received frames (ofdm_rx_acf): abs(AutoCorr) of AutoCorrFunction(frame, width, Nfft), the
+    plot of T4/Main_model_Task_4.m:282-287, with the function's TgPosition and FreqOffset; width=None is T_guard (T4:278).
+
+    rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
+    Returns dict(amp=[n_frames, n_out] real in the plan's precision, n_out = frame_samples - width - Nfft, |rho| formed in double
+    from rho and rounded; rho=[n_frames, n_out] complex with want_rho, else None: bit for bit the AutoCorr row of AutoCorrFunction
+    on that frame (0 / 0 = NaN for a window of zeros); tg_position=[n_frames] int64 (1-based); status=[n_frames] int32 (0 ok, 1 the
+    catch branch: TgPosition 65, no warning is issued); freq_offset=[n_frames] float64)."""
+    call = _Call(rx, f64=plan.f64)
+    rows, nfr = _shape2(rx)
+    if rows != plan.frame_samples:
+        raise OfdmError("rx_acf: rx must have (Nfft+T_guard)*N_symb rows")
+    W = plan.T_guard if width is None else int(width)
+    n_out = max(plan.frame_samples - W - plan.Nfft, 0) if 1 <= W <= 1024 else 0          # (a bad width is the library's refusal)
+    rdt = np.float64 if plan.f64 else np.float32
+    amp, pamp = call._out((nfr * n_out,), rdt, _torch_dtype(rdt) if call.dev else None)
+    rho, prho = (call.cout((nfr * n_out,)) if want_rho else (None, None))
+    tg, ptg = call._out((nfr,), np.int64, torch.int64 if call.dev else None)
+    stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    fo, pfo = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
+    L.check(call.lib.ofdm_rx_acf(plan.handle, call.cin(rx), nfr, W, pamp, prho, ptg, pst, pfo, call.flags), "rx_acf")
+    return dict(amp=amp.reshape(nfr, n_out), rho=None if rho is None else rho.reshape(nfr, n_out), tg_position=tg, status=stt,
+                freq_offset=fo)
 
 
 def _mer_db(sums):

@@ -7,6 +7,14 @@ namespace ofdm {
 int demod_device(const void* y, void* x, int nfft, int64_t n_symb, int t_guard, bool f64);   // ofdm_modem.hip
 int cfo_device(const void* y, void* out, int64_t len, double cfo, int nfft, bool f64);       // ofdm_channel.hip
 
+// FreqOffset = -angle(AutoCorr(TgPosition)) / (2 pi) (AutoCorrFunction.m:27) of the plateau result resv = rho(TgPosition), into
+// resv[2]: taken on the device by the expression of the batched routes (t4_scalars_kernel, t4_acf_search_kernel,
+// sync_capture_kernel), so a frame has one FreqOffset whichever entry it goes through (the host's atan2 differs from the device's
+// in the last place on some arguments)
+__global__ void acf_freq_offset_kernel(double* __restrict__ resv) {
+  resv[2] = -atan2(resv[1], resv[0]) / (2.0 * M_PI);
+}
+
 }  // namespace ofdm
 
 using namespace ofdm;
@@ -22,7 +30,7 @@ int ofdm_AutoCorrFunction(const void* rx, int64_t len, int width_window, int nff
   const int64_t n_out = len - width_window - nfft;
   Stage st(flags);
   int64_t res[2] = {65, 0};
-  double resv[2] = {NAN, NAN};
+  double resv[3] = {NAN, NAN, NAN};                    // rho(TgPosition), FreqOffset
   if (n_out <= 0) {
     // zeros(1, <=0) -> empty AutoCorr; find() empty -> catch -> 65; AutoCorr(65) errors in MATLAB
     set_error("AutoCorrFunction: signal shorter than WidthWindow+Nfft (index exceeds array bounds at :27)");
@@ -50,6 +58,8 @@ int ofdm_AutoCorrFunction(const void* rx, int64_t len, int width_window, int nff
                        n_out, width_window, 0.77, (int64_t*)dres, (double*)dresv);
   }
   OFDM_TRY(check_launch("acf_plateau_kernel"));
+  hipLaunchKernelGGL(acf_freq_offset_kernel, dim3(1), dim3(1), 0, ctx().stream, (double*)dresv);
+  OFDM_TRY(check_launch("acf_freq_offset_kernel"));
   OFDM_TRY(st.finish());
   if (tg_position_out) *tg_position_out = res[0];
   if (res[0] > n_out) {
@@ -57,7 +67,7 @@ int ofdm_AutoCorrFunction(const void* rx, int64_t len, int width_window, int nff
               (long long)res[0], (long long)n_out);
     return OFDM_ERR_ARG;
   }
-  if (freq_offset_out) *freq_offset_out = -std::atan2(resv[1], resv[0]) / (2.0 * M_PI);   // :27
+  if (freq_offset_out) *freq_offset_out = resv[2];                                         // :27
   return res[1] ? OFDM_OK : OFDM_SOFT_ACF_FALLBACK;
 }
 

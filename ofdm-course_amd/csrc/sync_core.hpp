@@ -27,6 +27,7 @@ constexpr int ACF_TILE = 1024;
 constexpr int ACF_THREADS = 256;
 constexpr int ACF_MAXW = 1024;                       // WidthWindow limit (T_guard <= 1024 <-> Nfft <= 8192)
 constexpr int ACF_ELEMS = ACF_TILE + ACF_MAXW;       // prefix entries 0..ACF_ELEMS
+constexpr int ACF_DIRECT_W = 8;                      // windows below the shortest guard interval (Nfft 64) are summed directly
 
 // accumulation type A: double in parity mode; float in fp32 mode (tile-local prefixes of <= 2048 terms: the window sums
 // keep ~1e-6 relative accuracy, the fp32 tolerance of rho is 1e-4) -- 16-byte table entries, 20 KB per workgroup instead of
@@ -90,6 +91,17 @@ __device__ __forceinline__ void acf_tile(const cx<T>* __restrict__ x, int64_t n0
   for (int i = tid; i < n_here; i += ACF_THREADS) {
     const acc hi = S[i + W], lo = S[i];
     A pr = hi.pr - lo.pr, pi = hi.pi - lo.pi, e1 = hi.e1 - lo.e1, e2 = hi.e2 - lo.e2;
+    if (W < ACF_DIRECT_W) {
+      // A window of a few samples is a small part of the tile's prefix, and a weak sample loses its digits in the difference
+      // (WidthWindow 1, double: 5e-11 in |rho| against the 1e-11 this library holds rho to): its sums are taken from x.
+      pr = pi = e1 = e2 = A(0);
+      const cx<T>* const xa = x + n0 + i;              // m + nfft < len as in (1)
+      for (int k = 0; k < W; ++k) {
+        const cx<T> a = xa[k], b = xa[k + nfft];
+        const A ar = a.x, ai = a.y, br = b.x, bi = b.y;
+        pr += ar * br + ai * bi; pi += ai * br - ar * bi; e1 += ar * ar + ai * ai; e2 += br * br + bi * bi;
+      }
+    }
     // A window of zeros (the tail add_STO leaves, a late frame's head) is 0 / 0 = NaN in the reference, "not above" in :10-12.
     // The table is not bitwise constant over a run of zeros that crosses a thread boundary (tree scan of the run totals), so
     // the difference can be a rounding residue instead of 0: an energy within the table's rounding of zero is looked at.
