@@ -809,6 +809,91 @@ int ofdm_sync_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, compl
                     double* frame_fo_out,              /* optional [n_points][frames_per_point] */
                     int flags);
 
+/* The fine synchroniser's curve for a batch of demodulated frames: `taus`, the residual-delay estimate of every pair of adjacent
+ * pilots of T4/fine_sync.m:10-30 (T5/fine_sync.m:8-16), which figures 18a / 18b of the Task-4 report plot over the carrier number
+ * (the commented lines T4/fine_sync.m:10-18), with the mask the report argues for (T4 :32-35, T5 :18-20) and the two estimates.
+ * x: [n_frames][N_symb][Nfft] complex in the plan's precision, where `flags` says: per frame the column-major Nfft x N_symb matrix
+ * OFDM_demodulator returns and ofdm_fine_sync takes.  The pilots are the plan's (its pilot column on every symbol, T4:28-31).
+ * variant: 0 = T5/fine_sync.m, 1 = T4/fine_sync.m.  L = Np * N_symb - 1 for variant 1 when that is >= Np (T4 :8 + :25-30: no trailing
+ * 0), else Np * N_symb (the last entry 0).  Per frame, every output optional but one:
+ *   taus_out[n_frames][L] (double): angle(q(i+1) conj(q(i))) / (2 pi deltak), q = pilotValues .* conj(rx pilots), before the mask;
+ *   keep_out[n_frames][L] (uint8): the mask |taus(i) - taus(i-1)| < 1e-3 (entry 0 false), variant 1 also diff ~= 0 (T4 :33, T5 :18);
+ *   tau_out[n_frames] (double): the mean of the kept entries behind the first Np kept ones (T4 :35, T5 :20); NaN = mean([]);
+ *   phase_out[n_frames] (double): the mean of the angles qks with |qks| > 1e-3 after the timing derotation by tau when time_desync is
+ *     set (T4 :38-52, T5 :23-37); NaN = mean([]);
+ *   n_used_out[n_frames] (int32): the denominator of tau; n_phase_out[n_frames] (int32): the denominator of phase.
+ * tau and phase are bit for bit what ofdm_fine_sync(.., tau_out, phase_out) returns for the frame with the plan's pilots, the same
+ * variant and time_desync, and what the batched Task-4 receiver's fine_sync stage computes (variant 1): one arithmetic, the
+ * reductions of csrc/sync_core.hpp with their capture on.  One workgroup per frame (fine_capture_kernel, csrc/ofdm_fine_study.hip).
+ * OFDM_ERR_ARG, before anything is launched or written, in this order: plan or x missing; the plan (device: OFDM_ERR_STATE;
+ * precision flag; data carriers; pilots in band; Nfft 64 .. 8192); n_frames 0 .. 2^31 - 1; variant 0 / 1; at least two pilots;
+ * Np * N_symb < 2^31; an output is given.  The outputs live where `flags` says. */
+int ofdm_rx_fine(ofdm_rx_plan* plan, const void* x, int64_t n_frames, int variant, int time_desync,
+                 double* taus_out,                     /* optional [n_frames][L] */
+                 uint8_t* keep_out,                    /* optional [n_frames][L] */
+                 double* tau_out,                      /* optional [n_frames] */
+                 double* phase_out,                    /* optional [n_frames] */
+                 int32_t* n_used_out,                  /* optional [n_frames] */
+                 int32_t* n_phase_out,                 /* optional [n_frames] */
+                 int flags);
+/* The fine-timing study of a sweep as one device-resident call: the tau curve behind figures 18a / 18b over as many frames as a
+ * point has, how many pilot pairs the 1e-3 mask keeps, and the residual-timing error over SNR at the points of
+ * T4/Main_model_Task_4.m:137-203.  For every point p the frames frame0 .. frame0 + frames_per_point - 1 of
+ * ofdm_tx_frames_fused_ex (or, with taps, ofdm_tx_frames_fading_ex), bit for bit, go through the front end of
+ * ofdm_rx_chain_task4(time_desync, freq_desync) exactly as that receiver runs it on the route of csrc/t4_route.hpp --
+ * AutoCorrFunction(Rx, T_guard, Nfft), add_STO(TgPosition), add_STO(-(Nfft + T_guard)), with freq_desync add_CFO(-FreqOffset) and
+ * remove_IFO, OFDM_demodulator (T4:278-310) -- and of each frame's pilot rows the outputs of ofdm_rx_fine(variant, time_desync).
+ * Nothing behind fine_sync's two estimates runs: no equaliser, no demapper, no bit.  L as in ofdm_rx_fine.  Every output optional
+ * but one:
+ *   tau_curve_sums_out[n_points][L] (double): taus(i) summed over the point's frames in frame order, ((0 + t_0) + t_1) + ..; a value
+ *     that is not finite is left out and counted in curve_dropped_out[n_points][L];
+ *   keep_counts_out[n_points][L]: the frames whose entry i passed the mask;
+ *   tau_hist_out[n_points][bins_n], tau_below_out / tau_above_out / tau_nan_out[n_points]: the frames by their timing error e in
+ *     samples, e = tau * Nfft + phi_s + 1, phi = (TgPosition - 1 + Time_Delay) mod (Nfft + T_guard) the guard phase of
+ *     ofdm_sync_study, phi_s = phi wrapped into (-(Nfft + T_guard) / 2, (Nfft + T_guard) / 2]: bin floor((e - lo) n / (hi - lo)) on
+ *     [bins_lo, bins_hi), below for e < lo, above for e >= hi, nan for tau = NaN; their sum is frames_per_point;
+ *   tau_err_out[n_points][2] (double) = {sum |e|, sum e^2} and phase_sums_out[n_points][2] (double) = {sum phase, sum phase^2}, in
+ *     frame order over the frames where the value is finite; phase_nan_out[n_points]: the frames whose phase is NaN;
+ *   used_sums_out[n_points] = sum n_used;
+ *   tg_hist_out[n_points][Nfft + T_guard]: the frames by phi;
+ *   frame_tau_out, frame_phase_out (double), frame_n_used_out (int32), frame_tg_out (int64), frame_status_out (int32, the receiver's
+ *     status), frame_time_delay_out (int64, the frame's Time_Delay draw) [n_points][frames_per_point]: the per-frame scalars.
+ * The outputs are overwritten.  Chunks of one point's frames, budgeted as ofdm_ber_sweep_task4 budgets them with the chunk's rows
+ * beside (max_frames_per_chunk > 0 caps the frames of a chunk).  The integer tables are atomics on integers or fixed-order sums;
+ * every double is added by one thread in frame order, chunk after chunk in stream order: every output is bitwise independent of
+ * the chunking.  OFDM_ERR_ARG, before anything is launched or written, in this order: plan missing, a negative n_points or
+ * frames_per_point, max_frames_per_chunk outside 0 .. 65535; snr_db / seeds; too many points; the plan (as above, with the streams
+ * of one point); sto_mode / cfo_mode; register entries; h and taps together; the channel (as the generator refuses it); variant;
+ * at least two pilots; Np * N_symb < 2^31; time_desync and freq_desync both 0; the receiver's route (its refusals, in its words);
+ * bins_n >= 1 and finite bins_lo < bins_hi; an output is given.  The outputs live where `flags` says. */
+int ofdm_fine_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                    const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                    int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                    int time_desync, int freq_desync, int variant,
+                    const uint8_t* scr_reg15,          /* HOST uint8[15] or NULL */
+                    const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                    int64_t n_points, int64_t frames_per_point, int64_t frame0, int64_t max_frames_per_chunk,
+                    int bins_n, double bins_lo, double bins_hi,
+                    double* tau_curve_sums_out,        /* optional [n_points][L] */
+                    uint64_t* curve_dropped_out,       /* optional [n_points][L] */
+                    uint64_t* keep_counts_out,         /* optional [n_points][L] */
+                    uint64_t* tau_hist_out,            /* optional [n_points][bins_n] */
+                    uint64_t* tau_below_out,           /* optional [n_points] */
+                    uint64_t* tau_above_out,           /* optional [n_points] */
+                    uint64_t* tau_nan_out,             /* optional [n_points] */
+                    double* tau_err_out,               /* optional [n_points][2] */
+                    double* phase_sums_out,            /* optional [n_points][2] */
+                    uint64_t* phase_nan_out,           /* optional [n_points] */
+                    uint64_t* used_sums_out,           /* optional [n_points] */
+                    uint64_t* tg_hist_out,             /* optional [n_points][Nfft + T_guard] */
+                    double* frame_tau_out,             /* optional [n_points][frames_per_point] */
+                    double* frame_phase_out,           /* optional [n_points][frames_per_point] */
+                    int32_t* frame_n_used_out,         /* optional [n_points][frames_per_point] */
+                    int64_t* frame_tg_out,             /* optional [n_points][frames_per_point] */
+                    int32_t* frame_status_out,         /* optional [n_points][frames_per_point] */
+                    int64_t* frame_time_delay_out,     /* optional [n_points][frames_per_point] */
+                    int flags);
+
 #ifdef __cplusplus
 }
 #endif

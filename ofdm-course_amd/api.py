@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -1042,6 +1042,77 @@ class RxPlan:
             out.update(tg_position=ftg, status=fst, freq_offset=ffo_f)
         return out
 
+    def fine_study(self, SNRs, frames_per_point, h=None, fading=None, Time_Delay=None, Freq_Shift=None, time_desync=1, freq_desync=0,
+                   variant="T4", bins=None, seeds=None, seed=1, frame0=0, Register=None, device=None, want_frames=False,
+                   max_frames_per_chunk=0):
+        """The fine synchroniser's pictures of a sweep in one device-resident call (ofdm_fine_study): for every SNR of `SNRs` the
+        frames frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay,
+        Freq_Shift), bit for bit, through the front end of rx_chain_task4(time_desync, freq_desync) exactly as that receiver runs
+        it -- AutoCorrFunction(Rx, T_guard, Nfft), the two add_STO, with freq_desync add_CFO(-FreqOffset) and remove_IFO, the
+        demodulator (T4/Main_model_Task_4.m:278-310) -- and of each frame the outputs of rx_fine(variant, time_desync) on the
+        pilot rows.  Nothing behind fine_sync's estimates runs.  bins = dict(n, lo, hi) (default 64 bins on [-4, 4)) is the
+        histogram of the timing error in samples, e = tau Nfft + phi_s + 1 with phi = (TgPosition - 1 + Time_Delay) mod
+        (Nfft + T_guard) wrapped into (-(Nfft + T_guard) / 2, (Nfft + T_guard) / 2]: 0 where fine_sync measures what the coarse
+        stage left.
+        Returns dict(tau_curve_sums=[n_points, L] float64, taus(i) summed in frame order, the values that are not finite counted
+        in curve_dropped=[n_points, L] int64; keep_counts=[n_points, L] int64, the frames whose entry passed the 1e-3 mask
+        (keep_rate = keep_counts / frames_per_point); tau_hist=[n_points, bins.n], tau_below, tau_above, tau_nan=[n_points] int64
+        (their sum is frames_per_point; tau_nan: the frames where tau = mean([])); edges=[bins.n + 1]; tau_err=[n_points, 2]
+        float64 = {sum |e|, sum e^2} over the finite e, mean_abs_err = tau_err[:, 0] / (frames_per_point - tau_nan);
+        phase_sums=[n_points, 2] float64 = {sum phase, sum phase^2} over the finite values, phase_nan=[n_points] int64;
+        used_sums=[n_points] int64 = sum n_used; tg_hist=[n_points, Nfft + T_guard] int64, the frames by phi
+        (+ frame_tau, frame_phase float64, frame_n_used int32, frame_tg_position int64, frame_status int32, frame_time_delay int64 =
+        [n_points, frames_per_point] with want_frames)); torch tensors on `device` (no host synchronisation) when it is given,
+        numpy arrays otherwise.  No output depends on max_frames_per_chunk (> 0: the frames of a chunk)."""
+        if variant not in _FINE_VARIANTS:
+            raise OfdmError("fine_study: variant must be 'T4' or 'T5'")
+        bins = dict(n=64, lo=-4.0, hi=4.0) if bins is None else bins
+        try:
+            bn, blo, bhi = int(bins["n"]), float(bins["lo"]), float(bins["hi"])
+        except (TypeError, KeyError, ValueError):
+            raise OfdmError("fine_study: bins must be dict(n=, lo=, hi=)") from None
+        snr, sd = self._points(SNRs, seeds, seed, "fine_study")
+        n, fpp = snr.size, int(frames_per_point)
+        Lt = _fine_len(self.n_pilots, self.N_symb, variant)
+        fa, nb = max(fpp, 0), max(bn, 0)
+        fr = lambda dt: ((n, fa), dt) if want_frames else None
+        (sums, drop, keepc, hist, below, above, tnan, terr, psum, pnan, used, tgh, ftau, fph, fnu, ftg, fst, ftd), ptrs, flags = \
+            self._outputs(device, ((n, Lt), np.float64), ((n, Lt), np.uint64), ((n, Lt), np.uint64), ((n, nb), np.uint64),
+                          ((n,), np.uint64), ((n,), np.uint64), ((n,), np.uint64), ((n, 2), np.float64), ((n, 2), np.float64),
+                          ((n,), np.uint64), ((n,), np.uint64), ((n, self.Nfft + self.T_guard), np.uint64), fr(np.float64),
+                          fr(np.float64), fr(np.int32), fr(np.int64), fr(np.int32), fr(np.int64))
+        keep, ph_, nh, pr = self._fused_args(h, Register, "fine_study")    # keep / keep_f: the arrays behind the pointers, alive
+        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "fine_study")
+        sm, sv = _imp_mode(Time_Delay, "fine_study")
+        cm, cv = _imp_mode(Freq_Shift, "fine_study")
+        L.check(self.lib.ofdm_fine_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(bool(time_desync)),
+                                         int(bool(freq_desync)), _FINE_VARIANTS[variant], pr, snr.ctypes.data_as(C.c_void_p),
+                                         sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), int(max_frames_per_chunk), bn, blo,
+                                         bhi, *ptrs, flags), "fine_study")
+        if device is None:                                       # int64 views: a count of 2^63 is out of reach
+            drop, keepc, hist, below, above, tnan, pnan, used, tgh = (a.view(np.int64) for a in
+                                                                      (drop, keepc, hist, below, above, tnan, pnan, used, tgh))
+            count = np.float64(fpp)
+            finite = (fpp - tnan).astype(np.float64)
+        else:                                                    # tensor divisors: IEEE divisions, as numpy's
+            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
+            finite = (fpp - tnan).double()
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
+            rate = (keepc.double() if device is not None else keepc.astype(np.float64)) / count
+            mae = terr[:, 0] / finite
+        edges = np.linspace(blo, bhi, nb + 1)
+        if device is not None:                                   # like every other output (and papr_study's edges)
+            edges = torch.from_numpy(edges).to(sums.device)
+        out = dict(tau_curve_sums=sums, curve_dropped=drop, keep_counts=keepc, keep_rate=rate, tau_hist=hist, tau_below=below,
+                   tau_above=above, tau_nan=tnan, edges=edges, tau_err=terr, mean_abs_err=mae,
+                   phase_sums=psum, phase_nan=pnan, used_sums=used, tg_hist=tgh)
+        if want_frames:
+            out.update(frame_tau=ftau, frame_phase=fph, frame_n_used=fnu, frame_tg_position=ftg, frame_status=fst,
+                       frame_time_delay=ftd)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1417,6 +1488,49 @@ def rx_acf(plan: RxPlan, rx, width=None, want_rho=False):
     L.check(call.lib.ofdm_rx_acf(plan.handle, call.cin(rx), nfr, W, pamp, prho, ptg, pst, pfo, call.flags), "rx_acf")
     return dict(amp=amp.reshape(nfr, n_out), rho=None if rho is None else rho.reshape(nfr, n_out), tg_position=tg, status=stt,
                 freq_offset=fo)
+
+
+_FINE_VARIANTS = {"T5": 0, "T4": 1}
+
+
+def _fine_len(n_pilots, n_symb, variant):
+    """numel(taus): Np * N_symb - 1 for T4/fine_sync.m when that is >= Np (:8 + :25-30), else Np * N_symb (the last entry 0)."""
+    M = n_pilots * n_symb
+    return M - 1 if variant == "T4" and M - 1 >= n_pilots else M
+
+
+def rx_fine(plan: RxPlan, X, variant="T4", time_desync=1, want_taus=False, want_keep=False):
+    """The fine synchroniser's curve of demodulated frames (ofdm_rx_fine): `taus` of T4/fine_sync.m:10-30 (variant="T5":
+    T5/fine_sync.m:8-16), the residual delay every pair of adjacent pilots gives -- what figures 18a / 18b of the Task-4 report plot
+    over the carrier number --, its mask (T4 :33, T5 :18) and the two estimates of fine_sync with their denominators.
+
+    X: [Nfft, N_symb, n_frames] (or [Nfft, N_symb], one frame) complex, per frame what OFDM_demodulator returns and fine_sync takes
+    (numpy -> host flavour, torch.cuda -> device flavour).  The pilots are the plan's.
+    Returns dict(tau=[n_frames] float64, phase=[n_frames] float64 -- bit for bit fine_sync(frame, pilotCarriers, pilotValues,
+    time_desync, ., variant, return_estimates=True)[1:], NaN = mean([]) --, n_used=[n_frames] int32 (the kept entries behind the
+    first Np kept ones: the denominator of tau), n_phase=[n_frames] int32 (the angles above 1e-3: the denominator of phase),
+    taus=[n_frames, L] float64 with want_taus (before the mask; L = Np N_symb - 1 for T4 when that is >= Np, else Np N_symb with a
+    trailing 0), keep=[n_frames, L] uint8 with want_keep, else None)."""
+    if variant not in _FINE_VARIANTS:
+        raise OfdmError("rx_fine: variant must be 'T4' or 'T5'")
+    call = _Call(X, f64=plan.f64)
+    shape = tuple(X.shape)
+    if len(shape) == 2:
+        shape = shape + (1,)
+    if len(shape) != 3 or shape[:2] != (plan.Nfft, plan.N_symb):
+        raise OfdmError("rx_fine: X must be [Nfft, N_symb, n_frames]")
+    nfr = int(shape[2])
+    Lt = _fine_len(plan.n_pilots, plan.N_symb, variant)
+    taus, ptaus = (call._out((nfr * Lt,), np.float64, torch.float64 if call.dev else None) if want_taus else (None, None))
+    keep, pkeep = (call._out((nfr * Lt,), np.uint8, torch.uint8 if call.dev else None) if want_keep else (None, None))
+    tau, ptau = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
+    ph, pph = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
+    nu, pnu = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    nph, pnph = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    L.check(call.lib.ofdm_rx_fine(plan.handle, call.cin(X), nfr, _FINE_VARIANTS[variant], int(bool(time_desync)), ptaus, pkeep, ptau,
+                                  pph, pnu, pnph, call.flags), "rx_fine")
+    return dict(tau=tau, phase=ph, n_used=nu, n_phase=nph, taus=None if taus is None else taus.reshape(nfr, Lt),
+                keep=None if keep is None else keep.reshape(nfr, Lt))
 
 
 def _mer_db(sums):

@@ -712,11 +712,12 @@ static int t4_equalise_stage(const T4Call<T>& c) {
   return OFDM_OK;
 }
 
+// The call as its stages see it: the route (a refusal before anything is launched or allocated), the regions of the plan arena,
+// the twiddles and the plan's tables.  The caller fills the outputs behind the front end (bits, ref, errs, h_out, mer, scope).
 template <typename T>
-static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
-                     void* dbits, const void* dref, void* derr, int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat,
-                     void* dh_out, int mer_skip, double* dmer, const ScopeCall* scope) {
-  T4Call<T> c{};
+static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
+                           int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat) {
+  c = T4Call<T>{};
   c.pl = pl; c.F = F;
   c.s = T4Shape{pl->nfft, pl->t_guard, pl->n_symb, pl->n_carrier, pl->np, pl->f64, time_desync, freq_desync, mp_desync, pl->f64 ? 0 : 1};
   const char* why = nullptr;
@@ -739,28 +740,77 @@ static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desy
   c.Xp = (cx<T>*)(arena + a.Xp); c.rho = (cx<T>*)(arena + a.rho); c.seg = (cx<T>*)(arena + a.seg); c.spec = (cx<T>*)(arena + a.spec);
   c.pil = c.r.pilots_compact ? c.Xp : c.X;
   c.rot = c.r.lazy_rot ? c.est : nullptr;
-  c.rx = (const cx<T>*)drx; c.bits = dbits; c.ref = dref; c.errs = derr; c.h_out = dh_out;
-  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat; c.mer_skip = mer_skip; c.mer = dmer; c.scope = scope;
+  c.rx = (const cx<T>*)drx;
+  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &c.tw));
   OFDM_TRY(t4_plan_tables<T>(pl));
-  // stage brackets (ofdm_rx_plan_set_timing): [0] start, [1] AutoCorrFunction stage, [2] remove_IFO stage, [3] demodulator,
-  // [4] fine_sync + estimate_channel, [5] equalise / demap / (DeScrambler)
-  const bool timed = pl->timing && pl->ev_t4[0];
-  pl->t4_timed = timed ? 1 : 0;
-  auto mark = [&](int i) { if (timed) (void)hipEventRecord(pl->ev_t4[i], s); };
+  return OFDM_OK;
+}
+
+// The front end of the receiver (T4/Main_model_Task_4.m:278-310): the per-frame scalars zeroed, AutoCorrFunction, the two add_STO
+// and add_CFO(-FreqOffset), remove_IFO, OFDM_demodulator -- what stands in front of fine_sync.  It leaves X (and, in the direct
+// form, the compact pilot rows) in the arena.  mark(i): the stage brackets [0] .. [3] of task4_run.
+template <typename T, typename Mark>
+static int t4_front_end(const T4Call<T>& c, Mark mark) {
   mark(0);
   // per-frame scalars start at zero: one launch instead of four memsets (4.7 us each)
-  hipLaunchKernelGGL(t4_init_kernel, dim3(cdiv_u(F, 256)), dim3(256), 0, s, dstat, dtg, dfo, difo, F);
+  hipLaunchKernelGGL(t4_init_kernel, dim3(cdiv_u(c.F, 256)), dim3(256), 0, ctx().stream, c.stat, c.tg, c.fo, c.ifo, c.F);
   OFDM_TRY(t4_acf_stage(c));
   mark(1);
   OFDM_TRY(t4_ifo_stage(c));
   mark(2);
   OFDM_TRY(t4_demod_stage(c));
   mark(3);
+  return OFDM_OK;
+}
+
+template <typename T>
+static int task4_run(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
+                     void* dbits, const void* dref, void* derr, int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat,
+                     void* dh_out, int mer_skip, double* dmer, const ScopeCall* scope) {
+  T4Call<T> c;
+  OFDM_TRY(t4_call_prepare<T>(c, pl, drx, F, time_desync, freq_desync, mp_desync, dtg, dfo, difo, dstat));
+  c.bits = dbits; c.ref = dref; c.errs = derr; c.h_out = dh_out; c.mer_skip = mer_skip; c.mer = dmer; c.scope = scope;
+  hipStream_t s = ctx().stream;
+  // stage brackets (ofdm_rx_plan_set_timing): [0] start, [1] AutoCorrFunction stage, [2] remove_IFO stage, [3] demodulator,
+  // [4] fine_sync + estimate_channel, [5] equalise / demap / (DeScrambler)
+  const bool timed = pl->timing && pl->ev_t4[0];
+  pl->t4_timed = timed ? 1 : 0;
+  auto mark = [&](int i) { if (timed) (void)hipEventRecord(pl->ev_t4[i], s); };
+  OFDM_TRY(t4_front_end(c, mark));
   OFDM_TRY(t4_estimate_stage(c));
   mark(4);
   OFDM_TRY(t4_equalise_stage(c));
   mark(5);
+  return OFDM_OK;
+}
+
+// The front end alone, for the fine-sync study (ofdm_fine_study.hip): nf frames at drx (device memory, the plan's precision)
+// through the stages task4_run runs in front of fine_sync, on the route t4_route_choose gives the receiver for these flags with
+// mp_desync 0 (no stage of the front end reads it).  view: where the pilot rows fine_sync reads were left.
+template <typename T>
+static int t4_front_only(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                         int32_t* difo, int32_t* dstat, T4PilotRows* view) {
+  T4Call<T> c;
+  OFDM_TRY(t4_call_prepare<T>(c, pl, drx, F, time_desync, freq_desync, 0, dtg, dfo, difo, dstat));
+  OFDM_TRY(t4_front_end(c, [](int) {}));
+  view->rows = c.pil;
+  view->tx = pl->d_t4_tx;
+  view->fstride = c.r.pilot_fstride;
+  view->compact = c.r.pilots_compact;
+  return OFDM_OK;
+}
+
+int task4_front_end(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                    int32_t* difo, int32_t* dstat, T4PilotRows* view) {
+  return pl->f64 ? t4_front_only<double>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view)
+                 : t4_front_only<float>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view);
+}
+
+// the plan's pilot matrix [np x n_symb] on the device (t4_plan_tables), for ofdm_rx_fine
+int task4_pilot_matrix(ofdm_rx_plan* pl, const void** tx) {
+  OFDM_TRY(pl->f64 ? t4_plan_tables<double>(pl) : t4_plan_tables<float>(pl));
+  *tx = pl->d_t4_tx;
   return OFDM_OK;
 }
 

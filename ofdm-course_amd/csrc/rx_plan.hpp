@@ -87,6 +87,17 @@ int rx_chain_task4_run(ofdm_rx_plan* pl, const void* rx, int64_t n_frames, int t
                        uint8_t* bits_out, const uint8_t* ref_bits, uint32_t* errors_out, int64_t* tg_position_out,
                        double* freq_offset_out, int32_t* ifo_out, int32_t* status_out, void* h_out, int64_t mer_skip,
                        double* mer_sums_out, const ScopeCall* scope, int flags);
+// ofdm_chain_t4.hip: the receiver's front end alone (the scalars zeroed, AutoCorrFunction, add_STO x 2, add_CFO, remove_IFO,
+// OFDM_demodulator: what task4_run runs in front of fine_sync) for the fine-sync study, and where it left the pilot rows
+struct T4PilotRows {
+  const void* rows;        // per frame [np x n_symb] (compact) or the whole grid [nfft x n_symb], the plan's precision
+  const void* tx;          // the plan's pilot matrix [np x n_symb]
+  int64_t fstride;         // elements between the frames of rows
+  int compact;
+};
+int task4_front_end(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                    int32_t* difo, int32_t* dstat, T4PilotRows* view);
+int task4_pilot_matrix(ofdm_rx_plan* pl, const void** tx);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
 }

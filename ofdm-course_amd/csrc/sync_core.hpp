@@ -273,9 +273,24 @@ struct FsScratch {
   double result;
 };
 
+// What the two reductions leave behind beside their estimate.  FsNoCapture, the default, is nothing: the receiver's and
+// ofdm_fine_sync's instantiations are the code they were.  FsCapture (fine_capture_kernel, ofdm_fine_study.hip): every entry of
+// `taus` (fine_sync.m:14, before the mask) and its keep flag (:18 / T4 :33) go to the frame's rows in the trip that forms them, and
+// the two denominators -- the kept entries behind the first Np kept ones (:20), the angles above 1e-3 (:37) -- are written once.
+struct FsNoCapture {
+  static constexpr bool on = false;
+};
+struct FsCapture {
+  static constexpr bool on = true;
+  double* taus;              // [L], or null
+  uint8_t* keep;             // [L], or null
+  int32_t* n_used;           // [1]
+  int32_t* n_phase;          // [1]
+};
+
 // the residual timing estimate tau of one frame, returned to every thread of the FS_THREADS-thread workgroup
-template <typename T>
-__device__ double fine_tau_body(const PilotView<T>& pv, double deltak, int variant, FsScratch& sc) {
+template <typename T, typename Cap = FsNoCapture>
+__device__ double fine_tau_body(const PilotView<T>& pv, double deltak, int variant, FsScratch& sc, Cap cap = Cap{}) {
   int (&wcnt)[FS_THREADS / 64] = sc.wcnt;
   double (&wsum)[FS_THREADS / 64] = sc.wsum;
   int64_t (&wn)[FS_THREADS / 64] = sc.wn;
@@ -318,6 +333,12 @@ __device__ double fine_tau_body(const PilotView<T>& pv, double deltak, int varia
       }
       tp = tv[u];
       mine += keep[u] ? 1 : 0;
+      if constexpr (Cap::on) {
+        if (i < L) {
+          if (cap.taus) cap.taus[i] = tv[u];
+          if (cap.keep) cap.keep[i] = keep[u] ? 1 : 0;
+        }
+      }
     }
     // rank among the kept entries, in entry order (thread-major, then u)
     int before = 0, wtot = 0;
@@ -348,6 +369,7 @@ __device__ double fine_tau_body(const PilotView<T>& pv, double deltak, int varia
     double s = 0; int64_t n = 0;
     for (int w = 0; w < FS_THREADS / 64; ++w) { s += wsum[w]; n += wn[w]; }
     sc.result = n > 0 ? s / (double)n : NAN;                     // mean([]) = NaN
+    if constexpr (Cap::on) *cap.n_used = (int32_t)n;
   }
   __syncthreads();
   const double r = sc.result;
@@ -380,9 +402,9 @@ __device__ __forceinline__ void fine_rot(double tau, int k, double& cs, double& 
 
 // rot_tab (optional, [np] (cos, sin) of fine_rot per pilot row): the rotation depends on the pilot row only, a caller that
 // holds a whole frame computes it once per row instead of once per (row, symbol) -- same values
-template <typename T>
+template <typename T, typename Cap = FsNoCapture>
 __device__ double fine_phase_body(const PilotView<T>& pv, int time_desync, double tau, FsScratch& sc,
-                                  const double2* rot_tab = nullptr) {
+                                  const double2* rot_tab = nullptr, Cap cap = Cap{}) {
   double (&wsum)[FS_THREADS / 64] = sc.wsum;
   int64_t (&wn)[FS_THREADS / 64] = sc.wn;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -424,6 +446,7 @@ __device__ double fine_phase_body(const PilotView<T>& pv, int time_desync, doubl
     double s = 0; int64_t n = 0;
     for (int w = 0; w < FS_THREADS / 64; ++w) { s += wsum[w]; n += wn[w]; }
     sc.result = n > 0 ? s / (double)n : NAN;
+    if constexpr (Cap::on) *cap.n_phase = (int32_t)n;
   }
   __syncthreads();
   const double r = sc.result;
