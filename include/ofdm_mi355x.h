@@ -894,6 +894,92 @@ int ofdm_fine_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, compl
                     int64_t* frame_time_delay_out,     /* optional [n_points][frames_per_point] */
                     int flags);
 
+/* The spectrum remove_IFO thresholds, for a batch of frames: abs(fft(rx_signal(Nfft+1 : 2*Nfft))) of T4/remove_IFO.m:5 with
+ * IFO = inds(1) - 1 of :6-8, at either of the function's two call sites.
+ * rx: [frame_samples x n_frames] complex in the plan's precision, where `flags` says.
+ * stage 0: the received frame as it is, AutoCorrFunction beside it (T4/Main_model_Task_4.m:124-125).  stage 1: the stream the
+ * receiver hands remove_IFO (T4:278-303): with time_desync add_STO(rx, TgPosition) and add_STO(., -(Nfft + T_guard)) -- the leading
+ * zeros are zeros --, then add_CFO(., -FreqOffset), every sample rounded to the plan's precision as the receiver's separate stages
+ * round it (t4_raw / t4_rotate, csrc/t4_stream.hpp: the receiver's own bodies).  In both stages TgPosition, FreqOffset and the
+ * catch-branch flag come from the receiver's AutoCorrFunction stage (width T_guard), so they are bit for bit the tg_position_out /
+ * freq_offset_out of ofdm_rx_chain_task4(time_desync, 1, 0) on the same frames.  Per frame, every output optional but one:
+ *   amp_out[n_frames][Nfft] (real, the plan's precision) = |S(k)|: sqrt(re^2 + im^2) formed in double from the spectrum in the
+ *     plan's precision (forward, unscaled), as the receiver's threshold test forms it, then rounded to the plan's precision;
+ *   ifo_out[n_frames]: the first bin whose |S|, before that last rounding, exceeds 0.77; 0 where no bin does (status -1: the
+ *     script stops at inds(1); ofdm_rx_chain_task4 reports -1 there and goes on with an IFO of 0);
+ *   status_out[n_frames]: 0; 1 = AutoCorrFunction's catch branch (TgPosition 65); -1 = no bin above 0.77 (it replaces 0 and 1); -2
+ *     where the catch branch's lag 65 lies behind the curve (FreqOffset NaN), as in ofdm_rx_chain_task4;
+ *   n_above_out[n_frames]: the number of bins whose |S| exceeds 0.77;
+ *   tg_position_out[n_frames] (1-based), freq_offset_out[n_frames].
+ * In float a bin whose |S| in double lies above 0.77 by less than half a float step counts as above although its amp_out reads
+ * 0.76999998.  One transform of Nfft / 8 threads per frame on the workgroup FFT of csrc/fft_core.hpp (ifo_capture_kernel,
+ * csrc/ofdm_ifo_study.hip): no complex spectrum and no corrected copy of a frame reaches memory.  OFDM_ERR_ARG, before anything is
+ * launched or written, in this order: plan or rx missing; the plan (device: OFDM_ERR_STATE; precision flag; data carriers; pilots
+ * in band; Nfft 64 .. 8192); n_frames 0 .. 2^31 - 1; stage 0 / 1; time_desync 0 / 1; a frame shorter than 2 Nfft samples; the
+ * receiver's route (its other refusals, in its words: T_guard 1 .. 1024, two pilots); an output is given.  The outputs live where
+ * `flags` says. */
+int ofdm_rx_ifo(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int stage, int time_desync,
+                void* amp_out,                         /* optional [n_frames][Nfft], real */
+                int32_t* ifo_out,                      /* optional [n_frames] */
+                int32_t* status_out,                   /* optional [n_frames] */
+                int32_t* n_above_out,                  /* optional [n_frames] */
+                int64_t* tg_position_out,              /* optional [n_frames] */
+                double* freq_offset_out,               /* optional [n_frames] */
+                int flags);
+/* The integer-offset study of a sweep as one device-resident call: figure 13b of the Task-4 report (the loop of
+ * T4/Main_model_Task_4.m:113-135, |FreqOffset + e_IFO - Freq_Shift| over SNR) over as many frames as a point has, with the spectrum
+ * remove_IFO looks at and where its pick falls.  For every point p the frames frame0 .. frame0 + frames_per_point - 1 of
+ * ofdm_tx_frames_fused_ex(h, h_len, snr_db[p], seeds[p], scr_reg15, sto_mode, sto_value, cfo_mode, cfo_value) -- or, with tap_delay /
+ * tap_power / n_taps in place of h, of ofdm_tx_frames_fading_ex --, bit for bit, and of each frame the outputs of
+ * ofdm_rx_ifo(stage, time_desync).  The frames never leave the device; no demodulator and nothing behind it runs.  Every output
+ * optional but one:
+ *   spec_sums_out[n_points][Nfft] (double): the frames' amp rows, widened to double, summed per bin in frame order,
+ *     ((0 + a_0) + a_1) + ..; a value that is not finite is left out and counted in spec_dropped_out[n_points][Nfft];
+ *   above_counts_out[n_points][Nfft]: the frames whose bin exceeds 0.77 (which leakage bins below the true line take the pick);
+ *   ifo_hist_out[n_points][Nfft]: the frames with a line, by IFO; no_line_out[n_points]: the frames with status -1; their sum is
+ *     frames_per_point;
+ *   err_hist_out[n_points][2 err_span + 1], err_below_out / err_above_out[n_points]: the frames with a line by d = IFO -
+ *     rint(Freq_Shift), the frame's own draw (0 when off) rounded in double, ties to even: bin d + err_span, below for d < -err_span,
+ *     above for d > err_span; their sum is frames_per_point - no_line;  hit_out[n_points]: the frames with d = 0;
+ *   cfo_err_out[n_points][2] (double) = {sum |e|, sum e^2} in frame order of e = (FreqOffset + IFO) - Freq_Shift over the frames with
+ *     a line and a finite FreqOffset: the y axis of T4:130;
+ *   fallback_out[n_points]: the frames whose status is 1;
+ *   frame_ifo_out, frame_status_out, frame_n_above_out (int32), frame_tg_out (int64), frame_fo_out (double)
+ *     [n_points][frames_per_point]: the per-frame scalars.
+ * The outputs are overwritten.  Chunks of one point's frames in the plan-owned workspace, budgeted with the chunk's rows beside it
+ * (max_frames_per_chunk > 0 caps the frames of a chunk).  The integer tables are atomics on integers or fixed-order sums; every
+ * double is added by one thread in frame order, chunk after chunk in stream order: every output is bitwise independent of the
+ * chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the workspace.  OFDM_ERR_ARG, before
+ * anything is launched or written, in this order: plan missing, a negative n_points, frames_per_point or max_frames_per_chunk;
+ * snr_db / seeds; too many points; the plan (as above, with the streams of one point); sto_mode / cfo_mode; register entries; h and
+ * taps together; the channel (as the generator refuses it); stage; time_desync; a frame shorter than 2 Nfft samples; the receiver's
+ * route; err_span 1 .. 4096; an output is given.  The outputs live where `flags` says. */
+int ofdm_ifo_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                   const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                   int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                   int stage, int time_desync,
+                   const uint8_t* scr_reg15,           /* HOST uint8[15] or NULL */
+                   const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                   int64_t n_points, int64_t frames_per_point, int64_t frame0, int64_t max_frames_per_chunk,
+                   int64_t err_span,
+                   double* spec_sums_out,              /* optional [n_points][Nfft] */
+                   uint64_t* spec_dropped_out,         /* optional [n_points][Nfft] */
+                   uint64_t* above_counts_out,         /* optional [n_points][Nfft] */
+                   uint64_t* ifo_hist_out,             /* optional [n_points][Nfft] */
+                   uint64_t* no_line_out,              /* optional [n_points] */
+                   uint64_t* err_hist_out,             /* optional [n_points][2 err_span + 1] */
+                   uint64_t* err_below_out,            /* optional [n_points] */
+                   uint64_t* err_above_out,            /* optional [n_points] */
+                   uint64_t* hit_out,                  /* optional [n_points] */
+                   double* cfo_err_out,                /* optional [n_points][2] */
+                   uint64_t* fallback_out,             /* optional [n_points] */
+                   int32_t* frame_ifo_out,             /* optional [n_points][frames_per_point] */
+                   int32_t* frame_status_out,          /* optional [n_points][frames_per_point] */
+                   int32_t* frame_n_above_out,         /* optional [n_points][frames_per_point] */
+                   int64_t* frame_tg_out,              /* optional [n_points][frames_per_point] */
+                   double* frame_fo_out,               /* optional [n_points][frames_per_point] */
+                   int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "rx_ifo", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -1113,6 +1113,65 @@ class RxPlan:
                        frame_time_delay=ftd)
         return out
 
+    def ifo_study(self, SNRs, frames_per_point, h=None, fading=None, Time_Delay=None, Freq_Shift=None, stage="receiver", time_desync=1,
+                  err_span=32, seeds=None, seed=1, frame0=0, Register=None, device=None, want_frames=False, max_frames_per_chunk=0):
+        """remove_IFO's pictures of a sweep in one device-resident call (ofdm_ifo_study): for every SNR of `SNRs` the frames
+        frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay, Freq_Shift),
+        bit for bit, and of each frame the outputs of rx_ifo(stage, time_desync): the spectrum abs(fft(rx_signal(Nfft+1 : 2*Nfft)))
+        of T4/remove_IFO.m:5, IFO = inds(1) - 1 and the bins above 0.77.  stage="raw": remove_IFO on the received frame with
+        AutoCorrFunction beside it, the study of T4/Main_model_Task_4.m:113-135 (figure 13b of the Task-4 report);
+        stage="receiver": behind the receiver's two add_STO (with time_desync) and add_CFO(-FreqOffset), T4:278-303.  Nothing
+        behind remove_IFO's pick runs.
+        Returns dict(spec_sums=[n_points, Nfft] float64, each point's amp rows summed per bin in frame order, the values that are
+        not finite counted in spec_dropped=[n_points, Nfft] int64; mean_spec = spec_sums / (frames_per_point - spec_dropped);
+        above_counts=[n_points, Nfft] int64, the frames whose bin exceeds 0.77; ifo_hist=[n_points, Nfft] int64, the frames with
+        a line by IFO; no_line=[n_points] int64, the frames without one (status -1), no_line_rate = no_line / frames_per_point;
+        err_hist=[n_points, 2 err_span + 1], err_below, err_above=[n_points] int64, the frames with a line by IFO -
+        rint(Freq_Shift) against the frame's own draw (bin err_span is 0); hit=[n_points] int64, the frames with error 0,
+        hit_rate = hit / frames_per_point; cfo_err=[n_points, 2] float64 = {sum |e|, sum e^2} of e = FreqOffset + IFO -
+        Freq_Shift over the frames with a line, mean_abs_cfo_err = cfo_err[:, 0] / (frames_per_point - no_line) (the y axis of
+        T4:130); fallback=[n_points] int64, the frames whose status is 1 (AutoCorrFunction's catch branch)
+        (+ ifo, status, n_above int32, tg_position int64, freq_offset float64 = [n_points, frames_per_point] with want_frames));
+        torch tensors on `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on
+        max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace)."""
+        snr, sd = self._points(SNRs, seeds, seed, "ifo_study")
+        n, fpp, span = snr.size, int(frames_per_point), int(err_span)
+        fa, ne = max(fpp, 0), 2 * span + 1 if 1 <= span <= 4096 else 0   # (a bad span is the library's refusal)
+        fr = lambda dt: ((n, fa), dt) if want_frames else None
+        N = self.Nfft
+        (sums, drop, above, hist, none, ehist, ebelow, eabove, hit, cerr, fall, fifo, fst, fna, ftg, ffo), ptrs, flags = \
+            self._outputs(device, ((n, N), np.float64), ((n, N), np.uint64), ((n, N), np.uint64), ((n, N), np.uint64),
+                          ((n,), np.uint64), ((n, ne), np.uint64), ((n,), np.uint64), ((n,), np.uint64), ((n,), np.uint64),
+                          ((n, 2), np.float64), ((n,), np.uint64), fr(np.int32), fr(np.int32), fr(np.int32), fr(np.int64),
+                          fr(np.float64))
+        keep, ph_, nh, pr = self._fused_args(h, Register, "ifo_study")     # keep / keep_f: the arrays behind the pointers, alive
+        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "ifo_study")
+        sm, sv = _imp_mode(Time_Delay, "ifo_study")
+        cm, cv = _imp_mode(Freq_Shift, "ifo_study")
+        L.check(self.lib.ofdm_ifo_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), _ifo_stage(stage, "ifo_study"),
+                                        int(time_desync), pr, snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                        int(frame0), int(max_frames_per_chunk), span, *ptrs, flags), "ifo_study")
+        if device is None:                                       # int64 views: a count of 2^63 is out of reach
+            drop, above, hist, none, ehist, ebelow, eabove, hit, fall = (a.view(np.int64) for a in
+                                                                         (drop, above, hist, none, ehist, ebelow, eabove, hit, fall))
+            count = np.float64(fpp)
+            f64 = lambda a: a.astype(np.float64)
+        else:                                                    # tensor divisors: IEEE divisions, as numpy's
+            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
+            f64 = lambda a: a.double()
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
+            mean = sums / f64(fpp - drop)
+            hit_rate, none_rate = f64(hit) / count, f64(none) / count
+            mae = cerr[:, 0] / f64(fpp - none)
+        out = dict(spec_sums=sums, spec_dropped=drop, mean_spec=mean, above_counts=above, ifo_hist=hist, no_line=none,
+                   no_line_rate=none_rate, err_hist=ehist, err_below=ebelow, err_above=eabove, hit=hit, hit_rate=hit_rate,
+                   cfo_err=cerr, mean_abs_cfo_err=mae, fallback=fall)
+        if want_frames:
+            out.update(ifo=fifo, status=fst, n_above=fna, tg_position=ftg, freq_offset=ffo)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1487,6 +1546,47 @@ def rx_acf(plan: RxPlan, rx, width=None, want_rho=False):
     fo, pfo = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
     L.check(call.lib.ofdm_rx_acf(plan.handle, call.cin(rx), nfr, W, pamp, prho, ptg, pst, pfo, call.flags), "rx_acf")
     return dict(amp=amp.reshape(nfr, n_out), rho=None if rho is None else rho.reshape(nfr, n_out), tg_position=tg, status=stt,
+                freq_offset=fo)
+
+
+_IFO_STAGES = {"raw": 0, "receiver": 1}
+
+
+def _ifo_stage(stage, what):
+    """"raw" / "receiver" -> the library's 0 / 1; a number goes through as it is (the library refuses what is neither)."""
+    if isinstance(stage, str):
+        if stage not in _IFO_STAGES:
+            raise OfdmError(f"{what}: stage must be 'raw' or 'receiver'")
+        return _IFO_STAGES[stage]
+    return int(stage)
+
+
+def rx_ifo(plan: RxPlan, rx, stage="receiver", time_desync=1, want_amp=True):
+    """The spectrum remove_IFO thresholds, for received frames (ofdm_rx_ifo): abs(fft(rx_signal(Nfft+1 : 2*Nfft))) of
+    T4/remove_IFO.m:5 and IFO = inds(1) - 1 (:6-8).  stage="raw": the frame as it is (T4/Main_model_Task_4.m:124-125);
+    stage="receiver": what the Task-4 receiver hands remove_IFO (T4:278-303) -- with time_desync add_STO(rx, TgPosition) and
+    add_STO(., -(Nfft + T_guard)), then add_CFO(., -FreqOffset), rounded as the receiver's stages round.  TgPosition and FreqOffset
+    are AutoCorrFunction(frame, T_guard, Nfft)'s in both stages, bit for bit those of rx_chain_task4(time_desync, 1, 0).
+
+    rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
+    Returns dict(amp=[n_frames, Nfft] real in the plan's precision with want_amp, else None: |S| formed in double and rounded;
+    ifo=[n_frames] int32, the first bin above 0.77, 0 where there is none; status=[n_frames] int32 (0 ok, 1 AutoCorrFunction's
+    catch branch, -1 no bin above 0.77, -2 as in rx_chain_task4); n_above=[n_frames] int32, the bins above 0.77;
+    tg_position=[n_frames] int64 (1-based); freq_offset=[n_frames] float64)."""
+    call = _Call(rx, f64=plan.f64)
+    rows, nfr = _shape2(rx)
+    if rows != plan.frame_samples:
+        raise OfdmError("rx_ifo: rx must have (Nfft+T_guard)*N_symb rows")
+    rdt = np.float64 if plan.f64 else np.float32
+    amp, pamp = (call._out((nfr * plan.Nfft,), rdt, _torch_dtype(rdt) if call.dev else None) if want_amp else (None, None))
+    ifo, pifo = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    na, pna = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    tg, ptg = call._out((nfr,), np.int64, torch.int64 if call.dev else None)
+    fo, pfo = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
+    L.check(call.lib.ofdm_rx_ifo(plan.handle, call.cin(rx), nfr, _ifo_stage(stage, "rx_ifo"), int(time_desync), pamp, pifo, pst, pna, ptg, pfo,
+                                 call.flags), "rx_ifo")
+    return dict(amp=None if amp is None else amp.reshape(nfr, plan.Nfft), ifo=ifo, status=stt, n_above=na, tg_position=tg,
                 freq_offset=fo)
 
 

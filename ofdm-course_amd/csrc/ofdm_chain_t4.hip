@@ -6,6 +6,7 @@
 #include "spline_op.hpp"
 #include "sync_core.hpp"
 #include "t4_route.hpp"
+#include "t4_stream.hpp"
 
 namespace ofdm {
 
@@ -174,20 +175,7 @@ __global__ void t4_ifo_kernel(cx<T>* __restrict__ y, int64_t len, int nfft, cons
 // ---- the same three stages without the intermediate streams (Nfft 512..4096): sample i of the aligned, CFO- and
 // IFO-corrected stream of a frame, computed from rx on the fly with the roundings of the separate stages
 // (round to T after the add_CFO(-FreqOffset) rotation and again after the add_CFO(-IFO) rotation).
-template <typename T>
-__device__ __forceinline__ cx<T> t4_raw(const cx<T>* __restrict__ x, int64_t i, int64_t len, int sym_len, int time_desync,
-                                        int64_t pos) {
-  if (!time_desync) return nt_load(x + i);
-  const int64_t i1 = i - sym_len;
-  return (i1 >= 0 && i1 < len - pos && i1 + pos < len) ? nt_load(x + i1 + pos) : mk<T>(0, 0);
-}
-template <typename T>
-__device__ __forceinline__ cx<T> t4_rotate(cx<T> v, double cfo, int64_t i, double inv_nfft) {
-  const double t = cfo * (double)i * inv_nfft;
-  double sn, cs;
-  sincospi(2.0 * (t - floor(t)), &sn, &cs);
-  return mk<T>((T)((double)v.x * cs - (double)v.y * sn), (T)((double)v.x * sn + (double)v.y * cs));
-}
+// t4_raw / t4_rotate: t4_stream.hpp.
 
 // rx_signal(Nfft+1 : 2*Nfft) after the STO fix and add_CFO(-FreqOffset), straight from rx (remove_IFO.m:5)
 template <typename T>
@@ -712,11 +700,11 @@ static int t4_equalise_stage(const T4Call<T>& c) {
   return OFDM_OK;
 }
 
-// The call as its stages see it: the route (a refusal before anything is launched or allocated), the regions of the plan arena,
-// the twiddles and the plan's tables.  The caller fills the outputs behind the front end (bits, ref, errs, h_out, mer, scope).
+// The call as its stages see it, first half: the route (a refusal before anything is launched or allocated), the frame's extents
+// and the caller's buffers.  What the AutoCorrFunction stage on the search route reads; no arena, no table.
 template <typename T>
-static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
-                           int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat) {
+static int t4_call_route(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
+                         int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat) {
   c = T4Call<T>{};
   c.pl = pl; c.F = F;
   c.s = T4Shape{pl->nfft, pl->t_guard, pl->n_symb, pl->n_carrier, pl->np, pl->f64, time_desync, freq_desync, mp_desync, pl->f64 ? 0 : 1};
@@ -724,6 +712,17 @@ static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int6
   OFDM_ARG(t4_route_choose(c.s, c.r, &why) == T4_ROUTE_OK, "%s", why);       // refused before anything is launched or allocated
   c.len = (int64_t)(pl->nfft + pl->t_guard) * pl->n_symb;
   c.n_out = c.len - pl->t_guard - pl->nfft;
+  c.rx = (const cx<T>*)drx;
+  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat;
+  return OFDM_OK;
+}
+
+// Second half: the regions of the plan arena, the twiddles and the plan's tables.  The caller fills the outputs behind the front
+// end (bits, ref, errs, h_out, mer, scope).
+template <typename T>
+static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int mp_desync,
+                           int64_t* dtg, double* dfo, int32_t* difo, int32_t* dstat) {
+  OFDM_TRY(t4_call_route<T>(c, pl, drx, F, time_desync, freq_desync, mp_desync, dtg, dfo, difo, dstat));
   hipStream_t s = ctx().stream;
   // intermediates live in one plan-owned arena (grown on demand): no allocation on the steady-state path
   const T4Arena a = t4_arena_layout(c.s, c.r, F);
@@ -740,11 +739,18 @@ static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int6
   c.Xp = (cx<T>*)(arena + a.Xp); c.rho = (cx<T>*)(arena + a.rho); c.seg = (cx<T>*)(arena + a.seg); c.spec = (cx<T>*)(arena + a.spec);
   c.pil = c.r.pilots_compact ? c.Xp : c.X;
   c.rot = c.r.lazy_rot ? c.est : nullptr;
-  c.rx = (const cx<T>*)drx;
-  c.tg = dtg; c.fo = dfo; c.ifo = difo; c.stat = dstat;
   OFDM_TRY(get_twiddles(pl->nfft, pl->f64 != 0, &c.tw));
   OFDM_TRY(t4_plan_tables<T>(pl));
   return OFDM_OK;
+}
+
+// The scalars zeroed and AutoCorrFunction (T4:278): TgPosition, FreqOffset and the status (0, 1: the catch branch, -2) of every
+// frame.  The first stage of the front end, and what the integer-CFO capture runs in front of its own kernel.
+template <typename T>
+static int t4_sync_scalars(const T4Call<T>& c) {
+  // per-frame scalars start at zero: one launch instead of four memsets (4.7 us each)
+  hipLaunchKernelGGL(t4_init_kernel, dim3(cdiv_u(c.F, 256)), dim3(256), 0, ctx().stream, c.stat, c.tg, c.fo, c.ifo, c.F);
+  return t4_acf_stage(c);
 }
 
 // The front end of the receiver (T4/Main_model_Task_4.m:278-310): the per-frame scalars zeroed, AutoCorrFunction, the two add_STO
@@ -753,9 +759,7 @@ static int t4_call_prepare(T4Call<T>& c, ofdm_rx_plan* pl, const void* drx, int6
 template <typename T, typename Mark>
 static int t4_front_end(const T4Call<T>& c, Mark mark) {
   mark(0);
-  // per-frame scalars start at zero: one launch instead of four memsets (4.7 us each)
-  hipLaunchKernelGGL(t4_init_kernel, dim3(cdiv_u(c.F, 256)), dim3(256), 0, ctx().stream, c.stat, c.tg, c.fo, c.ifo, c.F);
-  OFDM_TRY(t4_acf_stage(c));
+  OFDM_TRY(t4_sync_scalars(c));
   mark(1);
   OFDM_TRY(t4_ifo_stage(c));
   mark(2);
@@ -805,6 +809,25 @@ int task4_front_end(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desyn
                     int32_t* difo, int32_t* dstat, T4PilotRows* view) {
   return pl->f64 ? t4_front_only<double>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view)
                  : t4_front_only<float>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view);
+}
+
+// The AutoCorrFunction stage alone, for the integer-CFO capture (ofdm_ifo_study.hip): the stage task4_run runs first, on the route
+// t4_route_choose gives rx_chain_task4(time_desync, 1, 0), so tg / fo / stat are that call's tg_position_out / freq_offset_out and
+// its status before remove_IFO, bit for bit; ifo is zeroed.  The search route needs no arena; with OFDM_T4_FULL_ACF the curve
+// lives in the receiver's arena, which is then grown as for a receiver call.
+template <typename T>
+static int t4_acf_only(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int64_t* dtg, double* dfo, int32_t* difo,
+                       int32_t* dstat) {
+  T4Call<T> c;
+  OFDM_TRY(t4_call_route<T>(c, pl, drx, F, time_desync, 1, 0, dtg, dfo, difo, dstat));
+  if (c.r.acf == T4_ACF_FULL) OFDM_TRY(t4_call_prepare<T>(c, pl, drx, F, time_desync, 1, 0, dtg, dfo, difo, dstat));
+  return t4_sync_scalars(c);
+}
+
+int task4_acf_stage(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int64_t* dtg, double* dfo, int32_t* difo,
+                    int32_t* dstat) {
+  return pl->f64 ? t4_acf_only<double>(pl, drx, F, time_desync, dtg, dfo, difo, dstat)
+                 : t4_acf_only<float>(pl, drx, F, time_desync, dtg, dfo, difo, dstat);
 }
 
 // the plan's pilot matrix [np x n_symb] on the device (t4_plan_tables), for ofdm_rx_fine

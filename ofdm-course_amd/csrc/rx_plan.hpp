@@ -98,6 +98,9 @@ struct T4PilotRows {
 int task4_front_end(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
                     int32_t* difo, int32_t* dstat, T4PilotRows* view);
 int task4_pilot_matrix(ofdm_rx_plan* pl, const void** tx);
+// ofdm_chain_t4.hip: the first stage of that front end alone (the scalars zeroed, AutoCorrFunction), for the integer-CFO capture
+int task4_acf_stage(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int64_t* dtg, double* dfo, int32_t* difo,
+                    int32_t* dstat);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
 }
