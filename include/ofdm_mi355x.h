@@ -980,6 +980,90 @@ int ofdm_ifo_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, comple
                    double* frame_fo_out,               /* optional [n_points][frames_per_point] */
                    int flags);
 
+/* The channel-estimate capture: both outputs of estimate_channel (T4/estimate_channel.m:6,:8) of a batch of received frames.  The
+ * call runs ofdm_rx_chain_task4(time_desync, freq_desync, mp_desync = 1) up to and including estimate_channel -- the front end
+ * (AutoCorrFunction, the two add_STO, add_CFO, remove_IFO, the demodulator), fine_sync, the pilot means, the spline -- on the route
+ * that receiver takes for these flags; no equaliser, no demapper, no bits.  rx: [n_frames][(Nfft + T_guard) N_symb] complex in the
+ * plan's precision.  Every output optional but one:
+ *   h_est_out[n_frames][N_carrier] complex, the plan's precision: H_est, bit for bit the h_out of that receiver call;
+ *   h_pilots_out[n_frames][Np] complex, the plan's precision: Hest_at_pilots = mean(rx(pilotCarriers,:) ./ pilotValues, 2) on the
+ *     fine-synced symbols, the rows the spline operator reads;
+ *   tg_position_out, freq_offset_out, ifo_out, status_out[n_frames]: bit for bit those of that receiver call.
+ * With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the receiver's arena.  OFDM_ERR_ARG, before
+ * anything is launched or written, in this order: plan or rx missing; the plan (device, precision flag, data carriers, pilots in
+ * band, Nfft / T_guard); n_frames 0 .. 2^31 - 1; time_desync 0 / 1; freq_desync 0 / 1; fewer than two pilot carriers; the
+ * receiver's route; an output is given. */
+int ofdm_rx_hest(ofdm_rx_plan* plan, const void* rx, int64_t n_frames, int time_desync, int freq_desync,
+                 void* h_est_out,                      /* optional [n_frames][N_carrier] complex */
+                 void* h_pilots_out,                   /* optional [n_frames][Np] complex */
+                 int64_t* tg_position_out,             /* optional [n_frames] */
+                 double* freq_offset_out,              /* optional [n_frames] */
+                 int32_t* ifo_out,                     /* optional [n_frames] */
+                 int32_t* status_out,                  /* optional [n_frames] */
+                 int flags);
+/* The channel study of a sweep as one device-resident call: figure 21 of the Task-4 report (T4/Main_model_Task_4.m:318-332: |H_freq|,
+ * the stems |Hest_at_pilots|, the dashed |H_est| over the carrier index) over as many frames as a point has, with the error of the
+ * estimate per carrier, per pilot and per frame.  For every point p the frames frame0 .. frame0 + frames_per_point - 1 of
+ * ofdm_tx_frames_fused_ex(h, h_len, snr_db[p], seeds[p], scr_reg15, sto_mode, sto_value, cfo_mode, cfo_value) -- or, with tap_delay /
+ * tap_power / n_taps in place of h, of ofdm_tx_frames_fading_ex --, bit for bit, and of each frame what ofdm_rx_hest(time_desync,
+ * freq_desync) returns.  The true channel is H_f(k) = sum_t a_{f,t} e^{-2 pi i d_t k / Nfft} in double on carriers k = 0 ..
+ * N_carrier - 1, from the nonzero taps of h or the frame's drawn amplitudes (the expression of the Task-4 sweep's NMSE);
+ * |z| = sqrt(re re + im im) in double, the products and the sum rounded one by one.  The frames never leave the device.  Every
+ * output optional but one:
+ *   est_amp_sums_out, true_amp_sums_out, err_sums_out, amp_err_sums_out[n_points][N_carrier] (double): sum_f |H_est_f(k)|,
+ *     sum_f |H_f(k)|, sum_f |H_f(k) - H_est_f(k)|^2, sum_f (|H_est_f(k)| - |H_f(k)|)^2, each added in frame order, ((0 + v_0) + v_1)
+ *     + ..; a frame whose H_est_f(k) is not finite (fine_sync's mean of an empty selection) adds nothing to any of the four at
+ *     carrier k and is counted in dropped_out[n_points][N_carrier];
+ *   pilot_amp_sums_out, pilot_err_sums_out[n_points][Np] (double): sum_f |Hest_at_pilots_f(i)| and sum_f |H_f(pilotCarriers(i)) -
+ *     Hest_at_pilots_f(i)|^2, the error before interpolation, with pilot_dropped_out[n_points][Np] as above;
+ *   frame_nmse_out[n_points][frames_per_point], nmse_sums_out[n_points] (double): sum_k |H_f(k) - H_est_f(k)|^2 and its sum over the
+ *     point's frames, bit for bit those of ofdm_ber_sweep_task4_nmse / _fading with mp_desync = 1 (the same kernels);
+ *   frame_amp_nmse_out, amp_nmse_sums_out: the same of (|H_est_f(k)| - |H_f(k)|)^2 -- per frame a stride of 256 per thread, the
+ *     butterfly of a wavefront and the four wave partials paired, over the frames the sweeps' fixed-order sum; a frame that is not
+ *     finite makes its point NaN, as in nmse_sums_out;
+ *   nmse_hist_out[n_points][hist_bins], nmse_below_out, nmse_above_out, nmse_nan_out[n_points]: the frames by 10 log10(frame_nmse /
+ *     N_carrier) on hist_bins bins of equal width on [hist_lo_db, hist_hi_db); their sum is frames_per_point.  No logarithm is
+ *     taken on the device: the host makes the hist_bins + 1 linear thresholds N_carrier 10^(edge / 10) once, in double, and the
+ *     bin is the last threshold not above frame_nmse.  thresholds_out[hist_bins + 1] (double, HOST memory whatever the flags): that
+ *     table;
+ *   status_counts_out[n_points][4]: the frames with status 0, 1, -1, -2, as ofdm_ber_sweep_task4 reports them.
+ * The outputs are overwritten.  Chunks of one point's frames in the plan-owned workspace, budgeted with the receiver's arena and the
+ * chunk's rows beside it (max_frames_per_chunk > 0 caps the frames of a chunk).  The integer tables are atomics on integers; every
+ * per-carrier double is added by one thread in frame order, chunk after chunk in stream order: every output is bitwise independent
+ * of the chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the workspace.  OFDM_ERR_ARG,
+ * before anything is launched or written, in this order: plan missing, a negative n_points or frames_per_point,
+ * max_frames_per_chunk outside 0 .. 65535; snr_db / seeds; too many points; the plan (as above, with the streams of one point);
+ * sto_mode / cfo_mode; register entries; h and taps together; the channel (as the generator refuses it); time_desync; freq_desync;
+ * fewer than two pilot carriers; the receiver's route; hist_bins 1 .. 4096 with finite hist_lo_db < hist_hi_db; an output is
+ * given.  The outputs but thresholds_out live where `flags` says. */
+int ofdm_hest_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                    const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                    int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                    int time_desync, int freq_desync,
+                    const uint8_t* scr_reg15,          /* HOST uint8[15] or NULL */
+                    const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                    int64_t n_points, int64_t frames_per_point, int64_t frame0, int64_t max_frames_per_chunk,
+                    int hist_bins, double hist_lo_db, double hist_hi_db,
+                    double* est_amp_sums_out,          /* optional [n_points][N_carrier] */
+                    double* true_amp_sums_out,         /* optional [n_points][N_carrier] */
+                    double* err_sums_out,              /* optional [n_points][N_carrier] */
+                    double* amp_err_sums_out,          /* optional [n_points][N_carrier] */
+                    uint64_t* dropped_out,             /* optional [n_points][N_carrier] */
+                    double* pilot_amp_sums_out,        /* optional [n_points][Np] */
+                    double* pilot_err_sums_out,        /* optional [n_points][Np] */
+                    uint64_t* pilot_dropped_out,       /* optional [n_points][Np] */
+                    double* nmse_sums_out,             /* optional [n_points] */
+                    double* amp_nmse_sums_out,         /* optional [n_points] */
+                    double* frame_nmse_out,            /* optional [n_points][frames_per_point] */
+                    double* frame_amp_nmse_out,        /* optional [n_points][frames_per_point] */
+                    uint64_t* nmse_hist_out,           /* optional [n_points][hist_bins] */
+                    uint64_t* nmse_below_out,          /* optional [n_points] */
+                    uint64_t* nmse_above_out,          /* optional [n_points] */
+                    uint64_t* nmse_nan_out,            /* optional [n_points] */
+                    uint64_t* status_counts_out,       /* optional [n_points][4] */
+                    double* thresholds_out,            /* optional HOST [hist_bins + 1] */
+                    int flags);
+
 #ifdef __cplusplus
 }
 #endif

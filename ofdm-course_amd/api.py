@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "rx_ifo", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "rx_ifo", "rx_hest", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -1172,6 +1172,76 @@ class RxPlan:
             out.update(ifo=fifo, status=fst, n_above=fna, tg_position=ftg, freq_offset=ffo)
         return out
 
+    def channel_study(self, SNRs, frames_per_point, h=None, fading=None, Time_Delay=None, Freq_Shift=None, time_desync=0,
+                      freq_desync=0, bins=dict(n=60, lo=-50.0, hi=10.0), seeds=None, seed=1, frame0=0, Register=None, device=None,
+                      want_frame_nmse=False, max_frames_per_chunk=0):
+        """estimate_channel's picture of a sweep in one device-resident call (ofdm_hest_study): figure 21 of the Task-4 report
+        (T4/Main_model_Task_4.m:318-332) -- |H_freq|, the stems |Hest_at_pilots| and the dashed |H_est| over the carrier index --
+        with the error of the estimate per carrier, per pilot and per frame.  For every SNR of `SNRs` the frames frame0 .. frame0 +
+        frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay, Freq_Shift), bit for bit, and of
+        each frame what rx_hest(time_desync, freq_desync) returns; nothing behind estimate_channel runs.  The true channel is
+        H_f(k) = sum_t a_t e^{-2 pi i d_t k / Nfft} in float64 from the nonzero taps of h (none: one unit tap) or the frame's drawn
+        amplitudes.  bins = dict(n, lo, hi): the histogram of the frames by 10 log10(frame_nmse / N_carrier) in dB.
+        Returns dict(est_amp_sums, true_amp_sums, err_sums, amp_err_sums=[n_points, N_carrier] float64: sum_f |H_est_f(k)|,
+        sum_f |H_f(k)|, sum_f |H_f(k) - H_est_f(k)|^2, sum_f (|H_est_f(k)| - |H_f(k)|)^2 in frame order, a frame whose H_est_f(k) is
+        not finite left out of all four and counted in dropped=[n_points, N_carrier] int64; mean_est_amp, mean_true_amp = the two
+        sums / (frames_per_point - dropped), the curves of figure 21; nmse_profile = err_sums / (frames_per_point - dropped);
+        pilot_amp_sums (the stems), pilot_err_sums=[n_points, Np] float64 = sum_f |H_f(pilotCarriers(i)) - Hest_at_pilots_f(i)|^2,
+        the error before interpolation, pilot_dropped=[n_points, Np] int64; nmse_sums=[n_points] float64, bit for bit those of
+        ber_sweep_task4(mp_desync=1, want_nmse=True) for the same generator arguments and flags, NMSE = nmse_sums /
+        (frames_per_point * N_carrier); amp_nmse_sums, amp_NMSE: the same of (|H_est| - |H|)^2, which does not see the ramp
+        fine_sync removes; nmse_hist=[n_points, bins.n], nmse_below, nmse_above, nmse_nan=[n_points] int64 (their sum is
+        frames_per_point), edges=[bins.n + 1] in dB and thresholds=[bins.n + 1] = N_carrier 10^(edges / 10), the table the frames
+        were compared against (numpy, made on the host); status_counts=[n_points, 4] int64, the frames with status 0, 1, -1, -2
+        (+ frame_nmse, frame_amp_nmse=[n_points, frames_per_point] float64 with want_frame_nmse)); torch tensors on `device` (no
+        host synchronisation) when it is given, numpy arrays otherwise.  No output depends on max_frames_per_chunk (> 0: the frames
+        of a chunk of the plan-owned workspace)."""
+        try:
+            extra = set(bins) - {"n", "lo", "hi"}
+            bn, blo, bhi = int(bins["n"]), float(bins["lo"]), float(bins["hi"])
+        except (TypeError, KeyError, ValueError):
+            raise OfdmError("channel_study: bins must be dict(n=, lo=, hi=)") from None
+        if extra:
+            raise OfdmError(f"channel_study: unknown bins keys {sorted(extra)}")
+        snr, sd = self._points(SNRs, seeds, seed, "channel_study")
+        n, fpp = snr.size, int(frames_per_point)
+        fa, nb = max(fpp, 0), bn if 1 <= bn <= 4096 else 0       # (a bad count is the library's refusal)
+        nc, npil = self.N_carrier, self.n_pilots
+        fr = ((n, fa), np.float64) if want_frame_nmse else None
+        (esum, tsum, err, aerr, drop, pamp, perr, pdrop, ns, ans, fn, fan, hist, below, above, hnan, stc), ptrs, flags = \
+            self._outputs(device, ((n, nc), np.float64), ((n, nc), np.float64), ((n, nc), np.float64), ((n, nc), np.float64),
+                          ((n, nc), np.uint64), ((n, npil), np.float64), ((n, npil), np.float64), ((n, npil), np.uint64),
+                          ((n,), np.float64), ((n,), np.float64), fr, fr, ((n, nb), np.uint64), ((n,), np.uint64),
+                          ((n,), np.uint64), ((n,), np.uint64), ((n, 4), np.uint64))
+        thr = np.zeros(nb + 1, np.float64)
+        keep, ph_, nh, pr = self._fused_args(h, Register, "channel_study")  # keep / keep_f: the arrays behind the pointers, alive
+        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "channel_study")
+        sm, sv = _imp_mode(Time_Delay, "channel_study")
+        cm, cv = _imp_mode(Freq_Shift, "channel_study")
+        L.check(self.lib.ofdm_hest_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(time_desync),
+                                         int(freq_desync), pr, snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+                                         int(frame0), int(max_frames_per_chunk), bn, blo, bhi, *ptrs,
+                                         thr.ctypes.data_as(C.c_void_p), flags), "hest_study")
+        if device is None:                                       # int64 views: a count of 2^63 is out of reach
+            drop, pdrop, hist, below, above, hnan, stc = (a.view(np.int64) for a in (drop, pdrop, hist, below, above, hnan, stc))
+            f64 = lambda a: a.astype(np.float64)
+        else:                                                    # tensor divisors: IEEE divisions, as numpy's
+            f64 = lambda a: a.double()
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
+            kept = f64(fpp - drop)
+            mean_est, mean_true, profile = esum / kept, tsum / kept, err / kept
+            nmse, amp_nmse = ns / float(fpp * nc), ans / float(fpp * nc)
+        edges = np.linspace(blo, bhi, nb + 1)
+        out = dict(est_amp_sums=esum, true_amp_sums=tsum, err_sums=err, amp_err_sums=aerr, dropped=drop, mean_est_amp=mean_est,
+                   mean_true_amp=mean_true, nmse_profile=profile, pilot_amp_sums=pamp, pilot_err_sums=perr, pilot_dropped=pdrop,
+                   nmse_sums=ns, NMSE=nmse, amp_nmse_sums=ans, amp_NMSE=amp_nmse, nmse_hist=hist, nmse_below=below,
+                   nmse_above=above, nmse_nan=hnan, edges=edges, thresholds=thr, status_counts=stc)
+        if want_frame_nmse:
+            out.update(frame_nmse=fn, frame_amp_nmse=fan)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1588,6 +1658,33 @@ def rx_ifo(plan: RxPlan, rx, stage="receiver", time_desync=1, want_amp=True):
                                  call.flags), "rx_ifo")
     return dict(amp=None if amp is None else amp.reshape(nfr, plan.Nfft), ifo=ifo, status=stt, n_above=na, tg_position=tg,
                 freq_offset=fo)
+
+
+def rx_hest(plan: RxPlan, rx, time_desync=1, freq_desync=1, want_h=True, want_pilots=True):
+    """Both outputs of estimate_channel for received frames (ofdm_rx_hest, T4/estimate_channel.m:6,:8): the Task-4 receiver with
+    mp_desync = 1 up to and including estimate_channel -- AutoCorrFunction, the two add_STO, add_CFO(-FreqOffset), remove_IFO, the
+    demodulator, fine_sync, the pilot means, the spline -- on the route rx_chain_task4(time_desync, freq_desync, 1) takes; no
+    equaliser, no demapper, no bits.
+
+    rx: [(Nfft+Tg)*N_symb, n_frames] complex (numpy -> host flavour, torch.cuda -> device flavour).
+    Returns dict(H_est=[n_frames, N_carrier] complex in the plan's precision with want_h, else None: bit for bit
+    rx_chain_task4(..., mp_desync=1, want_h=True)["H"].T; Hest_at_pilots=[n_frames, Np] complex with want_pilots, else None:
+    mean(rx(pilotCarriers,:) ./ pilotValues, 2) on the fine-synced symbols, the rows the spline reads; tg_position=[n_frames]
+    int64, freq_offset=[n_frames] float64, ifo, status=[n_frames] int32: bit for bit that receiver's)."""
+    call = _Call(rx, f64=plan.f64)
+    rows, nfr = _shape2(rx)
+    if rows != plan.frame_samples:
+        raise OfdmError("rx_hest: rx must have (Nfft+T_guard)*N_symb rows")
+    H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))                # memory [n_frames][N_carrier]
+    Hp, pHp = (call.cout((plan.n_pilots, nfr)) if want_pilots else (None, None))
+    tg, ptg = call._out((nfr,), np.int64, torch.int64 if call.dev else None)
+    fo, pfo = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
+    ifo, pifo = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
+    L.check(call.lib.ofdm_rx_hest(plan.handle, call.cin(rx), nfr, int(time_desync), int(freq_desync), pH, pHp, ptg, pfo, pifo, pst,
+                                  call.flags), "rx_hest")
+    return dict(H_est=None if H is None else H.T, Hest_at_pilots=None if Hp is None else Hp.T, tg_position=tg, freq_offset=fo,
+                ifo=ifo, status=stt)
 
 
 _FINE_VARIANTS = {"T5": 0, "T4": 1}

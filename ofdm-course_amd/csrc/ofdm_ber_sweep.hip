@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "channel_resp.hpp"
 #include "scope_plan.hpp"
 #include "txf_generate.hpp"
 
@@ -39,11 +40,8 @@ __global__ __launch_bounds__(64) void tx_static_amp_kernel(c64* __restrict__ amp
 // per frame f of a fading sweep: sum_{k < n_carrier} |H_f(k) - hest[f][k]|^2 with H_f(k) = sum_t a_{f,t} e^{-2 pi i d_t k / Nfft}
 // = fft(h_f, Nfft)(k) of get_MP_channel_resp (T5/Task5_part2.m:160-166,:202-205), in double.  One workgroup per frame: each
 // thread a fixed stride of carriers, a fixed butterfly, the four wave partials paired -- no atomics.
-// amp_stride: dl.n for the amplitudes of a channel per frame [frames][dl.n], 0 for one static channel [dl.n].
-struct TxfDelays {
-  int32_t d[TXF_MAX_TAPS];
-  int n;
-};
+// amp_stride: dl.n for the amplitudes of a channel per frame [frames][dl.n], 0 for one static channel [dl.n].  H_f(k):
+// channel_resp (channel_resp.hpp), shared with the channel study.
 
 template <typename T>
 __global__ __launch_bounds__(256) void t5_frame_nmse_kernel(const c64* __restrict__ amp, const cx<T>* __restrict__ hest,
@@ -57,14 +55,8 @@ __global__ __launch_bounds__(256) void t5_frame_nmse_kernel(const c64* __restric
   const double inv = 2.0 / (double)nfft;
   double s = 0;
   for (int k = threadIdx.x; k < n_carrier; k += 256) {
-    double hr = 0, hi = 0;
-    for (int t = 0; t < dl.n; ++t) {
-      const int m = (int)(((int64_t)dl.d[t] * k) % nfft);       // the phase reduced in integers: the argument stays in [0, 2)
-      double sn, cs;
-      sincospi((double)m * inv, &sn, &cs);
-      hr += a[t].x * cs + a[t].y * sn;                           // a (cs - i sn)
-      hi += a[t].y * cs - a[t].x * sn;
-    }
+    double hr, hi;
+    channel_resp(a, dl, k, nfft, inv, hr, hi);
     const cx<T> e = hest[f * n_carrier + k];
     const double dr = hr - (double)e.x, di = hi - (double)e.y;
     s += dr * dr + di * di;
@@ -228,12 +220,26 @@ static int txf_point_sums(const void* frame_values, int64_t n_points, int64_t fr
   return check_launch("t4_point_mer_kernel");
 }
 
+// the W = 1 sum for callers outside this file (the channel study: its two per-frame error sums)
+int txf_point_sums1(const void* frame_values, int64_t n_points, int64_t frames_per_point, void* sums) {
+  return txf_point_sums<1>(frame_values, n_points, frames_per_point, sums);
+}
+
+// the taps of a static channel into damp (room for max(taps, 1) amplitudes): what txf_frame_nmse reads with a frame stride of 0
+int txf_static_amps(const TxfChannel& ch, c64* damp) {
+  const int n_taps = (int)ch.delay.size();
+  TxfAmps sa{};
+  for (int t = 0; t < n_taps; ++t) sa.a[t] = mk<double>(ch.amp[t].x, ch.amp[t].y);
+  hipLaunchKernelGGL(tx_static_amp_kernel, dim3(1), dim3(64), 0, ctx().stream, damp, sa, n_taps);
+  return check_launch("tx_static_amp_kernel");
+}
+
 static int txf_point_mer(const TxfSweepOut& o, int64_t n_points, int64_t frames_per_point) {
   return txf_point_sums<2>(o.fm, n_points, frames_per_point, o.mer);
 }
 
 // the channel-estimate error of the chunk's nf frames against the channel of taps dl / amplitudes amp (t5_frame_nmse_kernel)
-static int txf_frame_nmse(const ofdm_rx_plan* pl, const c64* amp, const void* hest, const TxfDelays& dl, int64_t amp_stride,
+int txf_frame_nmse(const ofdm_rx_plan* pl, const c64* amp, const void* hest, const TxfDelays& dl, int64_t amp_stride,
                           int64_t nf, double* frame_nmse) {
   if (pl->f64)
     hipLaunchKernelGGL(t5_frame_nmse_kernel<double>, dim3((unsigned)nf), dim3(256), 0, ctx().stream, amp, (const c64*)hest, dl,
@@ -244,7 +250,7 @@ static int txf_frame_nmse(const ofdm_rx_plan* pl, const c64* amp, const void* he
   return check_launch("t5_frame_nmse_kernel");
 }
 
-static TxfDelays txf_delays(const TxfChannel& ch) {
+TxfDelays txf_delays(const TxfChannel& ch) {
   TxfDelays dl{};
   dl.n = (int)ch.delay.size();
   for (int t = 0; t < dl.n; ++t) dl.d[t] = ch.delay[t];
@@ -499,11 +505,8 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   if (dfn) {
     dl = txf_delays(ch);
     if (!c.fading) {
-      TxfAmps sa{};
-      for (int t = 0; t < n_taps; ++t) sa.a[t] = mk<double>(ch.amp[t].x, ch.amp[t].y);
       OFDM_TRY(st.scratch(sizeof(c64) * (size_t)std::max(n_taps, 1), &dstatic));   // an all-zero h has no taps: H = 0
-      hipLaunchKernelGGL(tx_static_amp_kernel, dim3(1), dim3(64), 0, stream, (c64*)dstatic, sa, n_taps);
-      OFDM_TRY(check_launch("tx_static_amp_kernel"));
+      OFDM_TRY(txf_static_amps(ch, (c64*)dstatic));
     }
   }
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, &imp, c.fading ? &fade : nullptr, u,

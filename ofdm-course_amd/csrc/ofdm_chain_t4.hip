@@ -830,6 +830,27 @@ int task4_acf_stage(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desyn
                  : t4_acf_only<float>(pl, drx, F, time_desync, dtg, dfo, difo, dstat);
 }
 
+// The receiver up to and including estimate_channel, for the channel-estimate capture (ofdm_hest_study.hip): the stages task4_run
+// runs in front of the equaliser, on the route t4_route_choose gives rx_chain_task4(time_desync, freq_desync, 1).  view: the
+// arena's H -- the equalise stage copies it to h_out unchanged -- and the pilot means the spline operator read.
+template <typename T>
+static int t4_estimate_only(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                            int32_t* difo, int32_t* dstat, T4Estimate* view) {
+  T4Call<T> c;
+  OFDM_TRY(t4_call_prepare<T>(c, pl, drx, F, time_desync, freq_desync, 1, dtg, dfo, difo, dstat));
+  OFDM_TRY(t4_front_end(c, [](int) {}));
+  OFDM_TRY(t4_estimate_stage(c));
+  view->H = c.H;
+  view->hp = c.hp;
+  return OFDM_OK;
+}
+
+int task4_estimate(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                   int32_t* difo, int32_t* dstat, T4Estimate* view) {
+  return pl->f64 ? t4_estimate_only<double>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view)
+                 : t4_estimate_only<float>(pl, drx, F, time_desync, freq_desync, dtg, dfo, difo, dstat, view);
+}
+
 // the plan's pilot matrix [np x n_symb] on the device (t4_plan_tables), for ofdm_rx_fine
 int task4_pilot_matrix(ofdm_rx_plan* pl, const void** tx) {
   OFDM_TRY(pl->f64 ? t4_plan_tables<double>(pl) : t4_plan_tables<float>(pl));

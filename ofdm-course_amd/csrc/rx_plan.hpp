@@ -101,6 +101,14 @@ int task4_pilot_matrix(ofdm_rx_plan* pl, const void** tx);
 // ofdm_chain_t4.hip: the first stage of that front end alone (the scalars zeroed, AutoCorrFunction), for the integer-CFO capture
 int task4_acf_stage(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int64_t* dtg, double* dfo, int32_t* difo,
                     int32_t* dstat);
+// ofdm_chain_t4.hip: the receiver with mp_desync 1 up to and including estimate_channel (the front end, fine_sync, the pilot
+// means, the spline operator), for the channel-estimate capture, and where it left the estimate in the plan's arena
+struct T4Estimate {
+  const void* H;           // [F][n_carrier], the plan's precision: what the equalise stage reads and h_out copies
+  const void* hp;          // [F][np]: Hest_at_pilots, the rows the spline operator read
+};
+int task4_estimate(ofdm_rx_plan* pl, const void* drx, int64_t F, int time_desync, int freq_desync, int64_t* dtg, double* dfo,
+                   int32_t* difo, int32_t* dstat, T4Estimate* view);
 int descr_raw_workspace(ofdm_rx_plan* pl, int64_t n_frames, void** raw);
 int descr_pass_run(ofdm_rx_plan* pl, const void* raw, void* bits, const void* ref, void* errs, int64_t n_frames);
 }

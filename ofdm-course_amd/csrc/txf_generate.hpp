@@ -2,6 +2,7 @@
 // the plan-owned workspace and the generation of one chunk into them.  The decisions of a call are txf_plan.hpp's.
 #pragma once
 
+#include "channel_resp.hpp"
 #include "rx_plan.hpp"
 #include "txf_plan.hpp"
 
@@ -63,5 +64,14 @@ int txf_symbols(const ofdm_rx_plan* pl, void* tx, double* partial, const uint8_t
 int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf,
                  const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
                  const TxfImp* imp = nullptr, const TxfFade* fade = nullptr);
+
+// ofdm_ber_sweep.hip, for the channel study beside the Task-4 sweep: the channel-estimate error sum_k |H_f(k) - hest[f][k]|^2 of
+// nf frames (t5_frame_nmse_kernel; amp_stride: dl.n for a channel per frame, 0 for one static channel), the delays of a call's
+// channel, the taps of a static channel into device memory, and the fixed-order sum of one double per frame over every point
+int txf_frame_nmse(const ofdm_rx_plan* pl, const c64* amp, const void* hest, const TxfDelays& dl, int64_t amp_stride, int64_t nf,
+                   double* frame_nmse);
+TxfDelays txf_delays(const TxfChannel& ch);
+int txf_static_amps(const TxfChannel& ch, c64* damp);
+int txf_point_sums1(const void* frame_values, int64_t n_points, int64_t frames_per_point, void* sums);
 
 }  // namespace ofdm
