@@ -1064,6 +1064,82 @@ int ofdm_hest_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, compl
                     double* thresholds_out,            /* optional HOST [hist_bins + 1] */
                     int flags);
 
+/* Error anatomy: where the wrong bits of a batch of frames sit.  bits and ref_bits: [n_frames][ofdm_rx_plan_frame_bytes] packed
+ * bits in the layout the receivers write (bits_out) and read (ref_bits): stream bit i of a frame at bit 7 - i % 8 of byte i / 8, the
+ * padding of the last word zero or not (it is masked).  Stream bit i has QAM index q = i / bps, label bit r = i % bps (0 = the MSB
+ * of the constellation label) and q = s nd + d: OFDM symbol s, data carrier dataCarriers(d + 1) -- the inverse of the receivers'
+ * pack stage (csrc/ofdm_chain.hip:323-339).  No receiver runs; of the plan only nd, N_symb, bps and the frame's words are read,
+ * so any geometry ofdm_rx_plan_create accepts is accepted.  Every output optional but one, all sums over the n_frames frames:
+ *   errors_out[1]: the wrong bits; frames_in_error_out[1]: the frames with at least one;
+ *   carrier_out[nd], symbol_out[N_symb], label_out[bps]: the wrong bits per data carrier, per OFDM symbol, per label bit; each
+ *     sums to errors_out;
+ *   gap_hist_out[gap_bins], gap_above_out[1]: for a frame's errors at stream positions i_0 < i_1 < .. the gaps g_k = i_k - i_(k-1),
+ *     within the frame only; gap_hist_out[g - 1] counts the gaps g <= gap_bins, gap_above_out the larger ones; together they sum to
+ *     errors_out - frames_in_error_out.  The reference's self-synchronising DeScrambler (T5/DeScrambler.m:8-13: the register is
+ *     fed by the received bit, taps on Register(13) and Register(14)) turns one channel error into payload errors at i, i + 13 and
+ *     i + 14: peaks at gaps 1 and 13;
+ *   frame_errors_out[n_frames] (uint32): the wrong bits of each frame;
+ *   map_out[N_symb][nd]: the wrong bits on the time-frequency grid; its sums over s and over d are carrier_out and symbol_out.
+ * The outputs are overwritten.  Everything is an integer added in no particular order: every output is bitwise independent of
+ * how the frames are spread over launches and workgroups.  With OFDM_DEVICE nothing synchronises the host.  OFDM_ERR_ARG, before
+ * anything is launched or written, in this order: plan, bits or ref_bits missing; (OFDM_ERR_STATE) the plan's device; no data
+ * carriers; n_frames 0 .. 2^31 - 1; a frame of more than 2^32 - 1 bits; gap_bins 1 .. 1024; an output is given. */
+int ofdm_bit_error_profile(ofdm_rx_plan* plan, const uint8_t* bits, const uint8_t* ref_bits, int64_t n_frames, int gap_bins,
+                           uint64_t* errors_out,               /* optional [1] */
+                           uint64_t* frames_in_error_out,      /* optional [1] */
+                           uint64_t* carrier_out,              /* optional [nd] */
+                           uint64_t* symbol_out,               /* optional [N_symb] */
+                           uint64_t* label_out,                /* optional [bps] */
+                           uint64_t* gap_hist_out,             /* optional [gap_bins] */
+                           uint64_t* gap_above_out,            /* optional [1] */
+                           uint32_t* frame_errors_out,         /* optional [n_frames] */
+                           uint64_t* map_out,                  /* optional [N_symb][nd] */
+                           int flags);
+/* The error anatomy of a sweep as one device-resident call: for every point p the frames frame0 .. frame0 + frames_per_point - 1
+ * of ofdm_tx_frames_fused_ex(h, h_len, snr_db[p], seeds[p], scr_reg15, sto_mode, sto_value, cfo_mode, cfo_value) -- or, with
+ * tap_delay / tap_power / n_taps in place of h, of ofdm_tx_frames_fading_ex --, bit for bit, decoded as the matching sweep decodes
+ * them -- receiver 5: ofdm_rx_chain_task5 as in ofdm_ber_sweep_task5 / _fading (the plan's route, its MMSE, h = ifft(H_LS) and
+ * OMP-route modes; sto_mode, cfo_mode, time_desync and freq_desync must be 0 and mp_desync 1); receiver 4: ofdm_rx_chain_task4(
+ * time_desync, freq_desync, mp_desync) as in ofdm_ber_sweep_task4 / _fading, the per-point STO / CFO draws as there -- and of the
+ * decisions the tables of ofdm_bit_error_profile with a leading n_points.  The frames and the bits never leave the device.
+ *   side 0 (payload): what the receiver returns against the payload bits; errors_out is then errors_out of the matching sweep for
+ *     the same arguments, bit for bit (T3/Main_model_Task_3.m:237-266, T4/Main_model_Task_4.m:354-366);
+ *   side 1 (channel): the decisions in front of the DeScrambler against the scrambled bits (sc_ref_bits_out of the generator), so
+ *     that carrier, symbol and label mean what they say; behind the self-synchronising DeScrambler every channel error is three
+ *     payload errors.  The receiver runs with the plan's DeScrambler masked for the call; the plan is as it was when the call
+ *     returns, errors included.  While a side 1 call runs the plan itself is changed: no other thread may use the plan, and no
+ *     other call on it may be issued, until this call has returned (as for every call on a plan, whose workspaces are not
+ *     shared either).  Without scr_reg15 the two sides are the same bits.
+ * The outputs are overwritten.  Chunks of one point's frames in the plan-owned workspace, budgeted as the matching sweep budgets
+ * them with the two bit buffers of a chunk beside them (max_frames_per_chunk > 0 caps the frames of a chunk); every output is
+ * bitwise independent of the chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the
+ * workspace.  OFDM_ERR_ARG, before anything is launched or written, in this order: receiver 4 / 5; side 0 / 1; h and taps
+ * together; receiver 5 with an impairment or a flag ofdm_ber_sweep_task5 does not have; every refusal of the matching sweep in its
+ * order and its own words (as "ber_sweep_task5", "ber_sweep_task5_fading", "ber_sweep_task4", "ber_sweep_task4_fading": the
+ * generator's channel checks, the Scrambler / DeScrambler rule, the MMSE restrictions, max_frames_per_chunk among them); a frame of
+ * more than 2^32 - 1 bits; gap_bins 1 .. 1024; an output is given.  What the receiver's route refuses comes from the first receiver
+ * call, in the receiver's words. */
+int ofdm_error_study(ofdm_rx_plan* plan, int receiver,        /* 4 | 5 */
+                     const void* h, int h_len,                 /* HOST, complex in the plan's precision, or NULL / 0 */
+                     const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                     int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                     int time_desync, int freq_desync, int mp_desync,
+                     const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                     int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                     const uint8_t* scr_reg15,                 /* HOST uint8[15] or NULL */
+                     int side,                                 /* 0 payload | 1 channel */
+                     int gap_bins, int64_t max_frames_per_chunk,
+                     uint64_t* errors_out,                     /* optional [n_points] */
+                     uint64_t* frames_in_error_out,            /* optional [n_points] */
+                     uint64_t* carrier_out,                    /* optional [n_points][nd] */
+                     uint64_t* symbol_out,                     /* optional [n_points][N_symb] */
+                     uint64_t* label_out,                      /* optional [n_points][bps] */
+                     uint64_t* gap_hist_out,                   /* optional [n_points][gap_bins] */
+                     uint64_t* gap_above_out,                  /* optional [n_points] */
+                     uint32_t* frame_errors_out,               /* optional [n_points][frames_per_point] */
+                     uint64_t* map_out,                        /* optional [n_points][N_symb][nd] */
+                     int flags);
+
 #ifdef __cplusplus
 }
 #endif

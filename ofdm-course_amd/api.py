@@ -35,7 +35,7 @@ __all__ = [
     "OFDM_modulator", "OFDM_demodulator", "get_MP_channel_resp", "apply_channel", "Noise", "add_STO",
     "add_CFO", "add_STO_CFO_frames", "apply_channel_frames", "Noise_frames", "AutoCorrFunction", "remove_IFO", "fine_sync", "estimate_channel", "equalize_signal",
     "interpolate", "LS_CE", "MMSE_CE", "sensing_matrix", "MP_estimate", "OMP_estimate", "BER_func",
-    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "rx_ifo", "rx_hest", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
+    "MER_func", "calculatePAPR", "calculate_window_PAPR", "calculateCCDF", "RxPlan", "rx_chain_task5", "rx_chain_task4", "rx_spectrum", "rx_acf", "rx_fine", "rx_ifo", "rx_hest", "bit_error_profile", "task5_part2_tile", "task5_mse_tile", "OMP_estimate_batch", "DEFAULT_REGISTER",
 ]
 
 DEFAULT_REGISTER = (1, 0, 0, 1, 0, 1, 0, 1, 0, 0, 0, 0, 0, 0, 0)   # T5/Main_model_Task_5.m:55
@@ -667,6 +667,7 @@ class RxPlan:
         if pv.size != pc.size:
             raise OfdmError("RxPlan: pilotValues_col must have numel(pilotCarriers) entries")
         self.n_pilots, self.n_data = pc.size, dc.size
+        self.dataCarriers = dc.copy()                              # 1-based, the order of the packed bits (error_study)
         h = C.c_void_p(None)
         L.check(self.lib.ofdm_rx_plan_create(C.byref(h), self.Nfft, self.T_guard, self.N_symb, self.N_carrier,
                                              pc.ctypes.data_as(C.c_void_p), pc.size, dc.ctypes.data_as(C.c_void_p),
@@ -1242,6 +1243,45 @@ class RxPlan:
             out.update(frame_nmse=fn, frame_amp_nmse=fan)
         return out
 
+    def error_study(self, SNRs, frames_per_point, receiver="task5", h=None, fading=None, Time_Delay=None, Freq_Shift=None,
+                    time_desync=0, freq_desync=0, mp_desync=1, side="payload", gap_bins=64, want_map=False, want_frames=False,
+                    seeds=None, seed=1, frame0=0, Register=None, device=None, max_frames_per_chunk=0):
+        """Where a sweep point's bit errors sit, in one device-resident call (ofdm_error_study).  For every SNR of `SNRs` the frames
+        frame0 .. frame0 + frames_per_point - 1 of tx_frames_fused(h or fading, SNR, seeds[p], Register, Time_Delay, Freq_Shift), bit
+        for bit, decoded as the matching sweep decodes them -- receiver="task5": rx_chain_task5 as in ber_sweep (the plan's route,
+        its MMSE / mmse-ls / OMP-route modes; no Time_Delay / Freq_Shift, time_desync = freq_desync = 0, mp_desync = 1);
+        receiver="task4": rx_chain_task4(time_desync, freq_desync, mp_desync) as in ber_sweep_task4 -- and the tables of
+        bit_error_profile over each point's decisions.  The refusals of those sweeps apply in their own words.
+        side="payload": what the receiver returns against the payload bits; `errors` is then ber_sweep(...)["errors"] /
+        ber_sweep_task4(...)["errors"] for the same arguments, bit for bit.  side="channel": the decisions in front of the
+        DeScrambler against the scrambled bits (sc_packed of tx_frames_fused): carrier, symbol and label then mean what they say,
+        where the self-synchronising DeScrambler (T5/DeScrambler.m:8-13) turns every channel error into payload errors at i, i + 13
+        and i + 14.  The plan's DeScrambler is masked inside the call and is as it was afterwards; without Register the two sides
+        are the same bits.
+        Returns the dict of bit_error_profile with a leading n_points on every table (frame_errors=[n_points, frames_per_point],
+        map=[n_points, N_symb, nd]); torch tensors on `device` (no host synchronisation) when it is given, numpy arrays otherwise.
+        No output depends on max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace)."""
+        try:
+            rcv = {"task5": 5, "task4": 4, 5: 5, 4: 4}[receiver]
+            sd_ = {"payload": 0, "channel": 1}[side]
+        except (KeyError, TypeError):
+            raise OfdmError('error_study: receiver must be "task5" or "task4", side "payload" or "channel"') from None
+        snr, sd = self._points(SNRs, seeds, seed, "error_study")
+        n, fpp = snr.size, int(frames_per_point)
+        gb = int(gap_bins)
+        arrs, ptrs, flags = self._outputs(device, *_error_specs(self, n, max(fpp, 0), gb, want_frames, want_map))
+        keep, ph, nh, pr = self._fused_args(h, Register, "error_study")  # keep / keep_f: the arrays behind the pointers, alive
+        pdl, ppw, nt = None, None, 0                                     # until the call has returned
+        if fading is not None:                                           # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "error_study")
+        sm, sv = _imp_mode(Time_Delay, "error_study")
+        cm, cv = _imp_mode(Freq_Shift, "error_study")
+        L.check(self.lib.ofdm_error_study(self.handle, rcv, ph, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(time_desync),
+                                          int(freq_desync), int(mp_desync), snr.ctypes.data_as(C.c_void_p),
+                                          sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr, sd_, gb, int(max_frames_per_chunk),
+                                          *ptrs, flags), "error_study")
+        return _error_result(self, device is not None, max(fpp, 0), arrs)
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):
@@ -1688,6 +1728,71 @@ def rx_hest(plan: RxPlan, rx, time_desync=1, freq_desync=1, want_h=True, want_pi
 
 
 _FINE_VARIANTS = {"T5": 0, "T4": 1}
+
+
+def _error_specs(plan, n, frames, gap_bins, want_frames, want_map):
+    """The outputs of the error anatomy for n points (n = None: one batch, no leading axis) as _outputs specs."""
+    lead = () if n is None else (n,)
+    gb = gap_bins if 1 <= gap_bins <= 1024 else 0                   # (a bad count is the library's refusal)
+    u64 = lambda *shape: (lead + shape, np.uint64)
+    return (u64(), u64(), u64(plan.n_data), u64(plan.N_symb), u64(plan.bps), u64(gb), u64(),
+            (lead + (frames,), np.uint32) if want_frames else None, u64(plan.N_symb, plan.n_data) if want_map else None)
+
+
+def _error_result(plan, on_device, frames, arrs):
+    """The result of bit_error_profile / RxPlan.error_study from the arrays of _error_specs (`frames`: per point)."""
+    err, fie, car, sym, lab, gap, above, fe, emap = arrs
+    if not on_device:                                               # int64 views: a count of 2^63 is out of reach
+        err, fie, car, sym, lab, gap, above = (a.view(np.int64) for a in (err, fie, car, sym, lab, gap, above))
+        emap = None if emap is None else emap.view(np.int64)
+        f64 = lambda a: a.astype(np.float64)
+    else:
+        f64 = lambda a: a.double()
+    with np.errstate(divide="ignore", invalid="ignore"):            # no frame: NaN, the rate of nothing
+        fer = f64(fie) / float(frames) if frames else f64(fie) * float("nan")
+        cber = f64(car) / float(frames * plan.N_symb * plan.bps) if frames else f64(car) * float("nan")
+    out = dict(errors=err, frames_in_error=fie, FER=fer, carrier_errors=car, carrier_BER=cber, dataCarriers=plan.dataCarriers.copy(),
+               symbol_errors=sym, label_errors=lab, gap_hist=gap, gap_above=above, bits=frames * plan.frame_bits)
+    if emap is not None:
+        out["map"] = emap
+    if fe is not None:
+        out["frame_errors"] = fe
+    return out
+
+
+def bit_error_profile(plan: RxPlan, bits, ref_bits, gap_bins=64, want_map=False, want_frames=False):
+    """Where the wrong bits of a batch of frames sit (ofdm_bit_error_profile).  bits, ref_bits: [n_frames, frame_bytes] uint8 packed
+    as the receivers write bits= and read ref_bits_packed (both numpy -> host flavour, both torch.cuda -> device flavour, no host
+    synchronisation).  Stream bit i of a frame has QAM index q = i // bps, label bit r = i % bps (0 = the MSB of the constellation
+    label) and q = s * nd + d: OFDM symbol s, data carrier dataCarriers[d].  No receiver runs.
+    Returns dict(errors (the wrong bits), frames_in_error, FER = frames_in_error / n_frames, carrier_errors=[nd], carrier_BER =
+    carrier_errors / (n_frames * N_symb * bps), dataCarriers=[nd] (1-based, the axis of carrier_errors), symbol_errors=[N_symb],
+    label_errors=[bps], gap_hist=[gap_bins], gap_above, bits = the bits compared (+ map=[N_symb, nd] with want_map)
+    (+ frame_errors=[n_frames] uint32 with want_frames)), int64 counts.  For a frame's errors at stream positions i_0 < i_1 < .. the
+    gaps are g_k = i_k - i_(k-1), within the frame only: gap_hist[g - 1] counts the gaps g <= gap_bins, gap_above the larger ones.
+    Identities: sum(carrier_errors) = sum(symbol_errors) = sum(label_errors) = errors; sum(gap_hist) + gap_above = errors -
+    frames_in_error; map.sum(0) = carrier_errors; map.sum(1) = symbol_errors.  Integers added in no particular order: the result
+    does not depend on how the frames are spread over the device."""
+    dev = _is_torch(bits) and bits.is_cuda
+    if dev != (_is_torch(ref_bits) and ref_bits.is_cuda):
+        raise OfdmError("bit_error_profile: bits and ref_bits must both be numpy arrays or both be CUDA tensors")
+    if len(bits.shape) != 2 or bits.shape[1] != plan.frame_bytes or tuple(ref_bits.shape) != tuple(bits.shape):
+        raise OfdmError("bit_error_profile: bits and ref_bits must be [n_frames, frame_bytes]")
+    nfr = int(bits.shape[0])
+    if dev:
+        if bits.dtype != torch.uint8 or ref_bits.dtype != torch.uint8:
+            raise OfdmError("bit_error_profile: bits and ref_bits must be uint8")
+        b, r = bits.contiguous(), ref_bits.contiguous()
+        pb, prf = C.c_void_p(b.data_ptr()), C.c_void_p(r.data_ptr())
+        device = bits.device
+    else:
+        b = np.ascontiguousarray(np.asarray(bits.numpy() if _is_torch(bits) else bits, dtype=np.uint8))
+        r = np.ascontiguousarray(np.asarray(ref_bits.numpy() if _is_torch(ref_bits) else ref_bits, dtype=np.uint8))
+        pb, prf = b.ctypes.data_as(C.c_void_p), r.ctypes.data_as(C.c_void_p)
+        device = None
+    arrs, ptrs, flags = plan._outputs(device, *_error_specs(plan, None, nfr, int(gap_bins), want_frames, want_map))
+    L.check(plan.lib.ofdm_bit_error_profile(plan.handle, pb, prf, nfr, int(gap_bins), *ptrs, flags), "bit_error_profile")
+    return _error_result(plan, dev, nfr, arrs)
 
 
 def _fine_len(n_pilots, n_symb, variant):

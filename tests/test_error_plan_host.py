@@ -1,0 +1,199 @@
+"""The call plan of the error anatomy (csrc/error_plan.hpp) on the CPU: tests/host/error_plan_main.cpp is compiled with the host
+compiler and the address and undefined-behaviour sanitizers into a stand-alone program and asked about the refusals of both entries
+in their order, the gap_bins edges, the chunk rule and the flush cap at their edges, the LDS budget, and the position function --
+at the edges of a label, a symbol and the frame for every bps the library maps, and its division-free running form -- against the
+Python twins of tests/error_cases.py."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+import error_cases as ec
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "ofdm-course_amd", "csrc")
+HEADER = os.path.join(CSRC, "error_plan.hpp")
+
+
+@pytest.fixture(scope="module")
+def host_program(tmp_path_factory):
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("clang++") or shutil.which("c++")
+    assert cxx, "no C++ compiler for the stand-alone program"
+    exe = str(tmp_path_factory.mktemp("error_plan") / "error_plan_main")
+    subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(ROOT, "tests", "host", "error_plan_main.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def _ask(host_program, lines):
+    r = subprocess.run([host_program], input="\n".join(lines) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, r.stderr              # a sanitizer report is a failure
+    got = r.stdout.splitlines()
+    assert len(got) == len(lines)
+    return got
+
+
+def _line(cmd, *dicts, **kv):
+    merged = {}
+    for d in dicts:
+        merged.update(d)
+    merged.update(kv)
+    return cmd + " " + " ".join(f"{k}={v}" for k, v in merged.items())
+
+
+def test_bit_error_profile_first_refusal_wins_in_the_documented_order(host_program):
+    order, good = ec.profile_order(), ec.good_profile()
+    got = _ask(host_program, [_line("profile", ec.broken_from(good, order, i)) for i in range(len(order) + 1)])
+    for i, (rid, _, msg) in enumerate(order):
+        assert got[i] == f"refused {rid} {msg}", (i, rid, got[i])
+    assert got[-1] == "ok"
+    for brk in (dict(plan=0), dict(bits=0)):
+        assert _ask(host_program, [_line("profile", good, **brk)])[0] == "refused args bit_error_profile: bad arguments"
+    # nothing but nd, N_symb, bps and the words is read: no fast-path geometry, no precision, pilots anywhere, any Nfft
+    ok = [dict(n_frames=0), dict(n_frames=(1 << 31) - 1), dict(nfft=100), dict(pilots_in_band=0), dict(np=0), dict(t_guard=9999),
+          dict(f64=1), dict(n_symb=22369621), dict(nd=1, n_symb=1, bps=1), dict(bps=8), dict(descr=ec.DESCR), dict(mmse=1)]
+    assert _ask(host_program, [_line("profile", good, **o) for o in ok]) == ["ok"] * len(ok)
+    assert _ask(host_program, [_line("profile", good, bps=9)])[0].startswith("refused frame_bits ")
+
+
+@pytest.mark.parametrize("entry", ["profile", "study5", "study4"])
+def test_gap_bins_edges(host_program, entry):
+    cmd, good, what = {"profile": ("profile", ec.good_profile(), "bit_error_profile"),
+                       "study5": ("study", ec.good_study(5, 0), "error_study"),
+                       "study4": ("study", ec.good_study(4, 1), "error_study")}[entry]
+    got = _ask(host_program, [_line(cmd, good, gap_bins=g) for g in (0, 1, 1024, 1025, -1)])
+    assert got == [f"refused gap_bins {what}: gap_bins must be 1 .. 1024 (0)", "ok", "ok",
+                   f"refused gap_bins {what}: gap_bins must be 1 .. 1024 (1025)", f"refused gap_bins {what}: gap_bins must be 1 .. 1024 (-1)"]
+
+
+@pytest.mark.parametrize("receiver", [5, 4])
+@pytest.mark.parametrize("f64", [0, 1])
+def test_error_study_first_refusal_wins_in_the_documented_order(host_program, receiver, f64):
+    order, good = ec.study_order(receiver, f64), ec.good_study(receiver, f64)
+    got = _ask(host_program, [_line("study", ec.broken_from(good, order, i)) for i in range(len(order) + 1)])
+    for i, (rid, _, msg) in enumerate(order):
+        assert got[i] == f"refused {rid} {msg}", (i, rid, got[i])
+    assert got[-1] == "ok"
+    what = "ber_sweep_task5" if receiver == 5 else "ber_sweep_task4"
+    assert _ask(host_program, [_line("study", good, plan=0)])[0] == f"refused args {what}: bad arguments"
+    ok = [dict(side=0), dict(n_points=0, points=0), dict(fpp=0), dict(reg="none", descr=0), dict(reg="none", descr=0, side=0),
+          dict(h="none"), dict(h="none", taps="0,3,7"), dict(h=64), dict(max_chunk=1), dict(max_chunk=65535), dict(frame0=(1 << 32) - 6)]
+    assert _ask(host_program, [_line("study", good, **o) for o in ok]) == ["ok"] * len(ok)
+
+
+def test_the_sweeps_own_refusals_in_their_own_words(host_program):
+    """The two examples of a refusal that is the sweep's: a Register without the plan's DeScrambler (and a DeScrambler without a
+    Register), and what receiver 5 has no argument for; the fading forms name the fading sweeps."""
+    g5, g4 = ec.good_study(5, 0), ec.good_study(4, 0)
+    needs = "with the Scrambler on the plan needs a DeScrambler with the same register (ofdm_rx_plan_set_descrambler)"
+    asks = [(dict(g5, descr=0), f"refused descr_needed ber_sweep_task5: {needs}"),
+            (dict(g4, descr=0), f"refused descr_needed ber_sweep_task4: {needs}"),
+            (dict(g5, descr=ec.DESCR ^ 1), f"refused descr_needed ber_sweep_task5: {needs}"),
+            (dict(g5, reg="none"), "refused descr_unwanted ber_sweep_task5: the plan descrambles but the frames are not scrambled"),
+            (dict(g4, reg="none"), "refused descr_unwanted ber_sweep_task4: the plan descrambles but the frames are not scrambled"),
+            (dict(g5, h="none", taps="0,3", mmse=1), "refused mmse_fading ber_sweep_task5_fading: an MMSE-mode plan is built for one channel h "
+                                                     "(ofdm_rx_plan_set_mmse)"),
+            (dict(g5, h="none", taps="0,3,3"), "refused fade_twice ber_sweep_task5_fading: tap delay 3 given twice"),
+            (dict(g4, h="none", taps="0,4097"), "refused fade_delay ber_sweep_task4_fading: tap delay 4097 outside 0 .. 4096"),
+            (dict(g4, h=65), "refused tap_count tx_frames_fused: 65 nonzero channel taps (at most 64)")]
+    assert _ask(host_program, [_line("study", a) for a, _ in asks]) == [w for _, w in asks]
+    imp = "refused task5_imp error_study: receiver 5 runs as ber_sweep_task5 does: no sto_mode / cfo_mode, time_desync and freq_desync 0, mp_desync 1"
+    for brk in (dict(sto_mode=1), dict(cfo_mode=2), dict(time_desync=1), dict(freq_desync=1), dict(mp_desync=0)):
+        assert _ask(host_program, [_line("study", g5, **brk)])[0] == imp, brk
+    for brk in (dict(sto_mode=0, cfo_mode=0), dict(time_desync=0), dict(freq_desync=0), dict(mp_desync=0)):
+        assert _ask(host_program, [_line("study", g4, **brk)])[0] == "ok", brk
+
+
+def test_chunk_rule_at_its_edges(host_program):
+    """max(1, min(cap or budget // (the matching sweep's bytes per frame + the two bit buffers), frames_per_point, 65535))."""
+    combos = [(f64, rcv, scr, ft, fpp, cap) for f64 in (0, 1) for rcv in (5, 4) for scr in (0, 1) for ft in (0, 3)
+              for fpp in (1, 5, 65535, 65536, 10 ** 7) for cap in (0, 1, 3, 65535)]
+    got = _ask(host_program, [_line("chunk", ec.SHAPE, f64=f, receiver=r, scr=s, fade_taps=t, fpp=p, cap=c) for f, r, s, t, p, c in combos])
+    for (f64, rcv, scr, ft, fpp, cap), g in zip(combos, got):
+        chunk, fb, bits = map(int, g.split())
+        assert fb == ec.frame_bytes(ec.SHAPE, f64, scr, rcv == 4, ft) and bits == 8 * 30 == ec.bit_bytes(ec.SHAPE)
+        assert chunk == ec.chunk_model(ec.SHAPE, f64, rcv, scr, ft, fpp, cap), (f64, rcv, scr, ft, fpp, cap)
+        assert 1 <= chunk <= min(fpp, 65535)
+    big = dict(ec.SHAPE, nfft=8192, t_guard=1024, n_symb=64, n_carrier=6000, np=1500, nd=4500, frame_words=36000)
+    for rcv in (5, 4):                                               # the budget, not the grid, is the limit
+        a = int(_ask(host_program, [_line("chunk", big, f64=1, receiver=rcv, fpp=10 ** 6, cap=0)])[0].split()[0])
+        assert a == ec.chunk_model(big, 1, rcv, 0, 0, 10 ** 6, 0) and 1 <= a < 65535
+    huge = dict(big, n_symb=8192)                                    # a frame beyond the whole budget: one frame per chunk
+    assert int(_ask(host_program, [_line("chunk", huge, f64=1, receiver=4, fpp=10, cap=0)])[0].split()[0]) == 1
+
+
+def test_flush_cap_launch_shape_and_lds_budget(host_program):
+    """frames * frame_bits <= 2^32 - 1 for the frames of one workgroup, at the edges of the quotient; the symbol table leaves the
+    LDS at the first N_symb that does not fit beside the others."""
+    geoms = [dict(nd=48, n_symb=5, bps=4), dict(nd=1, n_symb=1, bps=1), dict(nd=8191, n_symb=1, bps=8), dict(nd=1705, n_symb=4, bps=6),
+             dict(nd=65535, n_symb=65537, bps=1),                                   # frame_bits = 2^32 - 1: one frame per workgroup
+             dict(nd=65536, n_symb=32768, bps=1), dict(nd=32768, n_symb=32768, bps=2),   # 2^31: one; 2^31 + ..: one
+             dict(nd=1, n_symb=(1 << 31) - 1, bps=1), dict(nd=3, n_symb=477218588, bps=1),  # two frames; three, with 3 bits to spare
+             dict(nd=48, n_symb=16247, bps=4), dict(nd=48, n_symb=16248, bps=4),    # gap_bins 64: the last N_symb in LDS, the first outside
+             dict(nd=8192, n_symb=7139, bps=8), dict(nd=8192, n_symb=7140, bps=8)]  # gap_bins 1024
+    combos = [(g, gb, fr) for g in geoms for gb in (1, 64, 1024) for fr in (1, 5, 1023, 1024, 1025, 65535, (1 << 31) - 1)]
+    got = _ask(host_program, [_line("pass", ec.SHAPE, g, gap_bins=gb, frames=fr) for g, gb, fr in combos])
+    seen = set()
+    for (g, gb, fr), line in zip(combos, got):
+        shape = dict(ec.SHAPE, **g)
+        assert tuple(map(int, line.split())) == ec.pass_model(shape, gb, fr), (g, gb, fr, line)
+        threads, sym, lds, flush, launch, grid = map(int, line.split())
+        fbits = ec.frame_bits(shape)
+        assert threads == 256 and flush >= 1 and flush * fbits <= ec.COUNTER_MAX < (flush + 1) * fbits
+        assert 1 <= grid <= 1024 and grid <= launch <= fr and -(-launch // grid) <= flush    # no workgroup beyond its cap
+        assert launch == fr or launch == flush * 1024 or launch == 1 << 31
+        # (nd beyond the 8192 bins of the largest Nfft: only the cap's arithmetic is asked about, no plan has such a frame)
+        assert (lds <= ec.LDS_LIMIT or shape["nd"] > 8192) and lds == 4 * (shape["nd"] + sym * shape["n_symb"] + shape["bps"] + gb + 1 + 20)
+        assert sym == (4 * (shape["nd"] + shape["n_symb"] + shape["bps"] + gb + 1 + 20) <= ec.LDS_LIMIT)
+        seen.add((sym, flush == 1))
+    # (a symbol table that fits in LDS beside nd counters bounds frame_bits far below 2^31: that pair cannot occur)
+    assert seen == {(0, False), (0, True), (1, False)}
+    edge = dict(ec.SHAPE, nd=48, bps=4)
+    a, b = (tuple(map(int, _ask(host_program, [_line("pass", edge, n_symb=n, gap_bins=64, frames=1)])[0].split())) for n in (16247, 16248))
+    assert (a[1], b[1]) == (1, 0) and a[2] == 65536 and b[2] == 4 * (48 + 4 + 65 + 20)
+
+
+@pytest.mark.parametrize("bps", ec.BPS)
+def test_position_function_at_its_edges_and_its_running_form(host_program, bps):
+    for nd, n_symb in ((48, 5), (1, 3), (7, 2), (1705, 4), (8191, 1)):
+        fbits = nd * n_symb * bps
+        at = sorted({0, bps - 1, bps, nd * bps - 1, nd * bps, fbits - 1} & set(range(fbits)))
+        got = _ask(host_program, [_line("pos", nd=nd, bps=bps, i=i) for i in at])
+        for i, g in zip(at, got):
+            assert tuple(map(int, g.split())) == ec.position(i, nd, bps), (nd, bps, i)
+        assert tuple(map(int, got[0].split())) == (0, 0, 0)
+        assert tuple(map(int, got[-1].split())) == (n_symb - 1, nd - 1, bps - 1)
+        # the running form from every word start a frame of this geometry has (and the last one before 2^32)
+        starts = sorted({0, 32, 64, 32 * ((fbits - 1) // 32), 32 * (nd * bps // 32), ((1 << 32) - 1) // 32 * 32})
+        got = _ask(host_program, [_line("walk", nd=nd, bps=bps, i=i) for i in starts])
+        for i, g in zip(starts, got):
+            v = list(map(int, g.split()))
+            want = [x for delta in range(33) for x in ec.position(i + delta, nd, bps)]
+            assert v[:99] == want and v[99:] == want, (nd, bps, i)
+    got = list(map(int, _ask(host_program, [_line("div", bps=bps)])[0].split()))
+    assert got == [n // bps for n in range(64)] == [ec.small_div(n, ec.recip(bps)) for n in range(64)]
+
+
+def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_device_runtime():
+    src = open(HEADER).read()
+    for fmt in ("%s: a frame must have at most 2^32 - 1 bits of 1 .. %d per symbol (%lld, %d)", "%s: gap_bins must be 1 .. %d (%d)",
+                "%s: no output is given", "%s: n_frames must be 0 .. 2^31 - 1 (%lld)", "%s: the plan has no data carriers",
+                "%s: receiver must be 4 (rx_chain_task4) or 5 (rx_chain_task5) (%d)", "%s: side must be 0 (payload) or 1 (channel) (%d)",
+                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+        assert f'"{fmt}"' in src, fmt
+    main = open(os.path.join(ROOT, "tests", "host", "error_plan_main.cpp")).read()
+    names = re.findall(r'"(\w+)"', re.search(r"IDS\[ERR_REFUSALS\] = \{(.*?)\};", main, re.S).group(1))
+    txf = open(os.path.join(CSRC, "txf_plan.hpp")).read()
+    txf_enum = re.search(r"TXF_OK = 0,(.*?)TXF_REFUSALS", txf, re.S).group(1)
+    own = re.search(r"enum \{ ERR_REFUSE_FRAMES = TXF_REFUSALS,(.*?)ERR_REFUSALS \}", src, re.S).group(1)
+    assert [n.upper() for n in names[1:]] == re.findall(r"TXF_REFUSE_(\w+)", txf_enum) + ["FRAMES"] + re.findall(r"ERR_REFUSE_(\w+)", own)
+    assert "hip/" not in src and "__global__" not in src and "hipLaunch" not in src
+    assert set(re.findall(r'#include [<"]([^>"]+)[>"]', src)) <= {"algorithm", "cstddef", "cstdint", "txf_plan.hpp"}
+    hip = open(os.path.join(CSRC, "ofdm_error_study.hip")).read()
+    assert '#include "error_plan.hpp"' in hip and "err_profile_prelude(" in hip and "err_study_prelude(" in hip
+    assert "err_chunk(" in hip and "err_pass(" in hip and "TXF_WS_BUDGET" not in hip
+    assert "err_position(" in hip and "err_advance(" in hip
+    assert "rx_chain_task5_run(" in hip and "rx_chain_task4_run(" in hip and "txf_generate(" in hip     # called, not rewritten
+    assert "hipfft" not in hip.lower() and "rocblas" not in hip.lower()
