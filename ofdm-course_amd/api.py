@@ -824,6 +824,32 @@ class RxPlan:
             raise OfdmError(f"{what}: seeds must have one entry per SNR point")
         return snr, sd
 
+    def _study_args(self, what, SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift):
+        """The generator arguments every study entry takes, as its C signature groups them -> (keep, n_points, chan = (h, h_len,
+        tap_delay, tap_power, n_taps), imp = (sto_mode, sto_value, cfo_mode, cfo_value), scr_reg15, pts = (snr_db, seeds,
+        n_points)).  keep: the arrays behind the pointers; the caller holds it until the call has returned."""
+        snr, sd = self._points(SNRs, seeds, seed, what)
+        keep, ph, nh, pr = self._fused_args(h, Register, what)
+        pdl, ppw, nt = None, None, 0
+        if fading is not None:                                   # (with h too: the library's refusal)
+            keep_f, pdl, ppw, nt = self._fading_args(None, fading, what)
+            keep += keep_f
+        sm, sv = _imp_mode(Time_Delay, what)
+        cm, cv = _imp_mode(Freq_Shift, what)
+        return (keep + (snr, sd), snr.size, (ph, nh, pdl, ppw, nt), (sm, int(sv), cm, float(cv)), pr,
+                (snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), snr.size))
+
+    @staticmethod
+    def _counts(device, count, *tables):
+        """What a study's means are formed with -> (the counter `tables` as int64: views of the numpy uint64 arrays -- a count of
+        2^63 is out of reach -- the device tensors as they are; `count` as a float64 divisor: a tensor on the device, so that the
+        division is an IEEE division as numpy's, where a Python scalar would multiply by its reciprocal (None: no divisor is made,
+        and on the device nothing is launched for it); the cast to float64)."""
+        if device is None:
+            return [a.view(np.int64) for a in tables], None if count is None else np.float64(count), lambda a: a.astype(np.float64)
+        div = None if count is None else torch.full((1,), float(count), dtype=torch.float64, device=torch.device(device))
+        return list(tables), div, lambda a: a.double()
+
     def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None, Time_Delay=None,
                         Freq_Shift=None, want_draws=False, fading=None, want_taps=False):
         """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
@@ -962,25 +988,16 @@ class RxPlan:
         window, with want_peak) (+ frame_power=[n_points, frames_per_point, Nfft] with want_frame_power)); torch tensors on
         `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on max_frames_per_chunk
         (> 0: the frames of a chunk of the plan-owned workspace)."""
-        snr, sd = self._points(SNRs, seeds, seed, "spectrum_study")
-        n, fpp = snr.size, int(frames_per_point)
+        keep, n, chan, imp, pr, pts = self._study_args("spectrum_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp = int(frames_per_point)
         first = self.T_guard if first is None else int(first)
         nw = int(n_windows)
         (sums, peak, fp), ptrs, flags = self._outputs(
             device, ((n, self.Nfft), np.float64), ((n, self.Nfft), np.float64) if want_peak else None,
             ((n, max(fpp, 0), self.Nfft), np.float64) if want_frame_power else None)
-        keep, ph, nh, pr = self._fused_args(h, Register, "spectrum_study")
-        pdl, ppw, nt = None, None, 0
-        if fading is not None:                                   # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "spectrum_study")
-        sm, sv = _imp_mode(Time_Delay, "spectrum_study")
-        cm, cv = _imp_mode(Freq_Shift, "spectrum_study")
-        L.check(self.lib.ofdm_spectrum_study(self.handle, ph, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), pr,
-                                             snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0),
-                                             int(max_frames_per_chunk), first, nw, *ptrs, flags), "spectrum_study")
-        count = float(fpp * nw)
-        if device is not None:                                   # a tensor divisor: an IEEE division, as numpy's (a Python scalar
-            count = torch.full((1,), count, dtype=torch.float64, device=sums.device)   # would multiply by its reciprocal)
+        L.check(self.lib.ofdm_spectrum_study(self.handle, *chan, *imp, pr, *pts, fpp, int(frame0), int(max_frames_per_chunk), first,
+                                             nw, *ptrs, flags), "spectrum_study")
+        _, count, _ = self._counts(device, fpp * nw)
         with np.errstate(divide="ignore", invalid="ignore"):     # no frames: NaN, the mean of nothing
             mean = sums / count
         out = dict(power_sums=sums, mean_power=mean, amp_rms=mean.sqrt() if device is not None else np.sqrt(mean))
@@ -1008,8 +1025,8 @@ class RxPlan:
         [n_points, frames_per_point] with want_frames)); torch tensors on `device` (no host synchronisation) when it is given,
         numpy arrays otherwise.  No output depends on max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned
         workspace)."""
-        snr, sd = self._points(SNRs, seeds, seed, "sync_study")
-        n, fpp = snr.size, int(frames_per_point)
+        keep, n, chan, imp, pr, pts = self._study_args("sync_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp = int(frames_per_point)
         W = self.T_guard if width is None else int(width)
         n_out = max(self.frame_samples - W - self.Nfft, 0) if 1 <= W <= 1024 else 0     # (a bad width is the library's refusal)
         fa = max(fpp, 0)
@@ -1018,22 +1035,11 @@ class RxPlan:
             ((n, n_out), np.uint64), ((n,), np.uint64), ((n, self.Nfft + self.T_guard), np.uint64), ((n, 2), np.float64),
             ((n, fa), np.int64) if want_frames else None, ((n, fa), np.int32) if want_frames else None,
             ((n, fa), np.float64) if want_frames else None)
-        keep, ph_, nh, pr = self._fused_args(h, Register, "sync_study")
-        pdl, ppw, nt = None, None, 0
-        if fading is not None:                                   # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "sync_study")
-        sm, sv = _imp_mode(Time_Delay, "sync_study")
-        cm, cv = _imp_mode(Freq_Shift, "sync_study")
-        L.check(self.lib.ofdm_sync_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), pr,
-                                         snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0),
-                                         int(max_frames_per_chunk), W, *ptrs, flags), "sync_study")
-        if device is None:                                       # int64 views: a count of 2^63 is out of reach
-            drop, tgh, fall, ph = (a.view(np.int64) for a in (drop, tgh, fall, ph))
-            count = np.float64(fpp)
-        else:                                                    # a tensor divisor: an IEEE division, as numpy's
-            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
+        L.check(self.lib.ofdm_sync_study(self.handle, *chan, *imp, pr, *pts, fpp, int(frame0), int(max_frames_per_chunk), W, *ptrs,
+                                         flags), "sync_study")
+        (drop, tgh, fall, ph), count, f64 = self._counts(device, fpp, drop, tgh, fall, ph)
         with np.errstate(divide="ignore", invalid="ignore"):     # no frame added: NaN, the mean of nothing
-            mean = sums / (fpp - drop).double() if device is not None else sums / (fpp - drop).astype(np.float64)
+            mean = sums / f64(fpp - drop)
             mae = ffo[:, 0] / count
         out = dict(acf_sums=sums, acf_dropped=drop, mean_acf=mean, tg_hist=tgh, fallback=fall, phase_hist=ph, ffo_err=ffo,
                    mean_abs_ffo_err=mae)
@@ -1072,8 +1078,8 @@ class RxPlan:
             bn, blo, bhi = int(bins["n"]), float(bins["lo"]), float(bins["hi"])
         except (TypeError, KeyError, ValueError):
             raise OfdmError("fine_study: bins must be dict(n=, lo=, hi=)") from None
-        snr, sd = self._points(SNRs, seeds, seed, "fine_study")
-        n, fpp = snr.size, int(frames_per_point)
+        keep, n, chan, imp, pr, pts = self._study_args("fine_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp = int(frames_per_point)
         Lt = _fine_len(self.n_pilots, self.N_symb, variant)
         fa, nb = max(fpp, 0), max(bn, 0)
         fr = lambda dt: ((n, fa), dt) if want_frames else None
@@ -1082,27 +1088,14 @@ class RxPlan:
                           ((n,), np.uint64), ((n,), np.uint64), ((n,), np.uint64), ((n, 2), np.float64), ((n, 2), np.float64),
                           ((n,), np.uint64), ((n,), np.uint64), ((n, self.Nfft + self.T_guard), np.uint64), fr(np.float64),
                           fr(np.float64), fr(np.int32), fr(np.int64), fr(np.int32), fr(np.int64))
-        keep, ph_, nh, pr = self._fused_args(h, Register, "fine_study")    # keep / keep_f: the arrays behind the pointers, alive
-        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
-        if fading is not None:                                   # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "fine_study")
-        sm, sv = _imp_mode(Time_Delay, "fine_study")
-        cm, cv = _imp_mode(Freq_Shift, "fine_study")
-        L.check(self.lib.ofdm_fine_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(bool(time_desync)),
-                                         int(bool(freq_desync)), _FINE_VARIANTS[variant], pr, snr.ctypes.data_as(C.c_void_p),
-                                         sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), int(max_frames_per_chunk), bn, blo,
+        L.check(self.lib.ofdm_fine_study(self.handle, *chan, *imp, int(bool(time_desync)), int(bool(freq_desync)),
+                                         _FINE_VARIANTS[variant], pr, *pts, fpp, int(frame0), int(max_frames_per_chunk), bn, blo,
                                          bhi, *ptrs, flags), "fine_study")
-        if device is None:                                       # int64 views: a count of 2^63 is out of reach
-            drop, keepc, hist, below, above, tnan, pnan, used, tgh = (a.view(np.int64) for a in
-                                                                      (drop, keepc, hist, below, above, tnan, pnan, used, tgh))
-            count = np.float64(fpp)
-            finite = (fpp - tnan).astype(np.float64)
-        else:                                                    # tensor divisors: IEEE divisions, as numpy's
-            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
-            finite = (fpp - tnan).double()
+        (drop, keepc, hist, below, above, tnan, pnan, used, tgh), count, f64 = self._counts(
+            device, fpp, drop, keepc, hist, below, above, tnan, pnan, used, tgh)
         with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
-            rate = (keepc.double() if device is not None else keepc.astype(np.float64)) / count
-            mae = terr[:, 0] / finite
+            rate = f64(keepc) / count
+            mae = terr[:, 0] / f64(fpp - tnan)
         edges = np.linspace(blo, bhi, nb + 1)
         if device is not None:                                   # like every other output (and papr_study's edges)
             edges = torch.from_numpy(edges).to(sums.device)
@@ -1135,8 +1128,8 @@ class RxPlan:
         (+ ifo, status, n_above int32, tg_position int64, freq_offset float64 = [n_points, frames_per_point] with want_frames));
         torch tensors on `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on
         max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace)."""
-        snr, sd = self._points(SNRs, seeds, seed, "ifo_study")
-        n, fpp, span = snr.size, int(frames_per_point), int(err_span)
+        keep, n, chan, imp, pr, pts = self._study_args("ifo_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp, span = int(frames_per_point), int(err_span)
         fa, ne = max(fpp, 0), 2 * span + 1 if 1 <= span <= 4096 else 0   # (a bad span is the library's refusal)
         fr = lambda dt: ((n, fa), dt) if want_frames else None
         N = self.Nfft
@@ -1145,23 +1138,10 @@ class RxPlan:
                           ((n,), np.uint64), ((n, ne), np.uint64), ((n,), np.uint64), ((n,), np.uint64), ((n,), np.uint64),
                           ((n, 2), np.float64), ((n,), np.uint64), fr(np.int32), fr(np.int32), fr(np.int32), fr(np.int64),
                           fr(np.float64))
-        keep, ph_, nh, pr = self._fused_args(h, Register, "ifo_study")     # keep / keep_f: the arrays behind the pointers, alive
-        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
-        if fading is not None:                                   # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "ifo_study")
-        sm, sv = _imp_mode(Time_Delay, "ifo_study")
-        cm, cv = _imp_mode(Freq_Shift, "ifo_study")
-        L.check(self.lib.ofdm_ifo_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), _ifo_stage(stage, "ifo_study"),
-                                        int(time_desync), pr, snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
+        L.check(self.lib.ofdm_ifo_study(self.handle, *chan, *imp, _ifo_stage(stage, "ifo_study"), int(time_desync), pr, *pts, fpp,
                                         int(frame0), int(max_frames_per_chunk), span, *ptrs, flags), "ifo_study")
-        if device is None:                                       # int64 views: a count of 2^63 is out of reach
-            drop, above, hist, none, ehist, ebelow, eabove, hit, fall = (a.view(np.int64) for a in
-                                                                         (drop, above, hist, none, ehist, ebelow, eabove, hit, fall))
-            count = np.float64(fpp)
-            f64 = lambda a: a.astype(np.float64)
-        else:                                                    # tensor divisors: IEEE divisions, as numpy's
-            count = torch.full((1,), float(fpp), dtype=torch.float64, device=sums.device)
-            f64 = lambda a: a.double()
+        (drop, above, hist, none, ehist, ebelow, eabove, hit, fall), count, f64 = self._counts(
+            device, fpp, drop, above, hist, none, ehist, ebelow, eabove, hit, fall)
         with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
             mean = sums / f64(fpp - drop)
             hit_rate, none_rate = f64(hit) / count, f64(none) / count
@@ -1204,8 +1184,8 @@ class RxPlan:
             raise OfdmError("channel_study: bins must be dict(n=, lo=, hi=)") from None
         if extra:
             raise OfdmError(f"channel_study: unknown bins keys {sorted(extra)}")
-        snr, sd = self._points(SNRs, seeds, seed, "channel_study")
-        n, fpp = snr.size, int(frames_per_point)
+        keep, n, chan, imp, pr, pts = self._study_args("channel_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp = int(frames_per_point)
         fa, nb = max(fpp, 0), bn if 1 <= bn <= 4096 else 0       # (a bad count is the library's refusal)
         nc, npil = self.N_carrier, self.n_pilots
         fr = ((n, fa), np.float64) if want_frame_nmse else None
@@ -1215,21 +1195,10 @@ class RxPlan:
                           ((n,), np.float64), ((n,), np.float64), fr, fr, ((n, nb), np.uint64), ((n,), np.uint64),
                           ((n,), np.uint64), ((n,), np.uint64), ((n, 4), np.uint64))
         thr = np.zeros(nb + 1, np.float64)
-        keep, ph_, nh, pr = self._fused_args(h, Register, "channel_study")  # keep / keep_f: the arrays behind the pointers, alive
-        pdl, ppw, nt = None, None, 0                                        # until the call has returned (as in sync_study)
-        if fading is not None:                                   # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "channel_study")
-        sm, sv = _imp_mode(Time_Delay, "channel_study")
-        cm, cv = _imp_mode(Freq_Shift, "channel_study")
-        L.check(self.lib.ofdm_hest_study(self.handle, ph_, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(time_desync),
-                                         int(freq_desync), pr, snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp,
-                                         int(frame0), int(max_frames_per_chunk), bn, blo, bhi, *ptrs,
-                                         thr.ctypes.data_as(C.c_void_p), flags), "hest_study")
-        if device is None:                                       # int64 views: a count of 2^63 is out of reach
-            drop, pdrop, hist, below, above, hnan, stc = (a.view(np.int64) for a in (drop, pdrop, hist, below, above, hnan, stc))
-            f64 = lambda a: a.astype(np.float64)
-        else:                                                    # tensor divisors: IEEE divisions, as numpy's
-            f64 = lambda a: a.double()
+        L.check(self.lib.ofdm_hest_study(self.handle, *chan, *imp, int(time_desync), int(freq_desync), pr, *pts, fpp, int(frame0),
+                                         int(max_frames_per_chunk), bn, blo, bhi, *ptrs, thr.ctypes.data_as(C.c_void_p), flags),
+                "hest_study")
+        (drop, pdrop, hist, below, above, hnan, stc), _, f64 = self._counts(device, None, drop, pdrop, hist, below, above, hnan, stc)
         with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
             kept = f64(fpp - drop)
             mean_est, mean_true, profile = esum / kept, tsum / kept, err / kept
@@ -1266,20 +1235,11 @@ class RxPlan:
             sd_ = {"payload": 0, "channel": 1}[side]
         except (KeyError, TypeError):
             raise OfdmError('error_study: receiver must be "task5" or "task4", side "payload" or "channel"') from None
-        snr, sd = self._points(SNRs, seeds, seed, "error_study")
-        n, fpp = snr.size, int(frames_per_point)
-        gb = int(gap_bins)
+        keep, n, chan, imp, pr, pts = self._study_args("error_study", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        fpp, gb = int(frames_per_point), int(gap_bins)
         arrs, ptrs, flags = self._outputs(device, *_error_specs(self, n, max(fpp, 0), gb, want_frames, want_map))
-        keep, ph, nh, pr = self._fused_args(h, Register, "error_study")  # keep / keep_f: the arrays behind the pointers, alive
-        pdl, ppw, nt = None, None, 0                                     # until the call has returned
-        if fading is not None:                                           # (with h too: the library's refusal)
-            keep_f, pdl, ppw, nt = self._fading_args(None, fading, "error_study")
-        sm, sv = _imp_mode(Time_Delay, "error_study")
-        cm, cv = _imp_mode(Freq_Shift, "error_study")
-        L.check(self.lib.ofdm_error_study(self.handle, rcv, ph, nh, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(time_desync),
-                                          int(freq_desync), int(mp_desync), snr.ctypes.data_as(C.c_void_p),
-                                          sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr, sd_, gb, int(max_frames_per_chunk),
-                                          *ptrs, flags), "error_study")
+        L.check(self.lib.ofdm_error_study(self.handle, rcv, *chan, *imp, int(time_desync), int(freq_desync), int(mp_desync), *pts, fpp,
+                                          int(frame0), pr, sd_, gb, int(max_frames_per_chunk), *ptrs, flags), "error_study")
         return _error_result(self, device is not None, max(fpp, 0), arrs)
 
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,

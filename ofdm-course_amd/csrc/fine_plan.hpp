@@ -14,7 +14,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "sync_plan.hpp"     // sync_phase_bin, sync_use, SYNC_LDS_LIMIT; txf_plan.hpp and t4_route.hpp through it
+#include "sync_plan.hpp"     // sync_phase_bin, SYNC_LDS_LIMIT; txf_plan.hpp and t4_route.hpp through it
 
 #if defined(__HIPCC__)
 #define FINE_HD __host__ __device__
@@ -105,24 +105,13 @@ inline int fine_rx_prelude(const TxfShape* plan, bool x, bool f64_flag, int64_t 
   return TXF_OK;
 }
 
-// ---- ofdm_fine_study.  c: the generator arguments as the sweeps fill them; both_channels: h and a tap-delay line are given.  The
-// order of its checks, the generator's in front:
-//   bad arguments (plan, n_points >= 0, frames_per_point >= 0, max_frames_per_chunk 0 .. 65535: the receiver's limit) -> snr_db /
-//   seeds -> too many points -> the plan (as above, the streams of one point) -> sto_mode / cfo_mode -> register entries 0 / 1 ->
-//   h and taps together -> the channel (as the generator refuses it) -> the capture (above) -> both sync flags off -> the route of
-//   the receiver's front end (t4_route_choose, in the receiver's words) -> the bins (n >= 1, lo < hi, both finite) -> an output
+// ---- ofdm_fine_study.  The order of its checks: the front every study shares (txf_study_prelude: the generator's arguments,
+// max_frames_per_chunk 0 .. 65535, the receiver's limit) -> the capture (above) -> both sync flags off -> the route of the
+// receiver's front end (t4_route_choose, in the receiver's words) -> the bins (n >= 1, lo < hi, both finite) -> an output
 inline int fine_study_prelude(const TxfCall& c, bool both_channels, int time_desync, int freq_desync, const FineCapture& cap,
                               const FineBins& bins, TxfChannel& ch, TxfGains& g, TxfWhy& w) {
   static const char* const WHAT = "fine_study";
-  if (const int id = txf_check_args(c.plan && c.n_points >= 0 && c.n_frames >= 0 && c.max_chunk >= 0 && c.max_chunk <= 65535, WHAT, w))
-    return id;
-  if (const int id = txf_check_sweep(c, WHAT, w)) return id;
-  if (const int id = txf_check_modes(c.sto_mode, c.cfo_mode, WHAT, w)) return id;
-  if (c.scr_reg15)
-    for (int m = 0; m < 15; ++m)
-      if (c.scr_reg15[m] > 1) return txf_refuse(w, TXF_REFUSE_REGISTER, "%s: register entries must be 0 or 1", WHAT);
-  if (both_channels) return txf_refuse(w, FINE_REFUSE_BOTH, "%s: give h (one channel for every frame) or taps (a channel per frame), not both", WHAT);
-  if (const int id = txf_call_channel(c, c.plan->f64 != 0, WHAT, ch, g, w)) return id;
+  if (const int id = txf_study_prelude(c, both_channels, FINE_REFUSE_BOTH, WHAT, ch, g, w, 65535)) return id;
   if (const int id = fine_check_capture(*c.plan, cap, WHAT, w)) return id;
   if (!(time_desync || freq_desync))
     return txf_refuse(w, FINE_REFUSE_SYNC, "%s: time_desync and freq_desync are both off: the receiver runs no fine_sync, there is nothing to study", WHAT);

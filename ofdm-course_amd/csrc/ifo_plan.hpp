@@ -16,7 +16,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "sync_plan.hpp"     // sync_use, SYNC_LDS_LIMIT; txf_plan.hpp and t4_route.hpp through it
+#include "sync_plan.hpp"     // SYNC_LDS_LIMIT; txf_plan.hpp and t4_route.hpp through it
 
 #if defined(__HIPCC__)
 #define IFO_HD __host__ __device__
@@ -75,25 +75,15 @@ inline int ifo_rx_prelude(const TxfShape* plan, bool rx, bool f64_flag, int64_t 
   return ifo_check_capture(*plan, cap, WHAT, w);
 }
 
-// ---- ofdm_ifo_study.  c: the generator arguments as the sweeps fill them; both_channels: h and a tap-delay line are given.  The
-// order of its checks, the generator's in front:
-//   bad arguments (plan, n_points >= 0, frames_per_point >= 0, max_frames_per_chunk >= 0) -> snr_db / seeds -> too many points ->
-//   the plan (as above, the streams of one point) -> sto_mode / cfo_mode -> register entries 0 / 1 -> h and taps together -> the
-//   channel (as the generator refuses it) -> the capture (above)
+// ---- ofdm_ifo_study.  The order of its checks: the front every study shares (txf_study_prelude: the generator's arguments,
+// max_frames_per_chunk >= 0) -> the capture (above)
 inline int ifo_study_prelude(const TxfCall& c, bool both_channels, const IfoCapture& cap, TxfChannel& ch, TxfGains& g, TxfWhy& w) {
   static const char* const WHAT = "ifo_study";
-  if (const int id = txf_check_args(c.plan && c.n_points >= 0 && c.n_frames >= 0 && c.max_chunk >= 0, WHAT, w)) return id;
-  if (const int id = txf_check_sweep(c, WHAT, w)) return id;
-  if (const int id = txf_check_modes(c.sto_mode, c.cfo_mode, WHAT, w)) return id;
-  if (c.scr_reg15)
-    for (int m = 0; m < 15; ++m)
-      if (c.scr_reg15[m] > 1) return txf_refuse(w, TXF_REFUSE_REGISTER, "%s: register entries must be 0 or 1", WHAT);
-  if (both_channels) return txf_refuse(w, IFO_REFUSE_BOTH, "%s: give h (one channel for every frame) or taps (a channel per frame), not both", WHAT);
-  if (const int id = txf_call_channel(c, c.plan->f64 != 0, WHAT, ch, g, w)) return id;
+  if (const int id = txf_study_prelude(c, both_channels, IFO_REFUSE_BOTH, WHAT, ch, g, w)) return id;
   return ifo_check_capture(*c.plan, cap, WHAT, w);
 }
 
-// ---- the chunk of the study: frames of one point, budgeted on the generator's regions with the RX region (txf_plan.hpp) and,
+// ---- the chunk of the study: frames of one point, budgeted on the generator's regions with the RX region (txf_study_use) and,
 // beside the workspace, per frame one row of Nfft doubles (|S| of every bin), Nfft bytes (the bins above the threshold) and the
 // frame's scalars (TgPosition, FreqOffset, the total error: 8 bytes each; IFO, status, the count of bins above: 4 each, padded to
 // 40).  The AutoCorrFunction stage in front keeps nothing per frame on its search route (with OFDM_T4_FULL_ACF, an A/B switch, the

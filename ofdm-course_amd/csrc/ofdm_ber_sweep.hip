@@ -13,8 +13,8 @@
 //                                   reads them with a frame stride of 0 (ofdm_ber_sweep_task4_nmse, NMSE of T4:205-239)
 //
 // Host side: what a call decides -- its channel, the chunk, the argument checks in the entry's order -- is txf_plan.hpp's.
-// The sweeps share their outputs (txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points, the
-// receiver passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
+// The sweeps share their outputs (txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points of
+// txf_study.hpp, the receiver passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
 // per-point reduction.  The Task-5 entries fill a TxfCall and forward to t5_sweep, the Task-4 entries to t4_sweep; a fading
 // entry's TxfCall names a tap-delay line, and the generator then draws a channel per frame.
 #include <algorithm>
@@ -22,7 +22,7 @@
 
 #include "channel_resp.hpp"
 #include "scope_plan.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -151,13 +151,6 @@ __global__ __launch_bounds__(256) void t4_point_mer_kernel(const double* __restr
 // host side
 // ---------------------------------------------------------------------------------------------
 
-// the points of a sweep: point p at snr_db[p] with the Philox key seeds[p], frames frame0 .. frame0 + frames_per_point - 1
-struct TxfPoints {
-  const double* snr_db;
-  const uint64_t* seeds;
-  int64_t n_points, frames_per_point, frame0;
-};
-
 // the outputs both sweeps have: per point the bit errors and MER sums, per frame the errors and MER sums
 struct TxfSweepOut {
   void *err = nullptr, *fe = nullptr, *mer = nullptr, *fm = nullptr;
@@ -179,35 +172,6 @@ static int txf_sweep_outputs(Stage& st, int64_t n_points, int64_t frames_per_poi
   }
   if (!o.fe) OFDM_TRY(st.scratch(sizeof(uint32_t) * nf, &o.fe));
   if (o.mer && !o.fm) OFDM_TRY(st.scratch(sizeof(double) * 2 * nf, &o.fm));
-  return OFDM_OK;
-}
-
-// every point of a sweep, chunk by chunk of at most CH frames: the chunk generated into the workspace (imp: with the Task-4
-// impairments, the draws of the sweep's frame k at imp->sto[k] / imp->cfo[k]; fade: with a channel per frame, the chunk's
-// amplitudes at b.amp), then decode(b, nf, o) with o the sweep index of the chunk's first frame.  u: the workspace's regions.
-template <typename Decode>
-static int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfPoints& pt, const uint8_t* scr_reg15, int64_t CH,
-                            const TxfImp* imp, const TxfFade* fade, const TxfUse& u, Decode&& decode) {
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp ci;
-  if (imp) ci = *imp;
-  TxfFade cf;
-  if (fade) cf = *fade;
-  cf.amp = b.amp;
-  for (int64_t p = 0; p < pt.n_points; ++p) {
-    const double snr_lin = std::pow(10.0, pt.snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)pt.seeds[p], k1 = (uint32_t)(pt.seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < pt.frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, pt.frames_per_point - c0);
-      const int64_t o = p * pt.frames_per_point + c0;
-      if (imp) { ci.sto = imp->sto + o; ci.cfo = imp->cfo + o; }
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(pt.frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, nullptr,
-                            imp ? &ci : nullptr, fade ? &cf : nullptr));
-      OFDM_TRY(decode(b, nf, o));
-    }
-  }
   return OFDM_OK;
 }
 
@@ -376,10 +340,10 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   if (c.fading) dl = txf_delays(ch);
   // a plan in the h = ifft(H_LS) MMSE mode estimates every point at the point's own SNR (a host scalar of the stage's launch)
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, nullptr, c.fading ? &fade : nullptr, u,
-                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
-                              const double inv_snr = 1.0 / std::pow(10.0, pt.snr_db[k / frames_per_point] * 0.1);
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t k) {
+                              const double inv_snr = 1.0 / std::pow(10.0, pt.snr_db[p] * 0.1);
                               ScopeCall sc;
-                              if (sw.on) sc = acc.call(sw, k / frames_per_point);
+                              if (sw.on) sc = acc.call(sw, p);
                               OFDM_TRY(rx_chain_task5_run(pl, b.rx, nf, nullptr, (const uint8_t*)b.ref,
                                                           (uint32_t*)o.fe + k, b.hest, nullptr,
                                                           o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags, inv_snr,
@@ -510,10 +474,9 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
     }
   }
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, &imp, c.fading ? &fade : nullptr, u,
-                            [&](const TxfBuffers& b, int64_t nf, int64_t k) {
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t k) {
                               ScopeCall sc;                     // a chunk holds frames of one point: one grid per receiver call
                               if (a.scope) {
-                                const int64_t p = k / frames_per_point;
                                 sc.bins = a.bins; sc.skip = a.scope_skip; sc.half_width = a.half_width;
                                 sc.scale = scope_scale(a.bins, a.half_width);
                                 sc.density = ddens + (size_t)p * grid_elems; sc.dropped = ddrop + p;

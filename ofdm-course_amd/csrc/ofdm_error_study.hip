@@ -19,7 +19,7 @@
 //                                  the symbol counts go to the global table, one 64-bit atomic per OFDM symbol a word touches
 //                                  (a run of the word's errors in one symbol is one atomic, as for the map).
 // Integers added in no particular order: every output is bitwise independent of the chunking and of the grid.
-// ofdm_error_study generates each chunk with the fused generator (txf_generate), runs the Task-5 or the Task-4 receiver on it as
+// ofdm_error_study generates each chunk with the fused generator (txf_sweep_points), runs the Task-5 or the Task-4 receiver on it as
 // the matching sweep does (rx_chain_task5_run, rx_chain_task4_run: untouched) with bits_out in a chunk buffer, and profiles that
 // buffer.  side = channel: the plan's DeScrambler is masked for the call (DescrMask restores it on every return path), so the
 // receiver writes its raw decisions, which are compared against the scrambled bits.  Host side: the checks, the chunk and the
@@ -28,7 +28,7 @@
 #include <cmath>
 
 #include "error_plan.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -200,34 +200,32 @@ static int err_profile_frames(const TxfShape& s, int gap_bins, const uint32_t* b
 // the outputs of both entries for n points: the tables a caller did not ask for are still summed (scratch): the same kernel,
 // whatever the outputs; frame_errors and map only when asked for.  All zeroed on the launch stream.
 struct ErrOutputs {
-  void *errors, *fie, *carrier, *symbol, *label, *gap_hist, *gap_above, *frame_errors, *map;
-  size_t nd, ns, bps, gb, fpp;
+  unsigned long long *errors, *fie, *carrier, *symbol, *label, *gap_hist, *gap_above;
+  void *frame_errors, *map;
+  size_t nd, ns, bps, gb;
+  // the tables of point p; frame: the sweep index of the first frame counted (p * frames_per_point + its index in the point)
   ErrTables point(size_t p, size_t frame) const {
-    auto u = [](void* base, size_t at) { return (unsigned long long*)base + at; };
-    return ErrTables{u(errors, p), u(fie, p), u(carrier, p * nd), u(symbol, p * ns), u(label, p * bps), u(gap_hist, p * gb),
-                     u(gap_above, p), map ? u(map, p * ns * nd) : nullptr,
-                     frame_errors ? (uint32_t*)frame_errors + p * fpp + frame : nullptr};
+    return ErrTables{errors + p, fie + p, carrier + p * nd, symbol + p * ns, label + p * bps, gap_hist + p * gb, gap_above + p,
+                     map ? (unsigned long long*)map + p * ns * nd : nullptr,
+                     frame_errors ? (uint32_t*)frame_errors + frame : nullptr};
   }
 };
 
 static int err_outputs(Stage& st, const TxfShape& s, int gap_bins, size_t n_points, size_t frames_per_point, uint64_t* errors_out,
                        uint64_t* frames_in_error_out, uint64_t* carrier_out, uint64_t* symbol_out, uint64_t* label_out,
                        uint64_t* gap_hist_out, uint64_t* gap_above_out, uint32_t* frame_errors_out, uint64_t* map_out, ErrOutputs& o) {
-  o.nd = (size_t)s.nd; o.ns = (size_t)s.n_symb; o.bps = (size_t)s.bps; o.gb = (size_t)gap_bins; o.fpp = frames_per_point;
+  o.nd = (size_t)s.nd; o.ns = (size_t)s.n_symb; o.bps = (size_t)s.bps; o.gb = (size_t)gap_bins;
   const size_t one = sizeof(uint64_t);
-  hipStream_t stream = ctx().stream;
-  struct { void* user; size_t bytes; void** d; } tabs[] = {
-      {errors_out, one * n_points, &o.errors}, {frames_in_error_out, one * n_points, &o.fie},
-      {carrier_out, one * o.nd * n_points, &o.carrier}, {symbol_out, one * o.ns * n_points, &o.symbol},
-      {label_out, one * o.bps * n_points, &o.label}, {gap_hist_out, one * o.gb * n_points, &o.gap_hist},
-      {gap_above_out, one * n_points, &o.gap_above}};
-  for (auto& t : tabs) {
-    OFDM_TRY(t.user ? st.out(t.user, t.bytes, t.d) : st.scratch(t.bytes, t.d));
-    OFDM_HIP(hipMemsetAsync(*t.d, 0, t.bytes, stream));
-  }
+  OFDM_TRY(txf_table(st, errors_out, n_points, o.errors));
+  OFDM_TRY(txf_table(st, frames_in_error_out, n_points, o.fie));
+  OFDM_TRY(txf_table(st, carrier_out, o.nd * n_points, o.carrier));
+  OFDM_TRY(txf_table(st, symbol_out, o.ns * n_points, o.symbol));
+  OFDM_TRY(txf_table(st, label_out, o.bps * n_points, o.label));
+  OFDM_TRY(txf_table(st, gap_hist_out, o.gb * n_points, o.gap_hist));
+  OFDM_TRY(txf_table(st, gap_above_out, n_points, o.gap_above));
   OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * frames_per_point * n_points, &o.frame_errors));
   OFDM_TRY(st.out(map_out, one * o.ns * o.nd * n_points, &o.map));
-  if (o.map) OFDM_HIP(hipMemsetAsync(o.map, 0, one * o.ns * o.nd * n_points, stream));
+  if (o.map) OFDM_HIP(hipMemsetAsync(o.map, 0, one * o.ns * o.nd * n_points, ctx().stream));
   return OFDM_OK;
 }
 
@@ -280,19 +278,16 @@ extern "C" int ofdm_error_study(ofdm_rx_plan* pl, int receiver, const void* h, i
                                 uint64_t* gap_above_out, uint32_t* frame_errors_out, uint64_t* map_out, int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
+  const TxfStudyArgs g{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
+  const bool fading = g.fading();
   // the refusals of the matching sweep come in its own words: the call is named as that sweep names itself
-  TxfCall c(receiver == 4 ? (fading ? "ber_sweep_task4_fading" : "ber_sweep_task4") : (fading ? "ber_sweep_task5_fading" : "ber_sweep_task5"),
-            frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
+  TxfCall c = g.call(receiver == 4 ? (fading ? "ber_sweep_task4_fading" : "ber_sweep_task4")
+                                   : (fading ? "ber_sweep_task5_fading" : "ber_sweep_task5"), pl ? &s : nullptr);
   c.out = true;                                                  // (the study's own outputs are checked last)
-  c.f64_flag = is_f64(flags);
   c.mp_desync = mp_desync;
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
   ErrStudyArgs a;
-  a.receiver = receiver; a.side = side; a.both_channels = fading && h && h_len != 0;
+  a.receiver = receiver; a.side = side; a.both_channels = g.both_channels();
   a.time_desync = time_desync; a.freq_desync = freq_desync; a.mp_desync = mp_desync;
   ErrTablesWanted want;
   want.gap_bins = gap_bins;
@@ -323,31 +318,23 @@ extern "C" int ofdm_error_study(ofdm_rx_plan* pl, int receiver, const void* h, i
     OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &difo));
     OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &dstat));
   }
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);          // receiver 4: the draws of the chunk's frames, as the sweep's
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
+  const TxfImp imp = g.imp();                                    // receiver 4: the draws of the chunk's frames, as the sweep's
+  TxfPoints pt = g.points(true);
+  pt.scref = (uint32_t*)scref;
   const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
-  const DescrMask mask(pl, channel_side);                        // behind every check that reads the plan's DeScrambler
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const double inv_snr = 1.0 / std::pow(10.0, snr_db[p] * 0.1);           // (as ofdm_ber_sweep_task5 passes it: h = ifft(H_LS) mode)
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, b.ref, (uint32_t*)scref,
-                            receiver == 4 ? &imp : nullptr, fading ? &fade : nullptr));
-      if (receiver == 4)
-        OFDM_TRY(rx_chain_task4_run(pl, b.rx, nf, time_desync, freq_desync, mp_desync, (uint8_t*)dec, nullptr, nullptr, (int64_t*)dtg,
-                                    (double*)dfo, (int32_t*)difo, (int32_t*)dstat, nullptr, 0, nullptr, nullptr, rxflags));
-      else
-        OFDM_TRY(rx_chain_task5_run(pl, b.rx, nf, (uint8_t*)dec, nullptr, nullptr, nullptr, nullptr, nullptr, rxflags, inv_snr));
-      OFDM_TRY(err_profile_frames(s, gap_bins, (const uint32_t*)dec, channel_side ? (const uint32_t*)scref : b.ref, nf,
-                                  o.point((size_t)p, (size_t)c0)));
+  // behind every check that reads the plan's DeScrambler (the workspace the loop sets up in front of its first chunk reads none)
+  const DescrMask mask(pl, channel_side);
+  OFDM_TRY(txf_sweep_points(pl, ch, pt, scr_reg15, CH, receiver == 4 ? &imp : nullptr, fading ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
+    if (receiver == 4) {
+      OFDM_TRY(rx_chain_task4_run(pl, b.rx, nf, time_desync, freq_desync, mp_desync, (uint8_t*)dec, nullptr, nullptr, (int64_t*)dtg,
+                                  (double*)dfo, (int32_t*)difo, (int32_t*)dstat, nullptr, 0, nullptr, nullptr, rxflags));
+    } else {
+      const double inv_snr = 1.0 / std::pow(10.0, snr_db[p] * 0.1);         // (as ofdm_ber_sweep_task5 passes it: h = ifft(H_LS) mode)
+      OFDM_TRY(rx_chain_task5_run(pl, b.rx, nf, (uint8_t*)dec, nullptr, nullptr, nullptr, nullptr, nullptr, rxflags, inv_snr));
     }
-  }
+    return err_profile_frames(s, gap_bins, (const uint32_t*)dec, channel_side ? (const uint32_t*)scref : b.ref, nf,
+                              o.point((size_t)p, (size_t)at));
+  }));
   return st.finish();
 }

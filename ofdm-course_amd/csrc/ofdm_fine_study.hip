@@ -14,7 +14,7 @@
 //                             the chunk's timing errors and common phases in frame order to {sum |e|, sum e^2}, {sum ph, sum ph^2}.
 //                             The chunks of a point run in stream order on accumulators the call zeroed, so every double is
 //                             ((0 + v_0) + v_1) + .. whatever the chunking.
-// ofdm_fine_study generates each chunk with the fused generator (txf_generate, the RX frames in the plan-owned workspace), runs the
+// ofdm_fine_study generates each chunk with the fused generator (txf_sweep_points, the RX frames in the plan-owned workspace), runs the
 // front end of the Task-4 receiver on it (task4_front_end, ofdm_chain_t4.hip: the stages task4_run itself runs in front of
 // fine_sync, on the route of t4_route.hpp) and then the two kernels on the pilot rows the demodulator left; no equaliser, no
 // demapper.  Host side: the checks, the chunk and the launch shape are fine_plan.hpp's, plain C++ tested without a GPU.
@@ -23,7 +23,7 @@
 
 #include "fine_plan.hpp"
 #include "sync_core.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -215,13 +215,8 @@ extern "C" int ofdm_fine_study(ofdm_rx_plan* pl, const void* h, int h_len, const
                                int64_t* frame_time_delay_out, int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
-  TxfCall c("fine_study", frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
-  c.f64_flag = is_f64(flags);
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
+  const TxfStudyArgs a{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
   FineCapture cap;
   cap.variant = variant;
   cap.out = tau_curve_sums_out || curve_dropped_out || keep_counts_out || tau_hist_out || tau_below_out || tau_above_out || tau_nan_out ||
@@ -233,103 +228,79 @@ extern "C" int ofdm_fine_study(ofdm_rx_plan* pl, const void* h, int h_len, const
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(fine_study_prelude(c, fading && h && h_len != 0, td, fd, cap, bins, ch, fade.gains, why), why));
+  OFDM_TRY(txf_refused(fine_study_prelude(a.call("fine_study", pl ? &s : nullptr), a.both_channels(), td, fd, cap, bins, ch, fade.gains,
+                                          why), why));
   const int stride = pl->nfft + pl->t_guard;
   const int64_t L = fine_len(s.np, s.n_symb, variant);
-  const size_t np = (size_t)n_points, fpp = (size_t)frames_per_point;
-  const size_t row = sizeof(double) * (size_t)L, cnt = sizeof(uint64_t) * (size_t)L, one = sizeof(uint64_t);
+  const size_t np = (size_t)n_points, fpp = (size_t)frames_per_point, Ls = (size_t)L;
   Stage st(flags);
   hipStream_t stream = ctx().stream;
-  // the tables a caller did not ask for are still counted (scratch): one kernel, whatever the outputs
-  auto table = [&st](void* user, size_t bytes, void** d) { return user ? st.out(user, bytes, d) : st.scratch(bytes, d); };
-  void *dftau, *dfph, *dfnu, *dftg, *dfst, *dftd;
-  OFDM_TRY(st.out(frame_tau_out, sizeof(double) * np * fpp, &dftau));
-  OFDM_TRY(st.out(frame_phase_out, sizeof(double) * np * fpp, &dfph));
-  OFDM_TRY(st.out(frame_n_used_out, sizeof(int32_t) * np * fpp, &dfnu));
-  OFDM_TRY(st.out(frame_tg_out, sizeof(int64_t) * np * fpp, &dftg));
-  OFDM_TRY(st.out(frame_status_out, sizeof(int32_t) * np * fpp, &dfst));
-  OFDM_TRY(st.out(frame_time_delay_out, sizeof(int64_t) * np * fpp, &dftd));
+  TxfFrameOut<double> ftau, fph;
+  TxfFrameOut<int32_t> fnu, fst;
+  TxfFrameOut<int64_t> ftg, ftd;
+  OFDM_TRY(ftau.out(st, frame_tau_out, np * fpp));
+  OFDM_TRY(fph.out(st, frame_phase_out, np * fpp));
+  OFDM_TRY(fnu.out(st, frame_n_used_out, np * fpp));
+  OFDM_TRY(ftg.out(st, frame_tg_out, np * fpp));
+  OFDM_TRY(fst.out(st, frame_status_out, np * fpp));
+  OFDM_TRY(ftd.out(st, frame_time_delay_out, np * fpp));
   if (n_points == 0) return st.finish();
-  struct { void* user; size_t bytes; void* d; } tabs[] = {
-      {tau_curve_sums_out, row * np, nullptr}, {curve_dropped_out, cnt * np, nullptr}, {keep_counts_out, cnt * np, nullptr},
-      {tau_hist_out, one * (size_t)bins_n * np, nullptr}, {tau_below_out, one * np, nullptr}, {tau_above_out, one * np, nullptr},
-      {tau_nan_out, one * np, nullptr}, {tau_err_out, 2 * sizeof(double) * np, nullptr}, {phase_sums_out, 2 * sizeof(double) * np, nullptr},
-      {phase_nan_out, one * np, nullptr}, {used_sums_out, one * np, nullptr}, {tg_hist_out, one * (size_t)stride * np, nullptr}};
-  for (auto& t : tabs) {
-    OFDM_TRY(table(t.user, t.bytes, &t.d));
-    OFDM_HIP(hipMemsetAsync(t.d, 0, t.bytes, stream));                    // the accumulators: 0 + v_0 + v_1 + ..
-  }
-  double* const dsums = (double*)tabs[0].d;
-  unsigned long long* const ddrop = (unsigned long long*)tabs[1].d;
-  unsigned long long* const dkeepc = (unsigned long long*)tabs[2].d;
-  unsigned long long* const dhist = (unsigned long long*)tabs[3].d;
-  unsigned long long* const dbelow = (unsigned long long*)tabs[4].d;
-  unsigned long long* const dabove = (unsigned long long*)tabs[5].d;
-  unsigned long long* const dnan = (unsigned long long*)tabs[6].d;
-  double* const dterr = (double*)tabs[7].d;
-  double* const dpsum = (double*)tabs[8].d;
-  unsigned long long* const dpnan = (unsigned long long*)tabs[9].d;
-  unsigned long long* const dused = (unsigned long long*)tabs[10].d;
-  unsigned long long* const dtgh = (unsigned long long*)tabs[11].d;
+  double *dsums, *dterr, *dpsum;
+  unsigned long long *ddrop, *dkeepc, *dhist, *dbelow, *dabove, *dnan, *dpnan, *dused, *dtgh;
+  OFDM_TRY(txf_table(st, tau_curve_sums_out, Ls * np, dsums));
+  OFDM_TRY(txf_table(st, curve_dropped_out, Ls * np, ddrop));
+  OFDM_TRY(txf_table(st, keep_counts_out, Ls * np, dkeepc));
+  OFDM_TRY(txf_table(st, tau_hist_out, (size_t)bins_n * np, dhist));
+  OFDM_TRY(txf_table(st, tau_below_out, np, dbelow));
+  OFDM_TRY(txf_table(st, tau_above_out, np, dabove));
+  OFDM_TRY(txf_table(st, tau_nan_out, np, dnan));
+  OFDM_TRY(txf_table(st, tau_err_out, 2 * np, dterr));
+  OFDM_TRY(txf_table(st, phase_sums_out, 2 * np, dpsum));
+  OFDM_TRY(txf_table(st, phase_nan_out, np, dpnan));
+  OFDM_TRY(txf_table(st, used_sums_out, np, dused));
+  OFDM_TRY(txf_table(st, tg_hist_out, (size_t)stride * np, dtgh));
   if (frames_per_point == 0) return st.finish();
-  const bool imp_on = sto_mode != 0 || cfo_mode != 0;                     // both off: the plain channel pass, the same frames
-  const TxfUse u = sync_use(scr_reg15 != nullptr, imp_on, fading ? (int)ch.delay.size() : 0);
+  const bool imp_on = a.imp_on();
+  const TxfUse u = a.use(ch);
   const int64_t CH = fine_chunk(s, u, frames_per_point, max_frames_per_chunk, variant);
   const size_t chn = (size_t)CH;
-  void *rows, *keepm, *err, *ctau = nullptr, *cph = nullptr, *cnu = nullptr, *cnp, *ctg = nullptr, *cst = nullptr, *cfo, *cifo;
-  OFDM_TRY(st.scratch(row * chn, &rows));
-  OFDM_TRY(st.scratch((size_t)L * chn, &keepm));
+  void *rows, *keepm, *err, *cnp, *cfo, *cifo;
+  OFDM_TRY(st.scratch(sizeof(double) * Ls * chn, &rows));
+  OFDM_TRY(st.scratch(Ls * chn, &keepm));
   OFDM_TRY(st.scratch(sizeof(double) * chn, &err));
   OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cnp));
   OFDM_TRY(st.scratch(sizeof(double) * chn, &cfo));
   OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cifo));
-  if (!dftau) OFDM_TRY(st.scratch(sizeof(double) * chn, &ctau));
-  if (!dfph) OFDM_TRY(st.scratch(sizeof(double) * chn, &cph));
-  if (!dfnu) OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cnu));
-  if (!dftg) OFDM_TRY(st.scratch(sizeof(int64_t) * chn, &ctg));
-  if (!dfst) OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cst));
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, nullptr, nullptr,
-                            imp_on ? &imp : nullptr, fading ? &fade : nullptr));
-      const size_t at = (size_t)(p * frames_per_point + c0);
-      int64_t* const tg = dftg ? (int64_t*)dftg + at : (int64_t*)ctg;
-      int32_t* const stt = dfst ? (int32_t*)dfst + at : (int32_t*)cst;
-      T4PilotRows v{};
-      OFDM_TRY(task4_front_end(pl, b.rx, nf, td, fd, tg, (double*)cfo, (int32_t*)cifo, stt, &v));
-      if (dftd) {
-        if (imp_on) OFDM_HIP(hipMemcpyAsync((int64_t*)dftd + at, b.sto, sizeof(int64_t) * (size_t)nf, hipMemcpyDeviceToDevice, stream));
-        else OFDM_HIP(hipMemsetAsync((int64_t*)dftd + at, 0, sizeof(int64_t) * (size_t)nf, stream));
-      }
-      FineOut o{};
-      o.taus = (double*)rows; o.keep = (uint8_t*)keepm;
-      o.tau = dftau ? (double*)dftau + at : (double*)ctau;
-      o.phase = dfph ? (double*)dfph + at : (double*)cph;
-      o.n_used = dfnu ? (int32_t*)dfnu + at : (int32_t*)cnu;
-      o.n_phase = (int32_t*)cnp;
-      o.tg = tg; o.sto = imp_on ? b.sto : nullptr;
-      o.tau_hist = dhist + (size_t)bins_n * p; o.tau_below = dbelow + p; o.tau_above = dabove + p; o.tau_nan = dnan + p;
-      o.phase_nan = dpnan + p; o.used_sum = dused + p; o.tg_hist = dtgh + (size_t)stride * p;
-      o.err = (double*)err;
-      o.bins_n = bins_n; o.bins_lo = bins_lo; o.bins_hi = bins_hi;
-      o.nfft = pl->nfft; o.stride = stride;
-      OFDM_TRY(fine_capture_any(pl, s, v, nf, variant, td, o));
-      const FinePass fp = fine_pass(s, variant, nf);
-      hipLaunchKernelGGL(fine_accumulate_kernel, dim3(fp.acc_grid), dim3(fp.acc_threads), 0, stream, (const double*)rows,
-                         (const uint8_t*)keepm, (const double*)err, (const double*)o.phase, nf, L, dsums + (size_t)L * p,
-                         ddrop + (size_t)L * p, dkeepc + (size_t)L * p, dterr + 2 * p, dpsum + 2 * p);
-      OFDM_TRY(check_launch("fine_accumulate_kernel"));
+  OFDM_TRY(ftau.scratch(st, chn));
+  OFDM_TRY(fph.scratch(st, chn));
+  OFDM_TRY(fnu.scratch(st, chn));
+  OFDM_TRY(ftg.scratch(st, chn));
+  OFDM_TRY(fst.scratch(st, chn));
+  const TxfImp imp = a.imp();
+  OFDM_TRY(txf_sweep_points(pl, ch, a.points(), scr_reg15, CH, imp_on ? &imp : nullptr, a.fading() ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
+    T4PilotRows v{};
+    OFDM_TRY(task4_front_end(pl, b.rx, nf, td, fd, ftg.at(at), (double*)cfo, (int32_t*)cifo, fst.at(at), &v));
+    if (ftd.sweep) {                                                      // (no scratch: written only where the caller wants it)
+      if (imp_on) OFDM_HIP(hipMemcpyAsync(ftd.at(at), b.sto, sizeof(int64_t) * (size_t)nf, hipMemcpyDeviceToDevice, stream));
+      else OFDM_HIP(hipMemsetAsync(ftd.at(at), 0, sizeof(int64_t) * (size_t)nf, stream));
     }
-  }
+    FineOut o{};
+    o.taus = (double*)rows; o.keep = (uint8_t*)keepm;
+    o.tau = ftau.at(at); o.phase = fph.at(at); o.n_used = fnu.at(at);
+    o.n_phase = (int32_t*)cnp;
+    o.tg = ftg.at(at); o.sto = imp_on ? b.sto : nullptr;
+    o.tau_hist = dhist + (size_t)bins_n * p; o.tau_below = dbelow + p; o.tau_above = dabove + p; o.tau_nan = dnan + p;
+    o.phase_nan = dpnan + p; o.used_sum = dused + p; o.tg_hist = dtgh + (size_t)stride * p;
+    o.err = (double*)err;
+    o.bins_n = bins_n; o.bins_lo = bins_lo; o.bins_hi = bins_hi;
+    o.nfft = pl->nfft; o.stride = stride;
+    OFDM_TRY(fine_capture_any(pl, s, v, nf, variant, td, o));
+    const FinePass fp = fine_pass(s, variant, nf);
+    hipLaunchKernelGGL(fine_accumulate_kernel, dim3(fp.acc_grid), dim3(fp.acc_threads), 0, stream, (const double*)rows,
+                       (const uint8_t*)keepm, (const double*)err, (const double*)o.phase, nf, L, dsums + Ls * p, ddrop + Ls * p,
+                       dkeepc + Ls * p, dterr + 2 * p, dpsum + 2 * p);
+    return check_launch("fine_accumulate_kernel");
+  }));
   return st.finish();
 }

@@ -20,7 +20,7 @@
 //   hest_thresholds_kernel    the host's table of linear thresholds into device memory (kernel arguments, no host wait).
 //   hest_frame_hist_kernel    after the last chunk: every frame's error sum binned on the table of linear thresholds (hest_bin,
 //                             hest_plan.hpp) and its status counted (atomics on integers).
-// ofdm_hest_study generates each chunk with the fused generator (txf_generate), runs the receiver up to and including
+// ofdm_hest_study generates each chunk with the fused generator (txf_sweep_points), runs the receiver up to and including
 // estimate_channel on it (task4_estimate, ofdm_chain_t4.hip), the sweeps' own error kernel on the arena's H (txf_frame_nmse) and
 // the kernels above; no equaliser, no demapper.  Host side: the checks, the chunk and the launch shape are hest_plan.hpp's.
 #include <algorithm>
@@ -28,7 +28,7 @@
 #include <vector>
 
 #include "hest_plan.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -297,13 +297,9 @@ extern "C" int ofdm_hest_study(ofdm_rx_plan* pl, const void* h, int h_len, const
                                uint64_t* status_counts_out, double* thresholds_out, int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
-  TxfCall c("hest_study", frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
-  c.f64_flag = is_f64(flags);
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
+  const TxfStudyArgs a{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
+  const bool fading = a.fading();
   HestCapture cap;
   cap.time_desync = time_desync;
   cap.freq_desync = freq_desync;
@@ -315,43 +311,41 @@ extern "C" int ofdm_hest_study(ofdm_rx_plan* pl, const void* h, int h_len, const
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(hest_study_prelude(c, fading && h && h_len != 0, cap, ch, fade.gains, why), why));
+  OFDM_TRY(txf_refused(hest_study_prelude(a.call("hest_study", pl ? &s : nullptr), a.both_channels(), cap, ch, fade.gains, why), why));
   const size_t nc = (size_t)pl->n_carrier, npil = (size_t)pl->np, np = (size_t)n_points, fpp = (size_t)frames_per_point;
-  const size_t nb = (size_t)hist_bins, NF = np * fpp, one = sizeof(uint64_t);
+  const size_t nb = (size_t)hist_bins, NF = np * fpp;
   // the table of linear thresholds: made once, on the host; host memory whatever the flags
   std::vector<double> thr(nb + 1);
   hest_thresholds(cap.bins, pl->n_carrier, thr.data());
   if (thresholds_out) std::copy(thr.begin(), thr.end(), thresholds_out);
   Stage st(flags);
   hipStream_t stream = ctx().stream;
-  // the tables a caller did not ask for are still summed (scratch): the same kernels, whatever the outputs
-  auto table = [&st](void* user, size_t bytes, void** d) { return user ? st.out(user, bytes, d) : st.scratch(bytes, d); };
   void *dfn, *dfa;
   OFDM_TRY(st.out(frame_nmse_out, sizeof(double) * NF, &dfn));
   OFDM_TRY(st.out(frame_amp_nmse_out, sizeof(double) * NF, &dfa));
   if (n_points == 0) return st.finish();
-  struct { void* user; size_t bytes; void* d; } tabs[] = {
-      {est_amp_sums_out, sizeof(double) * nc * np, nullptr}, {true_amp_sums_out, sizeof(double) * nc * np, nullptr},
-      {err_sums_out, sizeof(double) * nc * np, nullptr}, {amp_err_sums_out, sizeof(double) * nc * np, nullptr},
-      {dropped_out, one * nc * np, nullptr}, {pilot_amp_sums_out, sizeof(double) * npil * np, nullptr},
-      {pilot_err_sums_out, sizeof(double) * npil * np, nullptr}, {pilot_dropped_out, one * npil * np, nullptr},
-      {nmse_sums_out, sizeof(double) * np, nullptr}, {amp_nmse_sums_out, sizeof(double) * np, nullptr},
-      {nmse_hist_out, one * nb * np, nullptr}, {nmse_below_out, one * np, nullptr}, {nmse_above_out, one * np, nullptr},
-      {nmse_nan_out, one * np, nullptr}, {status_counts_out, one * 4 * np, nullptr}};
-  for (auto& t : tabs) {
-    OFDM_TRY(table(t.user, t.bytes, &t.d));
-    OFDM_HIP(hipMemsetAsync(t.d, 0, t.bytes, stream));                    // the accumulators: 0 + v_0 + v_1 + ..
-  }
-  double* const dsum[4] = {(double*)tabs[0].d, (double*)tabs[1].d, (double*)tabs[2].d, (double*)tabs[3].d};
-  unsigned long long* const ddrop = (unsigned long long*)tabs[4].d;
-  double* const dpsum[2] = {(double*)tabs[5].d, (double*)tabs[6].d};
-  unsigned long long* const dpdrop = (unsigned long long*)tabs[7].d;
+  double *dsum[4], *dpsum[2], *dns, *dans;
+  unsigned long long *ddrop, *dpdrop, *dhist, *dbelow, *dabove, *dnan, *dstc;
+  OFDM_TRY(txf_table(st, est_amp_sums_out, nc * np, dsum[0]));
+  OFDM_TRY(txf_table(st, true_amp_sums_out, nc * np, dsum[1]));
+  OFDM_TRY(txf_table(st, err_sums_out, nc * np, dsum[2]));
+  OFDM_TRY(txf_table(st, amp_err_sums_out, nc * np, dsum[3]));
+  OFDM_TRY(txf_table(st, dropped_out, nc * np, ddrop));
+  OFDM_TRY(txf_table(st, pilot_amp_sums_out, npil * np, dpsum[0]));
+  OFDM_TRY(txf_table(st, pilot_err_sums_out, npil * np, dpsum[1]));
+  OFDM_TRY(txf_table(st, pilot_dropped_out, npil * np, dpdrop));
+  OFDM_TRY(txf_table(st, nmse_sums_out, np, dns));
+  OFDM_TRY(txf_table(st, amp_nmse_sums_out, np, dans));
+  OFDM_TRY(txf_table(st, nmse_hist_out, nb * np, dhist));
+  OFDM_TRY(txf_table(st, nmse_below_out, np, dbelow));
+  OFDM_TRY(txf_table(st, nmse_above_out, np, dabove));
+  OFDM_TRY(txf_table(st, nmse_nan_out, np, dnan));
+  OFDM_TRY(txf_table(st, status_counts_out, 4 * np, dstc));
   if (frames_per_point == 0) return st.finish();
   if (!dfn) OFDM_TRY(st.scratch(sizeof(double) * NF, &dfn));
   if (!dfa) OFDM_TRY(st.scratch(sizeof(double) * NF, &dfa));
-  const bool imp_on = sto_mode != 0 || cfo_mode != 0;                     // both off: the plain channel pass, the same frames
   const int taps = (int)ch.delay.size();
-  const TxfUse u = sync_use(scr_reg15 != nullptr, imp_on, fading ? taps : 0);
+  const TxfUse u = a.use(ch);
   const int64_t CH = hest_chunk(s, u, frames_per_point, max_frames_per_chunk);
   const size_t chn = (size_t)CH;
   void *car, *cmask, *pil, *pmask, *ctg, *cfo, *cifo, *dstat, *dthr, *dstatic = nullptr, *dtab = nullptr;
@@ -380,51 +374,37 @@ extern "C" int ofdm_hest_study(ofdm_rx_plan* pl, const void* h, int h_len, const
                        pl->nfft, pl->n_carrier, (c64*)dtab);
     OFDM_TRY(check_launch("hest_static_table_kernel"));
   }
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
   const HestPass hp = hest_pass(s, CH);
   const HestRows rows{(double*)car, (uint8_t*)cmask, (double*)pil, (uint8_t*)pmask};
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
+  const TxfImp imp = a.imp();
+  OFDM_TRY(txf_sweep_points(pl, ch, a.points(), scr_reg15, CH, a.imp_on() ? &imp : nullptr, fading ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
     HestSums cs{}, ps{};
     for (int q = 0; q < 4; ++q) cs.sums[q] = dsum[q] + nc * (size_t)p;
     cs.dropped = ddrop + nc * (size_t)p;
     for (int q = 0; q < 2; ++q) ps.sums[q] = dpsum[q] + npil * (size_t)p;
     ps.dropped = dpdrop + npil * (size_t)p;
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, nullptr, nullptr,
-                            imp_on ? &imp : nullptr, fading ? &fade : nullptr));
-      const size_t at = (size_t)(p * frames_per_point + c0);
-      T4Estimate e{};
-      OFDM_TRY(task4_estimate(pl, b.rx, nf, time_desync, freq_desync, (int64_t*)ctg, (double*)cfo, (int32_t*)cifo,
-                              (int32_t*)dstat + at, &e));
-      const c64* const amp = fading ? (const c64*)b.amp : (const c64*)dstatic;
-      const int64_t stride = fading ? taps : 0;
-      // the sweeps' own error sum on the estimate the equaliser would read
-      OFDM_TRY(txf_frame_nmse(pl, amp, e.H, dl, stride, nf, (double*)dfn + at));
-      OFDM_TRY(hest_capture_frames(pl, hp, e, amp, stride, dl, (const c64*)dtab, nf, rows));
-      hipLaunchKernelGGL(hest_frame_sum_kernel, dim3((unsigned)nf), dim3(256), 0, stream, (const double*)car, pl->n_carrier,
-                         (double*)dfa + at);
-      hipLaunchKernelGGL(hest_accumulate_kernel, dim3(hp.acc_grid, (unsigned)HEST_CARRIER_ROWS), dim3(hp.acc_threads), 0, stream,
-                         (const double*)car, (const uint8_t*)cmask, nf, (int)HEST_CARRIER_ROWS, pl->n_carrier, cs);
-      hipLaunchKernelGGL(hest_accumulate_kernel, dim3(hp.acc_grid_pilots, (unsigned)HEST_PILOT_ROWS), dim3(hp.acc_threads), 0, stream,
-                         (const double*)pil, (const uint8_t*)pmask, nf, (int)HEST_PILOT_ROWS, pl->np, ps);
-      OFDM_TRY(check_launch("hest_accumulate_kernel"));
-    }
-  }
-  OFDM_TRY(txf_point_sums1(dfn, n_points, frames_per_point, tabs[8].d));
-  OFDM_TRY(txf_point_sums1(dfa, n_points, frames_per_point, tabs[9].d));
+    T4Estimate e{};
+    OFDM_TRY(task4_estimate(pl, b.rx, nf, time_desync, freq_desync, (int64_t*)ctg, (double*)cfo, (int32_t*)cifo,
+                            (int32_t*)dstat + at, &e));
+    const c64* const amp = fading ? (const c64*)b.amp : (const c64*)dstatic;
+    const int64_t stride = fading ? taps : 0;
+    // the sweeps' own error sum on the estimate the equaliser would read
+    OFDM_TRY(txf_frame_nmse(pl, amp, e.H, dl, stride, nf, (double*)dfn + at));
+    OFDM_TRY(hest_capture_frames(pl, hp, e, amp, stride, dl, (const c64*)dtab, nf, rows));
+    hipLaunchKernelGGL(hest_frame_sum_kernel, dim3((unsigned)nf), dim3(256), 0, stream, (const double*)car, pl->n_carrier,
+                       (double*)dfa + at);
+    hipLaunchKernelGGL(hest_accumulate_kernel, dim3(hp.acc_grid, (unsigned)HEST_CARRIER_ROWS), dim3(hp.acc_threads), 0, stream,
+                       (const double*)car, (const uint8_t*)cmask, nf, (int)HEST_CARRIER_ROWS, pl->n_carrier, cs);
+    hipLaunchKernelGGL(hest_accumulate_kernel, dim3(hp.acc_grid_pilots, (unsigned)HEST_PILOT_ROWS), dim3(hp.acc_threads), 0, stream,
+                       (const double*)pil, (const uint8_t*)pmask, nf, (int)HEST_PILOT_ROWS, pl->np, ps);
+    return check_launch("hest_accumulate_kernel");
+  }));
+  OFDM_TRY(txf_point_sums1(dfn, n_points, frames_per_point, dns));
+  OFDM_TRY(txf_point_sums1(dfa, n_points, frames_per_point, dans));
   hipLaunchKernelGGL(hest_frame_hist_kernel, dim3(cdiv_u((int64_t)NF, 256)), dim3(256), 0, stream, (const double*)dfn,
-                     (const int32_t*)dstat, frames_per_point, (int64_t)NF, (const double*)dthr, hist_bins,
-                     (unsigned long long*)tabs[10].d, (unsigned long long*)tabs[11].d, (unsigned long long*)tabs[12].d,
-                     (unsigned long long*)tabs[13].d, (unsigned long long*)tabs[14].d);
+                     (const int32_t*)dstat, frames_per_point, (int64_t)NF, (const double*)dthr, hist_bins, dhist, dbelow, dabove, dnan,
+                     dstc);
   OFDM_TRY(check_launch("hest_frame_hist_kernel"));
   return st.finish();
 }

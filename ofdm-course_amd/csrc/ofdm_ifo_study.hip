@@ -20,7 +20,7 @@
 //                             dropped[k] instead, and counts the frames whose bin k was above.  Its last workgroup adds the
 //                             chunk's total errors in frame order to {sum |e|, sum e^2}.  The chunks of a point run in stream order
 //                             on accumulators the call zeroed, so every double is ((0 + v_0) + v_1) + .. whatever the chunking.
-// ofdm_ifo_study generates each chunk with the fused generator (txf_generate, the RX frames in the plan-owned workspace), runs the
+// ofdm_ifo_study generates each chunk with the fused generator (txf_sweep_points, the RX frames in the plan-owned workspace), runs the
 // receiver's AutoCorrFunction stage on it (task4_acf_stage, ofdm_chain_t4.hip) and then the two kernels; no demodulator, no
 // equaliser.  Host side: the checks, the chunk and the launch shape are ifo_plan.hpp's, plain C++ tested without a GPU.
 #include <algorithm>
@@ -29,7 +29,7 @@
 #include "fft_core.hpp"
 #include "ifo_plan.hpp"
 #include "t4_stream.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -297,13 +297,8 @@ extern "C" int ofdm_ifo_study(ofdm_rx_plan* pl, const void* h, int h_len, const 
                               double* frame_fo_out, int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
-  TxfCall c("ifo_study", frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
-  c.f64_flag = is_f64(flags);
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
+  const TxfStudyArgs a{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
   IfoCapture cap;
   cap.stage = stage;
   cap.time_desync = time_desync;
@@ -315,90 +310,67 @@ extern "C" int ofdm_ifo_study(ofdm_rx_plan* pl, const void* h, int h_len, const 
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(ifo_study_prelude(c, fading && h && h_len != 0, cap, ch, fade.gains, why), why));
+  OFDM_TRY(txf_refused(ifo_study_prelude(a.call("ifo_study", pl ? &s : nullptr), a.both_channels(), cap, ch, fade.gains, why), why));
   const size_t N = (size_t)pl->nfft, np = (size_t)n_points, fpp = (size_t)frames_per_point, nerr = 2 * (size_t)err_span + 1;
-  const size_t row = sizeof(double) * N, cnt = sizeof(uint64_t) * N, one = sizeof(uint64_t);
   Stage st(flags);
   hipStream_t stream = ctx().stream;
-  // the tables a caller did not ask for are still counted (scratch): one kernel, whatever the outputs
-  auto table = [&st](void* user, size_t bytes, void** d) { return user ? st.out(user, bytes, d) : st.scratch(bytes, d); };
-  void *dfifo, *dfst, *dfna, *dftg, *dffo;
-  OFDM_TRY(st.out(frame_ifo_out, sizeof(int32_t) * np * fpp, &dfifo));
-  OFDM_TRY(st.out(frame_status_out, sizeof(int32_t) * np * fpp, &dfst));
-  OFDM_TRY(st.out(frame_n_above_out, sizeof(int32_t) * np * fpp, &dfna));
-  OFDM_TRY(st.out(frame_tg_out, sizeof(int64_t) * np * fpp, &dftg));
-  OFDM_TRY(st.out(frame_fo_out, sizeof(double) * np * fpp, &dffo));
+  TxfFrameOut<int32_t> fifo, fst, fna;
+  TxfFrameOut<int64_t> ftg;
+  TxfFrameOut<double> ffo;
+  OFDM_TRY(fifo.out(st, frame_ifo_out, np * fpp));
+  OFDM_TRY(fst.out(st, frame_status_out, np * fpp));
+  OFDM_TRY(fna.out(st, frame_n_above_out, np * fpp));
+  OFDM_TRY(ftg.out(st, frame_tg_out, np * fpp));
+  OFDM_TRY(ffo.out(st, frame_fo_out, np * fpp));
   if (n_points == 0) return st.finish();
-  struct { void* user; size_t bytes; void* d; } tabs[] = {
-      {spec_sums_out, row * np, nullptr}, {spec_dropped_out, cnt * np, nullptr}, {above_counts_out, cnt * np, nullptr},
-      {ifo_hist_out, cnt * np, nullptr}, {no_line_out, one * np, nullptr}, {err_hist_out, one * nerr * np, nullptr},
-      {err_below_out, one * np, nullptr}, {err_above_out, one * np, nullptr}, {hit_out, one * np, nullptr},
-      {cfo_err_out, 2 * sizeof(double) * np, nullptr}, {fallback_out, one * np, nullptr}};
-  for (auto& t : tabs) {
-    OFDM_TRY(table(t.user, t.bytes, &t.d));
-    OFDM_HIP(hipMemsetAsync(t.d, 0, t.bytes, stream));                    // the accumulators: 0 + v_0 + v_1 + ..
-  }
-  double* const dsums = (double*)tabs[0].d;
-  unsigned long long* const ddrop = (unsigned long long*)tabs[1].d;
-  unsigned long long* const dabove = (unsigned long long*)tabs[2].d;
-  unsigned long long* const dhist = (unsigned long long*)tabs[3].d;
-  unsigned long long* const dnone = (unsigned long long*)tabs[4].d;
-  unsigned long long* const dehist = (unsigned long long*)tabs[5].d;
-  unsigned long long* const debelow = (unsigned long long*)tabs[6].d;
-  unsigned long long* const deabove = (unsigned long long*)tabs[7].d;
-  unsigned long long* const dhit = (unsigned long long*)tabs[8].d;
-  double* const dcerr = (double*)tabs[9].d;
-  unsigned long long* const dfall = (unsigned long long*)tabs[10].d;
+  double *dsums, *dcerr;
+  unsigned long long *ddrop, *dabove, *dhist, *dnone, *dehist, *debelow, *deabove, *dhit, *dfall;
+  OFDM_TRY(txf_table(st, spec_sums_out, N * np, dsums));
+  OFDM_TRY(txf_table(st, spec_dropped_out, N * np, ddrop));
+  OFDM_TRY(txf_table(st, above_counts_out, N * np, dabove));
+  OFDM_TRY(txf_table(st, ifo_hist_out, N * np, dhist));
+  OFDM_TRY(txf_table(st, no_line_out, np, dnone));
+  OFDM_TRY(txf_table(st, err_hist_out, nerr * np, dehist));
+  OFDM_TRY(txf_table(st, err_below_out, np, debelow));
+  OFDM_TRY(txf_table(st, err_above_out, np, deabove));
+  OFDM_TRY(txf_table(st, hit_out, np, dhit));
+  OFDM_TRY(txf_table(st, cfo_err_out, 2 * np, dcerr));
+  OFDM_TRY(txf_table(st, fallback_out, np, dfall));
   if (frames_per_point == 0) return st.finish();
-  const bool imp_on = sto_mode != 0 || cfo_mode != 0;                     // both off: the plain channel pass, the same frames
-  const TxfUse u = sync_use(scr_reg15 != nullptr, imp_on, fading ? (int)ch.delay.size() : 0);
+  const bool imp_on = a.imp_on();
+  const TxfUse u = a.use(ch);
   const int64_t CH = ifo_chunk(s, u, frames_per_point, max_frames_per_chunk);
   const size_t chn = (size_t)CH;
-  void *rows, *mask, *err, *cifo = nullptr, *cst = nullptr, *cna = nullptr, *ctg = nullptr, *cfo = nullptr;
-  OFDM_TRY(st.scratch(row * chn, &rows));
+  void *rows, *mask, *err;
+  OFDM_TRY(st.scratch(sizeof(double) * N * chn, &rows));
   OFDM_TRY(st.scratch(N * chn, &mask));
   OFDM_TRY(st.scratch(sizeof(double) * chn, &err));
-  if (!dfifo) OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cifo));
-  if (!dfst) OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cst));
-  if (!dfna) OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cna));
-  if (!dftg) OFDM_TRY(st.scratch(sizeof(int64_t) * chn, &ctg));
-  if (!dffo) OFDM_TRY(st.scratch(sizeof(double) * chn, &cfo));
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
+  OFDM_TRY(fifo.scratch(st, chn));
+  OFDM_TRY(fst.scratch(st, chn));
+  OFDM_TRY(fna.scratch(st, chn));
+  OFDM_TRY(ftg.scratch(st, chn));
+  OFDM_TRY(ffo.scratch(st, chn));
   const IfoPass ip = ifo_pass(s, CH);
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, nullptr, nullptr,
-                            imp_on ? &imp : nullptr, fading ? &fade : nullptr));
-      const size_t at = (size_t)(p * frames_per_point + c0);
-      IfoOut o{};
-      o.rows = (double*)rows; o.mask = (uint8_t*)mask;
-      o.ifo = dfifo ? (int32_t*)dfifo + at : (int32_t*)cifo;
-      o.status = dfst ? (int32_t*)dfst + at : (int32_t*)cst;
-      o.n_above = dfna ? (int32_t*)dfna + at : (int32_t*)cna;
-      int64_t* const tg = dftg ? (int64_t*)dftg + at : (int64_t*)ctg;
-      double* const fo = dffo ? (double*)dffo + at : (double*)cfo;
-      o.tg = tg; o.fo = fo;
-      o.cfo = imp_on ? b.cfo : nullptr;
-      o.ifo_hist = dhist + N * p; o.no_line = dnone + p; o.err_hist = dehist + nerr * p; o.err_below = debelow + p;
-      o.err_above = deabove + p; o.hit = dhit + p; o.fallback = dfall + p;
-      o.err = (double*)err;
-      o.span = err_span;
-      OFDM_TRY(task4_acf_stage(pl, b.rx, nf, time_desync, tg, fo, o.ifo, o.status));
-      OFDM_TRY(ifo_capture_frames(pl, s, b.rx, nf, stage, time_desync, o));
-      hipLaunchKernelGGL(ifo_accumulate_kernel, dim3(ip.acc_grid), dim3(ip.acc_threads), 0, stream, (const double*)rows,
-                         (const uint8_t*)mask, (const double*)err, nf, pl->nfft, dsums + N * p, ddrop + N * p, dabove + N * p,
-                         dcerr + 2 * p);
-      OFDM_TRY(check_launch("ifo_accumulate_kernel"));
-    }
-  }
+  const TxfImp imp = a.imp();
+  OFDM_TRY(txf_sweep_points(pl, ch, a.points(), scr_reg15, CH, imp_on ? &imp : nullptr, a.fading() ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
+    IfoOut o{};
+    o.rows = (double*)rows; o.mask = (uint8_t*)mask;
+    o.ifo = fifo.at(at); o.status = fst.at(at); o.n_above = fna.at(at);
+    int64_t* const tg = ftg.at(at);
+    double* const fo = ffo.at(at);
+    o.tg = tg; o.fo = fo;
+    o.cfo = imp_on ? b.cfo : nullptr;
+    o.ifo_hist = dhist + N * p; o.no_line = dnone + p; o.err_hist = dehist + nerr * p; o.err_below = debelow + p;
+    o.err_above = deabove + p; o.hit = dhit + p; o.fallback = dfall + p;
+    o.err = (double*)err;
+    o.span = err_span;
+    OFDM_TRY(task4_acf_stage(pl, b.rx, nf, time_desync, tg, fo, o.ifo, o.status));
+    OFDM_TRY(ifo_capture_frames(pl, s, b.rx, nf, stage, time_desync, o));
+    hipLaunchKernelGGL(ifo_accumulate_kernel, dim3(ip.acc_grid), dim3(ip.acc_threads), 0, stream, (const double*)rows,
+                       (const uint8_t*)mask, (const double*)err, nf, pl->nfft, dsums + N * p, ddrop + N * p, dabove + N * p,
+                       dcerr + 2 * p);
+    return check_launch("ifo_accumulate_kernel");
+  }));
   return st.finish();
 }

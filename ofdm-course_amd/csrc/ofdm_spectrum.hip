@@ -13,15 +13,15 @@
 //   spectrum_accumulate_kernel   one thread per bin adds: sums[k] = (..(sums[k] + P_0[k]) + P_1[k]) + .. over the chunk's rows in frame
 //                                order (the rows staged through LDS by the whole workgroup), peak[k] = fmax over them.  The chunks of a point run in stream order on the accumulators
 //                                the call zeroed, so the result is ((0 + P_0) + P_1) + .. whatever the chunking.
-// ofdm_spectrum_study generates each chunk with the fused generator (txf_generate, the RX frames in the plan-owned workspace), runs
-// the two kernels on it and never runs a receiver.  Host side: the checks, the chunk and the launch shape are
-// spectrum_plan.hpp's, plain C++ tested without a GPU.
+// ofdm_spectrum_study generates each chunk with the fused generator (the studies' scaffold, txf_study.hpp: the RX frames in the
+// plan-owned workspace), runs the two kernels on it and never runs a receiver.  Host side: the checks, the chunk and the launch
+// shape are spectrum_plan.hpp's, plain C++ tested without a GPU.
 #include <algorithm>
 #include <cmath>
 
 #include "fft_core.hpp"
 #include "spectrum_plan.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -174,59 +174,41 @@ extern "C" int ofdm_spectrum_study(ofdm_rx_plan* pl, const void* h, int h_len, c
                                    int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
-  TxfCall c("spectrum_study", frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
-  c.f64_flag = is_f64(flags);
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
+  const TxfStudyArgs a{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
   SpecCapture cap;
   cap.first = first; cap.n_windows = n_windows; cap.out = power_sums_out != nullptr;
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(spectrum_study_prelude(c, fading && h && h_len != 0, cap, ch, fade.gains, why), why));
-  const int nfft = pl->nfft;
-  const size_t row = sizeof(double) * (size_t)nfft;
+  OFDM_TRY(txf_refused(spectrum_study_prelude(a.call("spectrum_study", pl ? &s : nullptr), a.both_channels(), cap, ch, fade.gains, why), why));
+  const size_t nfft = (size_t)pl->nfft, row = sizeof(double) * nfft, np = (size_t)n_points;
   Stage st(flags);
   hipStream_t stream = ctx().stream;
-  void *dsums, *dpeak, *dfp;
-  OFDM_TRY(st.out(power_sums_out, row * (size_t)n_points, &dsums));
-  OFDM_TRY(st.out(power_peak_out, row * (size_t)n_points, &dpeak));
-  OFDM_TRY(st.out(frame_power_out, row * (size_t)n_points * (size_t)frames_per_point, &dfp));
+  void *dsums, *dpeak;
+  TxfFrameOut<double> fp;
+  OFDM_TRY(st.out(power_sums_out, row * np, &dsums));
+  OFDM_TRY(st.out(power_peak_out, row * np, &dpeak));
+  OFDM_TRY(fp.out(st, frame_power_out, nfft * np * (size_t)frames_per_point));
   if (n_points == 0) return st.finish();
-  OFDM_HIP(hipMemsetAsync(dsums, 0, row * (size_t)n_points, stream));     // the accumulators: 0 + P_0 + P_1 + ..
-  if (dpeak) OFDM_HIP(hipMemsetAsync(dpeak, 0, row * (size_t)n_points, stream));
+  OFDM_HIP(hipMemsetAsync(dsums, 0, row * np, stream));                   // the accumulators: 0 + P_0 + P_1 + ..
+  if (dpeak) OFDM_HIP(hipMemsetAsync(dpeak, 0, row * np, stream));
   if (frames_per_point == 0) return st.finish();
-  const bool imp_on = sto_mode != 0 || cfo_mode != 0;                     // both off: the plain channel pass, the same frames
-  const TxfUse u = spectrum_use(scr_reg15 != nullptr, imp_on, fading ? (int)ch.delay.size() : 0);
+  const TxfUse u = a.use(ch);
   const int64_t CH = spectrum_chunk(s, u, frames_per_point, max_frames_per_chunk, dpeak != nullptr);
-  void *rows = nullptr, *peak_rows = nullptr;
-  if (!dfp) OFDM_TRY(st.scratch(row * (size_t)CH, &rows));
+  void* peak_rows = nullptr;
+  OFDM_TRY(fp.scratch(st, nfft * (size_t)CH));
   if (dpeak) OFDM_TRY(st.scratch(row * (size_t)CH, &peak_rows));
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, nullptr, nullptr,
-                            imp_on ? &imp : nullptr, fading ? &fade : nullptr));
-      double* pr = dfp ? (double*)dfp + (size_t)nfft * (size_t)(p * frames_per_point + c0) : (double*)rows;
-      OFDM_TRY(spectrum_frames(pl, s, b.rx, nf, first, n_windows, nullptr, pr, (double*)peak_rows));
-      const SpecPass sp = spectrum_pass(s, nf);
-      hipLaunchKernelGGL(spectrum_accumulate_kernel, dim3(sp.acc_grid), dim3(sp.acc_threads), 0, stream, (const double*)pr,
-                         (const double*)peak_rows, nf, nfft, (double*)dsums + (size_t)nfft * p,
-                         dpeak ? (double*)dpeak + (size_t)nfft * p : nullptr);
-      OFDM_TRY(check_launch("spectrum_accumulate_kernel"));
-    }
-  }
+  const TxfImp imp = a.imp();
+  OFDM_TRY(txf_sweep_points(pl, ch, a.points(), scr_reg15, CH, a.imp_on() ? &imp : nullptr, a.fading() ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
+    double* const pr = fp.at(nfft * (size_t)at);
+    OFDM_TRY(spectrum_frames(pl, s, b.rx, nf, first, n_windows, nullptr, pr, (double*)peak_rows));
+    const SpecPass sp = spectrum_pass(s, nf);
+    hipLaunchKernelGGL(spectrum_accumulate_kernel, dim3(sp.acc_grid), dim3(sp.acc_threads), 0, stream, (const double*)pr,
+                       (const double*)peak_rows, nf, (int)nfft, (double*)dsums + nfft * (size_t)p,
+                       dpeak ? (double*)dpeak + nfft * (size_t)p : nullptr);
+    return check_launch("spectrum_accumulate_kernel");
+  }));
   return st.finish();
 }

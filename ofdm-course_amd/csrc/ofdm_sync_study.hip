@@ -18,7 +18,7 @@
 //                             dropped[n] instead; peak[n] = fmax over the rows.  Its last workgroup adds the chunk's wrapped errors
 //                             e in frame order to {sum |e|, sum e^2}.  The chunks of a point run in stream order on accumulators
 //                             the call zeroed, so every double is ((0 + v_0) + v_1) + .. whatever the chunking.
-// ofdm_sync_study generates each chunk with the fused generator (txf_generate, the RX frames in the plan-owned workspace), runs the
+// ofdm_sync_study generates each chunk with the fused generator (txf_sweep_points, the RX frames in the plan-owned workspace), runs the
 // two kernels on it and never runs a receiver; remove_IFO is out of scope (sync_plan.hpp).  Host side: the checks, the chunk and
 // the launch shape are sync_plan.hpp's, plain C++ tested without a GPU.
 #include <algorithm>
@@ -26,7 +26,7 @@
 
 #include "sync_core.hpp"
 #include "sync_plan.hpp"
-#include "txf_generate.hpp"
+#include "txf_study.hpp"
 
 namespace ofdm {
 
@@ -293,95 +293,70 @@ extern "C" int ofdm_sync_study(ofdm_rx_plan* pl, const void* h, int h_len, const
                                int32_t* frame_status_out, double* frame_fo_out, int flags) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const bool fading = tap_delay || tap_power || n_taps != 0;
-  TxfCall c("sync_study", frame0, frames_per_point, scr_reg15);
-  c.plan = pl ? &s : nullptr;
-  c.f64_flag = is_f64(flags);
-  c.with_points(snr_db, seeds, n_points, max_frames_per_chunk).with_imp(sto_mode, cfo_mode);
-  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
-  else c.with_h(h, h_len);
+  const TxfStudyArgs a{h, h_len, tap_delay, tap_power, n_taps, sto_mode, sto_value, cfo_mode, cfo_value, scr_reg15, snr_db, seeds,
+                       n_points, frames_per_point, frame0, max_frames_per_chunk, flags};
   SyncCapture cap;
   cap.width = width_window;
   cap.out = acf_sums_out != nullptr;
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(sync_study_prelude(c, fading && h && h_len != 0, cap, ch, fade.gains, why), why));
+  OFDM_TRY(txf_refused(sync_study_prelude(a.call("sync_study", pl ? &s : nullptr), a.both_channels(), cap, ch, fade.gains, why), why));
   const int W = (int)width_window, stride = pl->nfft + pl->t_guard;
   const int64_t n_out = sync_n_out(s, W);
-  const size_t np = (size_t)n_points, fpp = (size_t)frames_per_point;
-  const size_t row = sizeof(double) * (size_t)n_out, cnt = sizeof(uint64_t) * (size_t)n_out;
+  const size_t np = (size_t)n_points, fpp = (size_t)frames_per_point, no = (size_t)n_out, row = sizeof(double) * no;
   Stage st(flags);
   hipStream_t stream = ctx().stream;
-  // the tables a caller did not ask for are still counted (scratch): one kernel, whatever the outputs
-  auto table = [&st](void* user, size_t bytes, void** d) { return user ? st.out(user, bytes, d) : st.scratch(bytes, d); };
-  void *dsums, *ddrop, *dpeak, *dtgh, *dfall, *dph, *dffo, *dftg, *dfst, *dffo_f;
+  void *dsums, *dpeak;
+  TxfFrameOut<int64_t> ftg;
+  TxfFrameOut<int32_t> fst;
+  TxfFrameOut<double> ffo;
   OFDM_TRY(st.out(acf_sums_out, row * np, &dsums));
   OFDM_TRY(st.out(acf_peak_out, row * np, &dpeak));
-  OFDM_TRY(st.out(frame_tg_out, sizeof(int64_t) * np * fpp, &dftg));
-  OFDM_TRY(st.out(frame_status_out, sizeof(int32_t) * np * fpp, &dfst));
-  OFDM_TRY(st.out(frame_fo_out, sizeof(double) * np * fpp, &dffo_f));
+  OFDM_TRY(ftg.out(st, frame_tg_out, np * fpp));
+  OFDM_TRY(fst.out(st, frame_status_out, np * fpp));
+  OFDM_TRY(ffo.out(st, frame_fo_out, np * fpp));
   if (n_points == 0) return st.finish();
-  OFDM_TRY(table(acf_dropped_out, cnt * np, &ddrop));
-  OFDM_TRY(table(tg_hist_out, cnt * np, &dtgh));
-  OFDM_TRY(table(fallback_out, sizeof(uint64_t) * np, &dfall));
-  OFDM_TRY(table(phase_hist_out, sizeof(uint64_t) * (size_t)stride * np, &dph));
-  OFDM_TRY(table(ffo_err_out, 2 * sizeof(double) * np, &dffo));
+  unsigned long long *ddrop, *dtgh, *dfall, *dph;
+  double* dferr;
+  OFDM_TRY(txf_table(st, acf_dropped_out, no * np, ddrop));
+  OFDM_TRY(txf_table(st, tg_hist_out, no * np, dtgh));
+  OFDM_TRY(txf_table(st, fallback_out, np, dfall));
+  OFDM_TRY(txf_table(st, phase_hist_out, (size_t)stride * np, dph));
+  OFDM_TRY(txf_table(st, ffo_err_out, 2 * np, dferr));
   OFDM_HIP(hipMemsetAsync(dsums, 0, row * np, stream));                   // the accumulators: 0 + a_0 + a_1 + ..
-  OFDM_HIP(hipMemsetAsync(ddrop, 0, cnt * np, stream));
   if (dpeak) OFDM_HIP(hipMemsetAsync(dpeak, 0, row * np, stream));
-  OFDM_HIP(hipMemsetAsync(dtgh, 0, cnt * np, stream));
-  OFDM_HIP(hipMemsetAsync(dfall, 0, sizeof(uint64_t) * np, stream));
-  OFDM_HIP(hipMemsetAsync(dph, 0, sizeof(uint64_t) * (size_t)stride * np, stream));
-  OFDM_HIP(hipMemsetAsync(dffo, 0, 2 * sizeof(double) * np, stream));
   if (frames_per_point == 0) return st.finish();
-  const bool imp_on = sto_mode != 0 || cfo_mode != 0;                     // both off: the plain channel pass, the same frames
-  const TxfUse u = sync_use(scr_reg15 != nullptr, imp_on, fading ? (int)ch.delay.size() : 0);
+  const bool imp_on = a.imp_on();
+  const TxfUse u = a.use(ch);
   const int64_t CH = sync_chunk(s, u, frames_per_point, max_frames_per_chunk, W);
-  void *rows, *err, *ctg = nullptr, *cst = nullptr, *cfo_s = nullptr;
+  void *rows, *err;
   OFDM_TRY(st.scratch(row * (size_t)CH, &rows));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)CH, &err));
-  if (!dftg) OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)CH, &ctg));
-  if (!dfst) OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)CH, &cst));
-  if (!dffo_f) OFDM_TRY(st.scratch(sizeof(double) * (size_t)CH, &cfo_s));
-  OFDM_TRY(tx_dict_device(pl));
-  TxfBuffers b;
-  OFDM_TRY(txf_workspace(pl, CH, u, b));
-  TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
-  imp.sto = b.sto;
-  imp.cfo = b.cfo;
-  fade.amp = b.amp;
-  for (int64_t p = 0; p < n_points; ++p) {
-    const double snr_lin = std::pow(10.0, snr_db[p] / 10.0);
-    const uint32_t k0 = (uint32_t)seeds[p], k1 = (uint32_t)(seeds[p] >> 32);
-    for (int64_t c0 = 0; c0 < frames_per_point; c0 += CH) {
-      const int64_t nf = std::min<int64_t>(CH, frames_per_point - c0);
-      OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(frame0 + c0), nf, scr_reg15, b, b.rx, nullptr, nullptr,
-                            imp_on ? &imp : nullptr, fading ? &fade : nullptr));
-      const size_t at = (size_t)(p * frames_per_point + c0);
-      int64_t* tg = dftg ? (int64_t*)dftg + at : (int64_t*)ctg;
-      int32_t* stt = dfst ? (int32_t*)dfst + at : (int32_t*)cst;
-      double* fo = dffo_f ? (double*)dffo_f + at : (double*)cfo_s;
-      auto capture = [&](auto zero) {
-        using T = decltype(zero);
-        SyncOut<T> o{};
-        o.rows = (double*)rows; o.tg = tg; o.fo = fo; o.status = stt;
-        o.sto = imp_on ? b.sto : nullptr; o.cfo = imp_on ? b.cfo : nullptr;
-        o.tg_hist = (unsigned long long*)dtgh + (size_t)n_out * p;
-        o.phase_hist = (unsigned long long*)dph + (size_t)stride * p;
-        o.fallback = (unsigned long long*)dfall + p;
-        o.err = (double*)err;
-        o.stride = stride;
-        return sync_capture_frames<T>(s, b.rx, nf, W, o);
-      };
-      OFDM_TRY(pl->f64 ? capture(0.0) : capture(0.0f));
-      const SyncPass sp = sync_pass(s, W, nf);
-      hipLaunchKernelGGL(sync_accumulate_kernel, dim3(sp.acc_grid), dim3(sp.acc_threads), 0, stream, (const double*)rows,
-                         (const double*)err, nf, n_out, (double*)dsums + (size_t)n_out * p,
-                         (unsigned long long*)ddrop + (size_t)n_out * p, dpeak ? (double*)dpeak + (size_t)n_out * p : nullptr,
-                         (double*)dffo + 2 * p);
-      OFDM_TRY(check_launch("sync_accumulate_kernel"));
-    }
-  }
+  OFDM_TRY(ftg.scratch(st, (size_t)CH));
+  OFDM_TRY(fst.scratch(st, (size_t)CH));
+  OFDM_TRY(ffo.scratch(st, (size_t)CH));
+  const TxfImp imp = a.imp();
+  OFDM_TRY(txf_sweep_points(pl, ch, a.points(), scr_reg15, CH, imp_on ? &imp : nullptr, a.fading() ? &fade : nullptr, u,
+                            [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t at) -> int {
+    auto capture = [&](auto zero) {
+      using T = decltype(zero);
+      SyncOut<T> o{};
+      o.rows = (double*)rows; o.tg = ftg.at(at); o.fo = ffo.at(at); o.status = fst.at(at);
+      o.sto = imp_on ? b.sto : nullptr; o.cfo = imp_on ? b.cfo : nullptr;
+      o.tg_hist = dtgh + no * p;
+      o.phase_hist = dph + (size_t)stride * p;
+      o.fallback = dfall + p;
+      o.err = (double*)err;
+      o.stride = stride;
+      return sync_capture_frames<T>(s, b.rx, nf, W, o);
+    };
+    OFDM_TRY(pl->f64 ? capture(0.0) : capture(0.0f));
+    const SyncPass sp = sync_pass(s, W, nf);
+    hipLaunchKernelGGL(sync_accumulate_kernel, dim3(sp.acc_grid), dim3(sp.acc_threads), 0, stream, (const double*)rows,
+                       (const double*)err, nf, n_out, (double*)dsums + no * p, ddrop + no * p,
+                       dpeak ? (double*)dpeak + no * p : nullptr, dferr + 2 * p);
+    return check_launch("sync_accumulate_kernel");
+  }));
   return st.finish();
 }

@@ -11,7 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "txf_plan.hpp"      // TxfShape, TxfUse, TxfCall, txf_check_plan, txf_check_sweep, txf_call_channel, txf_chunk
+#include "txf_plan.hpp"      // TxfShape, TxfUse, TxfCall, txf_check_plan, txf_study_prelude, txf_chunk
 
 namespace ofdm {
 
@@ -52,36 +52,18 @@ inline int spectrum_rx_prelude(const TxfShape* plan, bool rx, bool f64_flag, int
   return spectrum_check_capture(*plan, cap, WHAT, w);
 }
 
-// ---- ofdm_spectrum_study.  c: the generator arguments as the sweeps fill them (n_frames = frames_per_point, with_points, with_imp,
-// with_h or with_fading); both_channels: h and a tap-delay line are given.  The order of its checks:
-//   bad arguments (plan, n_points >= 0, frames_per_point >= 0, max_frames_per_chunk >= 0) -> snr_db / seeds -> too many points ->
-//   the plan (as above, the streams of one point) -> sto_mode / cfo_mode -> register entries 0 / 1 -> h and taps together -> the
-//   channel (h: bad channel, tap delay, tap count, as "tx_frames_fused"; taps: n_taps, pointers, per tap delay range, duplicate,
-//   power; the sum) -> the capture (above)
+// ---- ofdm_spectrum_study.  The order of its checks: the front every study shares (txf_study_prelude: the generator's arguments,
+// max_frames_per_chunk >= 0) -> the capture (above)
 inline int spectrum_study_prelude(const TxfCall& c, bool both_channels, const SpecCapture& cap, TxfChannel& ch, TxfGains& g, TxfWhy& w) {
   static const char* const WHAT = "spectrum_study";
-  if (const int id = txf_check_args(c.plan && c.n_points >= 0 && c.n_frames >= 0 && c.max_chunk >= 0, WHAT, w)) return id;
-  if (const int id = txf_check_sweep(c, WHAT, w)) return id;
-  if (const int id = txf_check_modes(c.sto_mode, c.cfo_mode, WHAT, w)) return id;
-  if (c.scr_reg15)
-    for (int m = 0; m < 15; ++m)
-      if (c.scr_reg15[m] > 1) return txf_refuse(w, TXF_REFUSE_REGISTER, "%s: register entries must be 0 or 1", WHAT);
-  if (both_channels) return txf_refuse(w, SPEC_REFUSE_BOTH, "%s: give h (one channel for every frame) or taps (a channel per frame), not both", WHAT);
-  if (const int id = txf_call_channel(c, c.plan->f64 != 0, WHAT, ch, g, w)) return id;
+  if (const int id = txf_study_prelude(c, both_channels, SPEC_REFUSE_BOTH, WHAT, ch, g, w)) return id;
   return spectrum_check_capture(*c.plan, cap, WHAT, w);
 }
 
-// ---- the chunk of the study: frames of one point, budgeted on the generator's regions with the RX region (txf_plan.hpp) and,
+// ---- the chunk of the study: frames of one point, budgeted on the generator's regions with the RX region (txf_study_use) and,
 // beside the workspace, the chunk's power rows (Nfft doubles per frame; with the peak wanted a second row per frame, the maximum
 // over the frame's windows)
-inline TxfUse spectrum_use(bool scr, bool imp, int fade_taps) {
-  TxfUse u;
-  u.scr = scr;
-  u.sweep = true;            // the frames stay in the workspace, where the transform reads them
-  u.imp = imp;
-  u.fade_taps = fade_taps;
-  return u;
-}
+inline TxfUse spectrum_use(bool scr, bool imp, int fade_taps) { return txf_study_use(scr, imp, fade_taps); }   // the name callers know
 
 inline size_t spectrum_row_bytes(const TxfShape& s, bool peak) { return sizeof(double) * (size_t)s.nfft * (peak ? 2 : 1); }
 

@@ -365,4 +365,38 @@ inline int txf_task4_prelude(const TxfCall& c, TxfChannel& ch, TxfGains& g, TxfW
   return TXF_OK;
 }
 
+// ---- the studies (ofdm_spectrum_study, _sync_study, _fine_study, _ifo_study, _hest_study): one device-resident call that generates
+// the frames of every point of a sweep and runs part of a receiver on them.
+// The front of a study's checks, in this order; the study's own capture checks follow it.  c: the generator arguments as the sweeps
+// fill them (n_frames = frames_per_point, with_points, with_imp, with_h or with_fading); both_channels: h and a tap-delay line are
+// given, refused with the study's own id refuse_both; chunk_cap: the largest max_frames_per_chunk the study takes (65535 behind
+// the Task-4 receiver).
+//   bad arguments (plan, n_points >= 0, frames_per_point >= 0, max_frames_per_chunk 0 .. chunk_cap) -> snr_db / seeds -> too many
+//   points -> the plan (the streams of one point) -> sto_mode / cfo_mode -> register entries 0 / 1 -> h and taps together -> the
+//   channel (h: bad channel, tap delay, tap count, as "tx_frames_fused"; taps: n_taps, pointers, per tap delay range, duplicate,
+//   power; the sum)
+inline int txf_study_prelude(const TxfCall& c, bool both_channels, int refuse_both, const char* what, TxfChannel& ch, TxfGains& g,
+                             TxfWhy& w, int64_t chunk_cap = INT64_MAX) {
+  if (const int id = txf_check_args(c.plan && c.n_points >= 0 && c.n_frames >= 0 && c.max_chunk >= 0 && c.max_chunk <= chunk_cap, what, w))
+    return id;
+  if (const int id = txf_check_sweep(c, what, w)) return id;
+  if (const int id = txf_check_modes(c.sto_mode, c.cfo_mode, what, w)) return id;
+  if (c.scr_reg15)
+    for (int m = 0; m < 15; ++m)
+      if (c.scr_reg15[m] > 1) return txf_refuse(w, TXF_REFUSE_REGISTER, "%s: register entries must be 0 or 1", what);
+  if (both_channels) return txf_refuse(w, refuse_both, "%s: give h (one channel for every frame) or taps (a channel per frame), not both", what);
+  return txf_call_channel(c, c.plan->f64 != 0, what, ch, g, w);
+}
+
+// what a study needs of the workspace: the generator's regions with the RX region (the frames stay in the workspace, where the
+// capture reads them)
+inline TxfUse txf_study_use(bool scr, bool imp, int fade_taps) {
+  TxfUse u;
+  u.scr = scr;
+  u.sweep = true;
+  u.imp = imp;
+  u.fade_taps = fade_taps;
+  return u;
+}
+
 }  // namespace ofdm

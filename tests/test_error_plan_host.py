@@ -195,5 +195,6 @@ def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_devic
     assert '#include "error_plan.hpp"' in hip and "err_profile_prelude(" in hip and "err_study_prelude(" in hip
     assert "err_chunk(" in hip and "err_pass(" in hip and "TXF_WS_BUDGET" not in hip
     assert "err_position(" in hip and "err_advance(" in hip
-    assert "rx_chain_task5_run(" in hip and "rx_chain_task4_run(" in hip and "txf_generate(" in hip     # called, not rewritten
+    assert "rx_chain_task5_run(" in hip and "rx_chain_task4_run(" in hip                               # called, not rewritten
+    assert "txf_sweep_points(" in hip and "txf_generate(" in open(os.path.join(CSRC, "txf_study.hpp")).read()   # the generator: through the shared loop
     assert "hipfft" not in hip.lower() and "rocblas" not in hip.lower()

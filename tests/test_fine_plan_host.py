@@ -190,13 +190,17 @@ def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_devic
     src = open(HEADER).read()
     for fmt in ("%s: variant must be 0 (T5/fine_sync.m) or 1 (T4/fine_sync.m) (%d)", "%s: fine_sync needs at least two pilot carriers (%d)",
                 "%s: Np * N_symb must be below 2^31 (%lld)", "%s: no output is given", "%s: n_frames must be 0 .. 2^31 - 1 (%lld)",
-                "%s: bins must have n >= 1 and finite lo < hi (%d, %g, %g)",
-                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+                "%s: bins must have n >= 1 and finite lo < hi (%d, %g, %g)"):
         assert f'"{fmt}"' in src, fmt
     main = open(os.path.join(ROOT, "tests", "host", "fine_plan_main.cpp")).read()
     names = re.findall(r'"(\w+)"', re.search(r"IDS\[FINE_REFUSALS\] = \{(.*?)\};", main, re.S).group(1))
     txf = open(os.path.join(CSRC, "txf_plan.hpp")).read()
     txf_enum = re.search(r"TXF_OK = 0,(.*?)TXF_REFUSALS", txf, re.S).group(1)
+    # the front every study shares: its texts live in txf_plan.hpp, and the header calls it
+    for fmt in ("%s: register entries must be 0 or 1",
+                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+        assert f'"{fmt}"' in txf and f'"{fmt}"' not in src, fmt
+    assert "txf_study_prelude(" in src and "inline int txf_study_prelude(" in txf
     own = re.search(r"enum \{ FINE_REFUSE_FRAMES = TXF_REFUSALS,(.*?)FINE_REFUSALS \}", src, re.S).group(1)
     mine = [n.replace("PILOTS", "FEW_PILOTS") for n in re.findall(r"FINE_REFUSE_(\w+)", own)]
     assert [n.upper() for n in names[1:]] == re.findall(r"TXF_REFUSE_(\w+)", txf_enum) + ["FRAMES"] + mine

@@ -165,13 +165,17 @@ def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_devic
     for fmt in ("%s: time_desync must be 0 or 1 (%d)", "%s: freq_desync must be 0 or 1 (%d)",
                 "%s: estimate_channel needs at least two pilot carriers (%d)",
                 "%s: bins must have n 1 .. %d and finite lo < hi (%d, %g, %g)", "%s: no output is given",
-                "%s: n_frames must be 0 .. 2^31 - 1 (%lld)", "%s: register entries must be 0 or 1",
-                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+                "%s: n_frames must be 0 .. 2^31 - 1 (%lld)"):
         assert f'"{fmt}"' in src, fmt
     main = open(os.path.join(ROOT, "tests", "host", "hest_plan_main.cpp")).read()
     names = re.findall(r'"(\w+)"', re.search(r"IDS\[HEST_REFUSALS\] = \{(.*?)\};", main, re.S).group(1))
     txf = open(os.path.join(CSRC, "txf_plan.hpp")).read()
     txf_enum = re.search(r"TXF_OK = 0,(.*?)TXF_REFUSALS", txf, re.S).group(1)
+    # the front every study shares: its texts live in txf_plan.hpp, and the header calls it
+    for fmt in ("%s: register entries must be 0 or 1",
+                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+        assert f'"{fmt}"' in txf and f'"{fmt}"' not in src, fmt
+    assert "txf_study_prelude(" in src and "inline int txf_study_prelude(" in txf
     own = re.search(r"enum \{ HEST_REFUSE_FRAMES = TXF_REFUSALS,(.*?)HEST_REFUSALS \}", src, re.S).group(1)
     assert [n.upper() for n in names[1:]] == re.findall(r"TXF_REFUSE_(\w+)", txf_enum) + ["FRAMES"] + re.findall(r"HEST_REFUSE_(\w+)", own)
     assert "hip/" not in src and "__global__" not in src and "hipLaunch" not in src

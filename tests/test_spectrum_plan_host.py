@@ -144,13 +144,17 @@ def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_devic
     src = open(HEADER).read()
     for fmt in ("%s: first must be >= 0 (%lld)", "%s: n_windows must be >= 1 (%lld)",
                 "%s: %lld windows from sample %lld on end behind the frame of %lld samples", "%s: no output is given",
-                "%s: n_frames must be 0 .. 2^31 - 1 (%lld)", "%s: register entries must be 0 or 1",
-                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+                "%s: n_frames must be 0 .. 2^31 - 1 (%lld)"):
         assert f'"{fmt}"' in src, fmt
     main = open(os.path.join(ROOT, "tests", "host", "spectrum_plan_main.cpp")).read()
     names = re.findall(r'"(\w+)"', re.search(r"IDS\[SPEC_REFUSALS\] = \{(.*?)\};", main, re.S).group(1))
     txf = open(os.path.join(CSRC, "txf_plan.hpp")).read()
     txf_enum = re.search(r"TXF_OK = 0,(.*?)TXF_REFUSALS", txf, re.S).group(1)
+    # the front every study shares: its texts live in txf_plan.hpp, and the header calls it
+    for fmt in ("%s: register entries must be 0 or 1",
+                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+        assert f'"{fmt}"' in txf and f'"{fmt}"' not in src, fmt
+    assert "txf_study_prelude(" in src and "inline int txf_study_prelude(" in txf
     own = re.search(r"enum \{ SPEC_REFUSE_FRAMES = TXF_REFUSALS,(.*?)SPEC_REFUSALS \}", src, re.S).group(1)
     assert [n.upper() for n in names[1:]] == re.findall(r"TXF_REFUSE_(\w+)", txf_enum) + ["FRAMES"] + re.findall(r"SPEC_REFUSE_(\w+)", own)
     assert "hip/" not in src and "__global__" not in src and "hipLaunch" not in src and "__device__" not in src
@@ -158,4 +162,4 @@ def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_devic
     hip = open(os.path.join(CSRC, "ofdm_spectrum.hip")).read()
     assert '#include "spectrum_plan.hpp"' in hip and "spectrum_rx_prelude(" in hip and "spectrum_study_prelude(" in hip
     assert "spectrum_chunk(" in hip and "spectrum_pass(" in hip and "TXF_WS_BUDGET" not in hip
-    assert "hipfft" not in hip.lower() and "atomic" not in hip.split('#include "txf_generate.hpp"')[1]
+    assert "hipfft" not in hip.lower() and "atomic" not in hip.split('#include "txf_study.hpp"')[1]

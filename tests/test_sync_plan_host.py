@@ -158,13 +158,17 @@ def test_wrapped_fractional_error_against_the_twin(host_program):
 def test_every_refusal_text_is_in_the_header_and_the_header_is_free_of_the_device_runtime():
     src = open(HEADER).read()
     for fmt in ("%s: WidthWindow must be 1 .. %d (%lld)", "%s: a frame of %lld samples is shorter than WidthWindow + Nfft + 1 (%lld + %d + 1)",
-                "%s: no output is given", "%s: n_frames must be 0 .. 2^31 - 1 (%lld)", "%s: register entries must be 0 or 1",
-                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+                "%s: no output is given", "%s: n_frames must be 0 .. 2^31 - 1 (%lld)"):
         assert f'"{fmt}"' in src, fmt
     main = open(os.path.join(ROOT, "tests", "host", "sync_plan_main.cpp")).read()
     names = re.findall(r'"(\w+)"', re.search(r"IDS\[SYNC_REFUSALS\] = \{(.*?)\};", main, re.S).group(1))
     txf = open(os.path.join(CSRC, "txf_plan.hpp")).read()
     txf_enum = re.search(r"TXF_OK = 0,(.*?)TXF_REFUSALS", txf, re.S).group(1)
+    # the front every study shares: its texts live in txf_plan.hpp, and the header calls it
+    for fmt in ("%s: register entries must be 0 or 1",
+                "%s: give h (one channel for every frame) or taps (a channel per frame), not both"):
+        assert f'"{fmt}"' in txf and f'"{fmt}"' not in src, fmt
+    assert "txf_study_prelude(" in src and "inline int txf_study_prelude(" in txf
     own = re.search(r"enum \{ SYNC_REFUSE_FRAMES = TXF_REFUSALS,(.*?)SYNC_REFUSALS \}", src, re.S).group(1)
     assert [n.upper() for n in names[1:]] == re.findall(r"TXF_REFUSE_(\w+)", txf_enum) + ["FRAMES"] + re.findall(r"SYNC_REFUSE_(\w+)", own)
     assert "hip/" not in src and "__global__" not in src and "hipLaunch" not in src
