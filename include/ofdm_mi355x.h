@@ -153,7 +153,8 @@ int ofdm_equalize_signal(const void* x, int nfft, int64_t n_symb, const void* h_
 /* T5/LS_CE.m:1-34 (symbol 1 only).  y[nfft*n_symb], xp[n_pilots*n_symb] -> h_ls[n_carrier]. */
 int ofdm_LS_CE(const void* y, int nfft, int64_t n_symb, const void* xp, const int32_t* pilot_loc,
                int n_pilots, int n_carrier, void* h_ls_out, int flags);
-/* T5/MMSE_CE.m:1-39.  h[h_len] = CIR guess, snr_db. */
+/* T5/MMSE_CE.m:1-39.  h[h_len] = CIR guess, snr_db.  The rms delay spread of :19-24 has r2 - r^2 clamped at 0 (all the energy
+ * of h in one bin: the exact value is 0, the computed one rounding noise of either sign; MMSE_CE.m takes a complex sqrt there). */
 int ofdm_MMSE_CE(const void* y, int nfft, int64_t n_symb, const void* xp, const int32_t* pilot_loc,
                  int n_pilots, int n_carrier, const void* h, int h_len, double snr_db,
                  void* h_mmse_out, int flags);
@@ -209,6 +210,7 @@ int ofdm_rx_plan_destroy(ofdm_rx_plan* plan);
  * mrdivide of :36 and the spline re-interpolation of :38 folded together); it is built here once, on the host in
  * double, and applied to a whole batch as one complex GEMM (matrix cores in fp32).  h: host array of n_h complex
  * values in the precision of `flags` (OFDM_F32 / OFDM_F64); h = NULL returns the plan to OMP mode.
+ * The rms delay spread has r2 - r^2 clamped at 0 (a one-tap h = a pure delay gives tau_rms = 0, never NaN); an all-zero h is refused.
  * Needs 2..512 pilots; the chain call needs the fast-path geometry (Nfft 512..4096). */
 int ofdm_rx_plan_set_mmse(ofdm_rx_plan* plan, const void* h, int64_t n_h, double snr_db, int flags);
 /* MMSE mode without a supplied channel: per frame H_LS = LS_CE(Y, Xp, pilot_loc, N_carrier), h = ifft(H_LS) (N_carrier points),
@@ -573,7 +575,9 @@ int64_t ofdm_rx_plan_frame_bytes(const ofdm_rx_plan* plan);   /* packed bytes pe
  * for each (:269-304).
  *   nmse_out[4][n_frames] (double), errors_out[4][n_frames] (uint32 bit errors): rows LS, MMSE, MP, OMP.
  * The MP projections S^H * residue run as one real GEMM per iteration on the matrix cores in fp32 when Np is a multiple of
- * 16 (dense dictionaries of random pilot masks, :58-64).  At most 65535 realisations and 64 channel taps per call. */
+ * 16 (dense dictionaries of random pilot masks, :58-64).  At most 65535 realisations and 64 channel taps per call.
+ * The rms delay spread of MMSE_CE.m:19-24 is taken over the taps with delay < N_carrier (h_t(1:N_carrier), :176), r2 - r^2 clamped
+ * at 0 (a realisation with one such path: tau_rms = 0); a realisation with no such path (0 / 0 in :22) is refused. */
 int ofdm_task5_part2_tile(ofdm_rx_plan* plan, const void* tx_noised, const int32_t* tap_delay, const double* tap_amp,
                           int n_ch_taps, int64_t n_frames, double snr_db, const uint8_t* ref_bits, double* nmse_out,
                           uint32_t* errors_out, int flags);

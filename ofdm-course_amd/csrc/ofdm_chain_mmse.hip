@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "chain_fast_core.hpp"
+#include "mmse_tau.hpp"
 #include "spline_op.hpp"
 
 namespace ofdm {
@@ -34,9 +35,7 @@ int mmse_build_operator(const c64* h, int64_t n_h, double snr_db, const int32_t*
     s0 += p; s1 += p * (double)k; s2 += p * (double)k * (double)k;
   }
   OFDM_ARG(s0 > 0, "rx_plan_set_mmse: impulse response is all zero");
-  const double r = s1 / s0, r2 = s2 / s0;
-  const double tau_rms = std::sqrt(r2 - r * r);
-  const double c = 2.0 * M_PI * tau_rms * (1.0 / (double)n_carrier) * nps;          // :25-26,:30
+  const double c = mmse_tau_c(s0, s1, s2, 1.0 / (double)n_carrier, nps);            // :22-26,:30 (one tap: r2 - r^2 clamped at 0)
   // Rpp = toeplitz(1 / (1 + j c (i - j))) + I / snr  (:33-35), Hermitian positive definite
   std::vector<zc> A((size_t)np * np);
   for (int i = 0; i < np; ++i)

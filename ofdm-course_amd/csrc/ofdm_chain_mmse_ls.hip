@@ -13,6 +13,7 @@
 
 #include "mmse_levinson.hpp"
 #include "mmse_ls_forms.hpp"
+#include "mmse_tau.hpp"
 #include "rx_plan.hpp"
 #include "spline_op.hpp"
 
@@ -89,8 +90,7 @@ __global__ __launch_bounds__(256) void mmse_ls_wave_kernel(const cx<T>* __restri
     for (int w = 0; w < wpw; ++w) t += red[w][q][wave];
     m[q] = t;
   }
-  const double r = m[1] / m[0], r2 = m[2] / m[0];              // MMSE_CE.m:20-23
-  const double c = cscale * sqrt(fmax(r2 - r * r, 0.0));       // :24-26,:30 (a one-tap channel: the difference is rounding noise)
+  const double c = cscale * mmse_tau_rms(m[0], m[1], m[2]);    // MMSE_CE.m:20-26,:30 (a one-tap channel: r2 - r^2 clamped at 0)
   mmse_toeplitz_wave<T>(ypil + f * np, c, inv_snr, np, lev + (size_t)wave * 4 * np, vout + f * np, lane);
 }
 

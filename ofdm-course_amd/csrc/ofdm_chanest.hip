@@ -1,6 +1,7 @@
 // Channel estimators: interpolate / estimate_channel / LS_CE / MMSE_CE (spline as a precomputed
 // linear operator, Levinson solve of the Hermitian-Toeplitz MMSE system) and the single-problem
 // MP_estimate / OMP_estimate (the batched OMP of the benchmark chain lives in ofdm_chain.hip).
+#include "mmse_tau.hpp"
 #include "spline_op.hpp"
 #include "pursuit_core.hpp"
 
@@ -91,8 +92,7 @@ __global__ __launch_bounds__(MMSE_THREADS) void mmse_kernel(const cx<T>* __restr
   }
   s0 = block_sum_c64(s0, red);
   s1 = block_sum_c64(s1, red);
-  const double hh = s0.x, r = s0.y / hh, r2 = s1.x / hh;
-  const double tau_rms = sqrt(r2 - r * r);
+  const double tau_rms = mmse_tau_rms(s0.x, s0.y, s1.x);           // (one tap: r2 - r^2 is rounding noise, clamped at 0)
   if (tid == 0 && tau_out) tau_out[0] = tau_rms;
   const double c = 2.0 * M_PI * tau_rms * df * nps;              // j2pi_tau_df * Nps  (:26,:30)
   // ---- Toeplitz column: rf2[i][j] = 1/(1 + j c (i-j))  (:33) ; diag += 1/snr (:35)

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "mmse_levinson.hpp"
+#include "mmse_tau.hpp"
 #include "omp_wide_host.hpp"
 #include "rx_plan.hpp"
 #include "spline_op.hpp"
@@ -397,8 +398,8 @@ __global__ __launch_bounds__(256) void mse_tau_kernel(const cx<T>* __restrict__ 
   __syncthreads();
   if (threadIdx.x == 0) {
     const double H = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-    const double r = (red[1][0] + red[1][1] + red[1][2] + red[1][3]) / H, r2 = (red[2][0] + red[2][1] + red[2][2] + red[2][3]) / H;
-    cvals[f] = 2.0 * M_PI * sqrt(fmax(r2 - r * r, 0.0)) * (1.0 / (double)nc) * nps;      // :23-26, df = 1 / N_carrier
+    const double S1 = red[1][0] + red[1][1] + red[1][2] + red[1][3], S2 = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+    cvals[f] = mmse_tau_c(H, S1, S2, 1.0 / (double)nc, nps);                            // :22-26, df = 1 / N_carrier
   }
 }
 
@@ -569,8 +570,8 @@ extern "C" int ofdm_task5_part2_tile(ofdm_rx_plan* pl, const void* tx_noised, co
       const double p = ar * ar + ai * ai;
       hh += p; s1 += p * d; s2 += p * (double)d * d;
     }
-    const double r = s1 / hh, r2 = s2 / hh;
-    cvals[f] = 2.0 * M_PI * sqrt(r2 - r * r) * df * nps;
+    OFDM_ARG(hh > 0, "task5_part2_tile: impulse response of realisation %lld is all zero inside 1..N_carrier", (long long)f);
+    cvals[f] = mmse_tau_c(hh, s1, s2, df, nps);                    // (one path: r2 - r^2 clamped at 0)
   }
   Stage st(flags);
   const void *dtx, *ddel, *damp, *dcv, *dref;
