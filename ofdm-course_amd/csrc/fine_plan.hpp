@@ -143,24 +143,17 @@ inline int64_t fine_chunk(const TxfShape& s, const TxfUse& u, int64_t frames_per
 }
 
 // ---- the launch shape.  fine_capture_kernel: one workgroup of FINE_THREADS threads per frame, the static LDS of the two
-// reductions only (the rows are written as they are formed).  fine_accumulate_kernel: workgroups of FINE_ACC_THREADS threads own
-// FINE_ACC_COLS entries of the curve each and stage FINE_ACC_TILE rows at a time in LDS; one more workgroup, the last, sums the
-// chunk's per-frame scalars.
-constexpr int FINE_ACC_THREADS = 256;
-constexpr int FINE_ACC_COLS = 64;
-constexpr int FINE_ACC_TILE = 64;
-constexpr size_t FINE_ACC_LDS = sizeof(double) * FINE_ACC_TILE * FINE_ACC_COLS;
-
-static_assert(FINE_ACC_LDS == 32768 && FINE_ACC_LDS <= SYNC_LDS_LIMIT && FINE_SCRATCH_BYTES <= SYNC_LDS_LIMIT, "the LDS of the two kernels");
-static_assert(FINE_ACC_THREADS % FINE_ACC_COLS == 0 && FINE_ACC_TILE % (FINE_ACC_THREADS / FINE_ACC_COLS) == 0, "rows per thread and tile");
+// reductions only (the rows are written as they are formed).  fine_accumulate_kernel: the studies' accumulate launch
+// (txf_plan.hpp: STUDY_ACC_*) over the L entries of the curve, with the tail workgroup for the chunk's per-frame scalars.
+static_assert(FINE_SCRATCH_BYTES <= SYNC_LDS_LIMIT, "the capture kernel's LDS");
 
 struct FinePass {
   int threads;               // FINE_THREADS
   unsigned grid;             // frames: one workgroup each
   size_t lds;                // static LDS of the capture kernel
   int trips;                 // ceil(L / (FINE_THREADS * FINE_U)): passes of a workgroup over its frame
-  int acc_threads;           // FINE_ACC_THREADS
-  unsigned acc_grid;         // ceil(L / FINE_ACC_COLS) + 1
+  int acc_threads;           // STUDY_ACC_THREADS
+  unsigned acc_grid;         // ceil(L / STUDY_ACC_COLS) + 1
   size_t acc_lds;            // static LDS of the accumulating kernel
 };
 
@@ -171,9 +164,9 @@ inline FinePass fine_pass(const TxfShape& s, int variant, int64_t frames) {
   p.grid = (unsigned)frames;
   p.lds = FINE_SCRATCH_BYTES;
   p.trips = (int)((L + FINE_THREADS * FINE_U - 1) / (FINE_THREADS * FINE_U));
-  p.acc_threads = FINE_ACC_THREADS;
-  p.acc_grid = (unsigned)((L + FINE_ACC_COLS - 1) / FINE_ACC_COLS) + 1u;
-  p.acc_lds = FINE_ACC_LDS;
+  p.acc_threads = STUDY_ACC_THREADS;
+  p.acc_grid = study_acc_grid(L, 1);
+  p.acc_lds = STUDY_ACC_LDS;
   return p;
 }
 

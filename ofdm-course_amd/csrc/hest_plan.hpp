@@ -108,16 +108,13 @@ inline int64_t hest_chunk(const TxfShape& s, const TxfUse& u, int64_t frames_per
 // lanes: from 256 carriers on one frame per workgroup (a lane walks the carriers with a stride of 256), below that a frame takes
 // the next power of two of lanes (at least 16) and a workgroup holds 256 / lanes frames, so that no wavefront is launched part
 // empty.  Static LDS: the taps of every frame of the workgroup.  hest_frame_sum_kernel: one workgroup of 256 threads per frame, the
-// four wave partials.  hest_accumulate_kernel: workgroups of HEST_ACC_THREADS threads own HEST_ACC_COLS carriers (pilots) of one
-// quantity each and stage HEST_ACC_TILE rows at a time in LDS, doubles and the bytes beside them.
+// four wave partials.  hest_accumulate_kernel: the studies' accumulate shape (txf_plan.hpp: STUDY_ACC_*) over the carriers (pilots)
+// of one quantity each, no tail workgroup; its tile holds the doubles and the bytes beside them, 9 bytes per entry.
 constexpr int HEST_THREADS = 256;
 constexpr int HEST_MIN_LANES = 16;
 constexpr int HEST_MAX_FRAMES_PER_WG = HEST_THREADS / HEST_MIN_LANES;
 constexpr size_t HEST_CAPTURE_LDS = 16 * (size_t)HEST_MAX_FRAMES_PER_WG * TXF_MAX_TAPS;
-constexpr int HEST_ACC_THREADS = 256;
-constexpr int HEST_ACC_COLS = 64;
-constexpr int HEST_ACC_TILE = 64;
-constexpr size_t HEST_ACC_LDS = (sizeof(double) + 1) * HEST_ACC_TILE * HEST_ACC_COLS;
+constexpr size_t HEST_ACC_LDS = (sizeof(double) + 1) * STUDY_ACC_TILE * STUDY_ACC_COLS;
 
 constexpr int hest_lanes(int n_carrier) {
   int l = HEST_MIN_LANES;
@@ -127,7 +124,6 @@ constexpr int hest_lanes(int n_carrier) {
 
 static_assert(HEST_CAPTURE_LDS == 16384 && HEST_CAPTURE_LDS <= SYNC_LDS_LIMIT, "the capture kernel's LDS");
 static_assert(HEST_ACC_LDS == 36864 && HEST_ACC_LDS <= SYNC_LDS_LIMIT, "the accumulating kernel's LDS");
-static_assert(HEST_ACC_THREADS % HEST_ACC_COLS == 0 && HEST_ACC_TILE % (HEST_ACC_THREADS / HEST_ACC_COLS) == 0, "rows per thread and tile");
 static_assert(hest_lanes(1) == 16 && hest_lanes(64) == 64 && hest_lanes(65) == 128 && hest_lanes(256) == 256 && hest_lanes(4096) == 256,
               "the lanes of a frame");
 
@@ -137,9 +133,9 @@ struct HestPass {
   int frames_per_wg;         // threads / lanes
   size_t lds;                // static LDS of the capture kernel
   unsigned grid;             // ceil(frames / frames_per_wg)
-  int acc_threads;           // HEST_ACC_THREADS
-  unsigned acc_grid;         // ceil(N_carrier / HEST_ACC_COLS), times HEST_CARRIER_ROWS quantities in y
-  unsigned acc_grid_pilots;  // ceil(Np / HEST_ACC_COLS), times HEST_PILOT_ROWS quantities in y
+  int acc_threads;           // STUDY_ACC_THREADS
+  unsigned acc_grid;         // ceil(N_carrier / STUDY_ACC_COLS), times HEST_CARRIER_ROWS quantities in y
+  unsigned acc_grid_pilots;  // ceil(Np / STUDY_ACC_COLS), times HEST_PILOT_ROWS quantities in y
   size_t acc_lds;            // static LDS of the accumulating kernel
 };
 
@@ -150,9 +146,9 @@ inline HestPass hest_pass(const TxfShape& s, int64_t frames) {
   p.frames_per_wg = HEST_THREADS / p.lanes;
   p.lds = HEST_CAPTURE_LDS;
   p.grid = (unsigned)((frames + p.frames_per_wg - 1) / p.frames_per_wg);
-  p.acc_threads = HEST_ACC_THREADS;
-  p.acc_grid = (unsigned)((s.n_carrier + HEST_ACC_COLS - 1) / HEST_ACC_COLS);
-  p.acc_grid_pilots = (unsigned)((s.np + HEST_ACC_COLS - 1) / HEST_ACC_COLS);
+  p.acc_threads = STUDY_ACC_THREADS;
+  p.acc_grid = study_acc_grid(s.n_carrier, 0);
+  p.acc_grid_pilots = study_acc_grid(s.np, 0);
   p.acc_lds = HEST_ACC_LDS;
   return p;
 }

@@ -99,13 +99,8 @@ inline int64_t ifo_chunk(const TxfShape& s, const TxfUse& u, int64_t frames_per_
 // ---- the launch shape.  ifo_capture_kernel: a transform of Nfft / 8 threads per frame (fft_core.hpp's rule, restated;
 // ofdm_ifo_study.hip asserts it): one workgroup per frame from Nfft 2048 on, and below that workgroups of 256 threads that hold
 // 256 / (Nfft / 8) frames, so that no wavefront is launched part empty.  Static LDS: the padded exchange buffer of every transform
-// and two words per wavefront for the search.  ifo_accumulate_kernel: workgroups of IFO_ACC_THREADS threads own IFO_ACC_BINS bins
-// each (Nfft is a multiple of 64) and stage IFO_ACC_TILE rows at a time in LDS; one more workgroup, the last, sums the chunk's
-// total errors.
-constexpr int IFO_ACC_THREADS = 256;
-constexpr int IFO_ACC_BINS = 64;
-constexpr int IFO_ACC_TILE = 64;
-constexpr size_t IFO_ACC_LDS = sizeof(double) * IFO_ACC_TILE * IFO_ACC_BINS;
+// and two words per wavefront for the search.  ifo_accumulate_kernel: the studies' accumulate launch (txf_plan.hpp:
+// STUDY_ACC_*) over the Nfft bins, with the tail workgroup for the chunk's total errors.
 constexpr int IFO_MAX_WAVES = 16;                    // Nfft 8192: 1024 threads
 
 constexpr int ifo_threads(int nfft) { return nfft / 8 > 256 ? nfft / 8 : 256; }
@@ -117,16 +112,14 @@ constexpr size_t ifo_capture_lds(bool f64, int nfft) {
 // The largest case, double at Nfft 8192, is 147 712 bytes: inside the limit, one workgroup per CU.
 static_assert(ifo_capture_lds(true, 8192) == 147712 && ifo_capture_lds(true, 8192) <= SYNC_LDS_LIMIT, "the capture kernel's LDS at its largest");
 static_assert(ifo_capture_lds(true, 64) == 41088 &&ifo_capture_lds(true, 256) <= ifo_capture_lds(true, 64), "the small sizes pack 32 .. 2 frames");
-static_assert(IFO_ACC_LDS == 32768 && IFO_ACC_LDS <= SYNC_LDS_LIMIT, "the accumulating kernel's LDS");
-static_assert(IFO_ACC_THREADS % IFO_ACC_BINS == 0 && IFO_ACC_TILE % (IFO_ACC_THREADS / IFO_ACC_BINS) == 0, "rows per thread and tile");
 
 struct IfoPass {
   int threads;               // per workgroup: max(256, Nfft / 8)
   int frames_per_wg;         // threads / (Nfft / 8)
   size_t lds;                // static LDS of the capture kernel
   unsigned grid;             // ceil(frames / frames_per_wg)
-  int acc_threads;           // IFO_ACC_THREADS
-  unsigned acc_grid;         // Nfft / IFO_ACC_BINS + 1
+  int acc_threads;           // STUDY_ACC_THREADS
+  unsigned acc_grid;         // Nfft / STUDY_ACC_COLS + 1
   size_t acc_lds;            // static LDS of the accumulating kernel
 };
 
@@ -136,9 +129,9 @@ inline IfoPass ifo_pass(const TxfShape& s, int64_t frames) {
   p.frames_per_wg = ifo_frames_per_wg(s.nfft);
   p.lds = ifo_capture_lds(s.f64 != 0, s.nfft);
   p.grid = (unsigned)((frames + p.frames_per_wg - 1) / p.frames_per_wg);
-  p.acc_threads = IFO_ACC_THREADS;
-  p.acc_grid = (unsigned)(s.nfft / IFO_ACC_BINS) + 1u;
-  p.acc_lds = IFO_ACC_LDS;
+  p.acc_threads = STUDY_ACC_THREADS;
+  p.acc_grid = study_acc_grid(s.nfft, 1);
+  p.acc_lds = STUDY_ACC_LDS;
   return p;
 }
 

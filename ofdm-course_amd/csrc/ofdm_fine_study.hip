@@ -22,6 +22,7 @@
 #include <cmath>
 
 #include "fine_plan.hpp"
+#include "study_accumulate.hpp"
 #include "sync_core.hpp"
 #include "txf_study.hpp"
 
@@ -67,85 +68,18 @@ __global__ __launch_bounds__(FS_THREADS) void fine_capture_kernel(PilotView<T> p
   atomicAdd(o.tg_hist + sync_phase_bin(tg, sto, o.stride), 1ull);
 }
 
-// s + v^2 as a rounded product and a rounded sum, never one fused operation: what a host that rebuilds the sum from the per-frame
-// values computes (the build contracts in the backend, where a pragma does not reach: the product passes through an empty asm)
-__device__ __forceinline__ double fine_add_square(double s, double v) {
-  double p = v * v;
-  asm volatile("" : "+v"(p));
-  return s + p;
-}
-
-// rows / keep [nf][L] of a chunk into the point's sums / dropped / keep_counts [L]; err / phase [nf] into tau_err / phase_sums [2].
-// A workgroup owns FINE_ACC_COLS entries.  The sum of an entry is one chain of additions, so the loads are what can overlap: the
-// four wavefronts stage FINE_ACC_TILE rows at a time in LDS, then wavefront 0 adds the tile to its entries in frame order.  The
-// count is order-free: every thread counts the rows it loaded.  The last workgroup takes the two columns of per-frame scalars.
-__global__ __launch_bounds__(FINE_ACC_THREADS) void fine_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ keep,
-                                                                           const double* __restrict__ err, const double* __restrict__ phase,
-                                                                           int64_t nf, int64_t L, double* __restrict__ sums,
-                                                                           unsigned long long* __restrict__ dropped,
-                                                                           unsigned long long* __restrict__ keep_counts,
-                                                                           double* __restrict__ tau_err, double* __restrict__ phase_sums) {
-  __shared__ double tile[FINE_ACC_TILE][FINE_ACC_COLS];
-  if (blockIdx.x == gridDim.x - 1) {                  // the scalars: FINE_ACC_THREADS frames at a time, thread 0 adds in frame order
-    double* const fe = &tile[0][0];
-    double* const fp = fe + FINE_ACC_THREADS;
-    double e1 = tau_err[0], e2 = tau_err[1], p1 = phase_sums[0], p2 = phase_sums[1];
-    for (int64_t t0 = 0; t0 < nf; t0 += FINE_ACC_THREADS) {
-      const int64_t f = t0 + threadIdx.x;
-      fe[threadIdx.x] = f < nf ? err[f] : 0.0;
-      fp[threadIdx.x] = f < nf ? phase[f] : 0.0;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const int n = (int)(nf - t0 < FINE_ACC_THREADS ? nf - t0 : FINE_ACC_THREADS);
-        for (int q = 0; q < n; ++q) {
-          const double e = fe[q], p = fp[q];
-          if (e - e == 0.0) { e1 += fabs(e); e2 = fine_add_square(e2, e); }
-          if (p - p == 0.0) { p1 += p; p2 = fine_add_square(p2, p); }
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) { tau_err[0] = e1; tau_err[1] = e2; phase_sums[0] = p1; phase_sums[1] = p2; }
-    return;
-  }
-  constexpr int RW = FINE_ACC_THREADS / FINE_ACC_COLS;                       // row groups: 4
-  constexpr int PER = FINE_ACC_TILE / RW;                                    // rows per thread and tile
-  const int c = threadIdx.x % FINE_ACC_COLS, r = threadIdx.x / FINE_ACC_COLS;
-  const int64_t k = (int64_t)blockIdx.x * FINE_ACC_COLS + c;
-  const bool live = k < L;                            // L is no multiple of FINE_ACC_COLS: the last workgroup's tail idles
-  double s = (r == 0 && live) ? sums[k] : 0.0;
-  unsigned long long nd = 0, nk = 0;
-  for (int64_t t0 = 0; t0 < nf; t0 += FINE_ACC_TILE) {
-    double v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int64_t f = t0 + r * PER + i;
-      const bool in = live && f < nf;
-      v[i] = in ? rows[f * L + k] : 0.0;
-      nk += in ? (unsigned long long)keep[f * L + k] : 0ull;
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) tile[r * PER + i][c] = v[i];
-    __syncthreads();
-    if (r == 0) {
-      const int n = (int)(nf - t0 < FINE_ACC_TILE ? nf - t0 : FINE_ACC_TILE);
-      for (int q = 0; q < n; ++q) {
-        const double a = tile[q][c];
-        if (a - a == 0.0) s += a; else ++nd;
-      }
-    }
-    __syncthreads();
-  }
-  unsigned long long* const cnt = (unsigned long long*)&tile[0][0];         // [RW][FINE_ACC_COLS]: the tile is free again
-  cnt[r * FINE_ACC_COLS + c] = nk;
-  __syncthreads();
-  if (r == 0 && live) {
-    unsigned long long t = keep_counts[k];
-    for (int q = 0; q < RW; ++q) t += cnt[q * FINE_ACC_COLS + c];
-    keep_counts[k] = t;
-    sums[k] = s;
-    dropped[k] += nd;
-  }
+// rows / keep [nf][L] of a chunk into the point's sums / dropped / keep_counts [L]; err / phase [nf] into tau_err / phase_sums [2]:
+// the column workgroups of study_accumulate.hpp, a value that is not finite dropped, the keep bytes counted; the tail workgroup
+// takes the two columns of per-frame scalars, the values that are not finite left out.
+__global__ __launch_bounds__(STUDY_ACC_THREADS) void fine_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ keep,
+                                                                            const double* __restrict__ err, const double* __restrict__ phase,
+                                                                            int64_t nf, int64_t L, double* __restrict__ sums,
+                                                                            unsigned long long* __restrict__ dropped,
+                                                                            unsigned long long* __restrict__ keep_counts,
+                                                                            double* __restrict__ tau_err, double* __restrict__ phase_sums) {
+  __shared__ StudyAccTile tile;
+  if (blockIdx.x == gridDim.x - 1) return study_accumulate_scalars<true, true>(tile, err, phase, nf, tau_err, phase_sums);
+  study_accumulate_columns<true, ACC_PEAK_OFF, true>(tile, rows, nullptr, keep, nf, L, sums, dropped, nullptr, keep_counts);
 }
 
 // the capture over nf frames whose pilot rows are `rows` (device memory, the plan's precision)

@@ -140,22 +140,23 @@ struct HestSums {
 };
 
 // rows [nf][nq][ncols] and mask [nf][ncols] of a chunk into the point's sums [nq][ncols] and dropped [ncols].  A workgroup owns
-// HEST_ACC_COLS columns of quantity blockIdx.y.  The sum of a column is one chain of additions, so the loads are what can overlap:
-// the four wavefronts stage HEST_ACC_TILE rows at a time in LDS, then wavefront 0 adds the tile to its columns in frame order.
-__global__ __launch_bounds__(HEST_ACC_THREADS) void hest_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ mask,
+// STUDY_ACC_COLS columns of quantity blockIdx.y.  The sum of a column is one chain of additions, so the loads are what can overlap:
+// the four wavefronts stage STUDY_ACC_TILE rows at a time in LDS, then wavefront 0 adds the tile to its columns in frame order.
+// Its own body, not study_accumulate.hpp's: the exclusion is a mask byte staged beside the double, and the quantities are blockIdx.y.
+__global__ __launch_bounds__(STUDY_ACC_THREADS) void hest_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ mask,
                                                                            int64_t nf, int nq, int ncols, HestSums acc) {
-  __shared__ double tile[HEST_ACC_TILE][HEST_ACC_COLS];
-  __shared__ uint8_t bad[HEST_ACC_TILE][HEST_ACC_COLS];
-  constexpr int RW = HEST_ACC_THREADS / HEST_ACC_COLS;                       // row groups: 4
-  constexpr int PER = HEST_ACC_TILE / RW;                                    // rows per thread and tile
+  __shared__ double tile[STUDY_ACC_TILE][STUDY_ACC_COLS];
+  __shared__ uint8_t bad[STUDY_ACC_TILE][STUDY_ACC_COLS];
+  constexpr int RW = STUDY_ACC_THREADS / STUDY_ACC_COLS;                       // row groups: 4
+  constexpr int PER = STUDY_ACC_TILE / RW;                                    // rows per thread and tile
   const int q = blockIdx.y;
-  const int c = threadIdx.x % HEST_ACC_COLS, r = threadIdx.x / HEST_ACC_COLS;
-  const int k = blockIdx.x * HEST_ACC_COLS + c;
+  const int c = threadIdx.x % STUDY_ACC_COLS, r = threadIdx.x / STUDY_ACC_COLS;
+  const int k = blockIdx.x * STUDY_ACC_COLS + c;
   const bool col = k < ncols;                                                // the last workgroup's columns past the end
   double* const sums = acc.sums[q];
   double s = (r == 0 && col) ? sums[k] : 0.0;
   unsigned long long nd = 0;
-  for (int64_t t0 = 0; t0 < nf; t0 += HEST_ACC_TILE) {
+  for (int64_t t0 = 0; t0 < nf; t0 += STUDY_ACC_TILE) {
     double v[PER];
     uint8_t m[PER];
 #pragma unroll
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(HEST_ACC_THREADS) void hest_accumulate_kernel(const
     for (int i = 0; i < PER; ++i) { tile[r * PER + i][c] = v[i]; bad[r * PER + i][c] = m[i]; }
     __syncthreads();
     if (r == 0) {
-      const int n = (int)(nf - t0 < HEST_ACC_TILE ? nf - t0 : HEST_ACC_TILE);
+      const int n = (int)(nf - t0 < STUDY_ACC_TILE ? nf - t0 : STUDY_ACC_TILE);
       // sixteen rows into registers at a time (independent LDS reads), then the chain on them -- the same additions in the same
       // order; a row that is left out is a select, not a branch (its sum, maybe NaN, is discarded).  The rest one by one.
       int i0 = 0;

@@ -28,6 +28,7 @@
 
 #include "fft_core.hpp"
 #include "ifo_plan.hpp"
+#include "study_accumulate.hpp"
 #include "t4_stream.hpp"
 #include "txf_study.hpp"
 
@@ -135,80 +136,17 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void ifo_capture_kernel(const cx
   o.err[f] = cfo_total_err(o.fo[f], ifo, draw);
 }
 
-// s + v^2 as a rounded product and a rounded sum, never one fused operation: what a host that rebuilds the sum from the per-frame
-// values computes (the build contracts in the backend, where a pragma does not reach: the product passes through an empty asm)
-__device__ __forceinline__ double ifo_add_square(double s, double v) {
-  double p = v * v;
-  asm volatile("" : "+v"(p));
-  return s + p;
-}
-
-// rows / mask [nf][nfft] of a chunk into the point's sums / dropped / above_counts [nfft]; err [nf] into cfo_err [2].
-// A workgroup owns IFO_ACC_BINS bins.  The sum of a bin is one chain of additions, so the loads are what can overlap: the four
-// wavefronts stage IFO_ACC_TILE rows at a time in LDS, then wavefront 0 adds the tile to its bins in frame order.  The count is
-// order-free: every thread counts the rows it loaded.  The last workgroup takes the column of total errors.
-__global__ __launch_bounds__(IFO_ACC_THREADS) void ifo_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ mask,
-                                                                         const double* __restrict__ err, int64_t nf, int nfft,
-                                                                         double* __restrict__ sums, unsigned long long* __restrict__ dropped,
-                                                                         unsigned long long* __restrict__ above_counts,
-                                                                         double* __restrict__ cfo_err) {
-  __shared__ double tile[IFO_ACC_TILE][IFO_ACC_BINS];
-  if (blockIdx.x == gridDim.x - 1) {                  // the errors: IFO_ACC_THREADS frames at a time, thread 0 adds in frame order
-    double* const fe = &tile[0][0];
-    double e1 = cfo_err[0], e2 = cfo_err[1];
-    for (int64_t t0 = 0; t0 < nf; t0 += IFO_ACC_THREADS) {
-      const int64_t f = t0 + threadIdx.x;
-      fe[threadIdx.x] = f < nf ? err[f] : 0.0;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const int n = (int)(nf - t0 < IFO_ACC_THREADS ? nf - t0 : IFO_ACC_THREADS);
-        for (int q = 0; q < n; ++q) {
-          const double e = fe[q];
-          if (e - e == 0.0) { e1 += fabs(e); e2 = ifo_add_square(e2, e); }
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) { cfo_err[0] = e1; cfo_err[1] = e2; }
-    return;
-  }
-  constexpr int RW = IFO_ACC_THREADS / IFO_ACC_BINS;                         // row groups: 4
-  constexpr int PER = IFO_ACC_TILE / RW;                                     // rows per thread and tile
-  const int c = threadIdx.x % IFO_ACC_BINS, r = threadIdx.x / IFO_ACC_BINS;
-  const int64_t k = (int64_t)blockIdx.x * IFO_ACC_BINS + c;                  // nfft is a multiple of IFO_ACC_BINS
-  double s = r == 0 ? sums[k] : 0.0;
-  unsigned long long nd = 0, na = 0;
-  for (int64_t t0 = 0; t0 < nf; t0 += IFO_ACC_TILE) {
-    double v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int64_t f = t0 + r * PER + i;
-      const bool in = f < nf;
-      v[i] = in ? rows[f * nfft + k] : 0.0;
-      na += in ? (unsigned long long)mask[f * nfft + k] : 0ull;
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) tile[r * PER + i][c] = v[i];
-    __syncthreads();
-    if (r == 0) {
-      const int n = (int)(nf - t0 < IFO_ACC_TILE ? nf - t0 : IFO_ACC_TILE);
-      for (int q = 0; q < n; ++q) {
-        const double a = tile[q][c];
-        if (a - a == 0.0) s += a; else ++nd;
-      }
-    }
-    __syncthreads();
-  }
-  unsigned long long* const cnt = (unsigned long long*)&tile[0][0];         // [RW][IFO_ACC_BINS]: the tile is free again
-  cnt[r * IFO_ACC_BINS + c] = na;
-  __syncthreads();
-  if (r == 0) {
-    unsigned long long t = above_counts[k];
-    for (int q = 0; q < RW; ++q) t += cnt[q * IFO_ACC_BINS + c];
-    above_counts[k] = t;
-    sums[k] = s;
-    dropped[k] += nd;
-  }
+// rows / mask [nf][nfft] of a chunk into the point's sums / dropped / above_counts [nfft]; err [nf] into cfo_err [2]: the column
+// workgroups of study_accumulate.hpp, a value that is not finite dropped, the mask bytes counted; the tail workgroup takes the
+// column of total errors, a frame without a line (NaN) left out.
+__global__ __launch_bounds__(STUDY_ACC_THREADS) void ifo_accumulate_kernel(const double* __restrict__ rows, const uint8_t* __restrict__ mask,
+                                                                           const double* __restrict__ err, int64_t nf, int nfft,
+                                                                           double* __restrict__ sums, unsigned long long* __restrict__ dropped,
+                                                                           unsigned long long* __restrict__ above_counts,
+                                                                           double* __restrict__ cfo_err) {
+  __shared__ StudyAccTile tile;
+  if (blockIdx.x == gridDim.x - 1) return study_accumulate_scalars<true, false>(tile, err, nullptr, nf, cfo_err, nullptr);
+  study_accumulate_columns<true, ACC_PEAK_OFF, true>(tile, rows, nullptr, mask, nf, nfft, sums, dropped, nullptr, above_counts);
 }
 
 template <typename T, int N>

@@ -21,6 +21,7 @@
 
 #include "fft_core.hpp"
 #include "spectrum_plan.hpp"
+#include "study_accumulate.hpp"
 #include "txf_study.hpp"
 
 namespace ofdm {
@@ -70,46 +71,14 @@ __global__ __launch_bounds__(fft_wg_threads(N)) void spectrum_kernel(const cx<T>
   }
 }
 
-// rows [nf][nfft] (and peak_rows, optional) of a chunk into the point's accumulators sums [nfft] (and peak [nfft])
-// A workgroup owns SPEC_ACC_BINS bins.  The sum of a bin is one chain of additions, so the loads are what can overlap: the four
-// wavefronts stage SPEC_ACC_TILE rows at a time in LDS (sixteen loads in flight per thread, 512 bytes per wavefront and row), then
-// wavefront 0 adds the tile to its bins in frame order.  The peak is order-free: every thread folds the rows it loaded.
-__global__ __launch_bounds__(SPEC_ACC_THREADS) void spectrum_accumulate_kernel(const double* __restrict__ rows,
-                                                                               const double* __restrict__ peak_rows, int64_t nf,
-                                                                               int nfft, double* __restrict__ sums,
-                                                                               double* __restrict__ peak) {
-  constexpr int PER = SPEC_ACC_TILE / (SPEC_ACC_THREADS / SPEC_ACC_BINS);      // rows per thread and tile
-  __shared__ double tile[SPEC_ACC_TILE][SPEC_ACC_BINS];
-  const int c = threadIdx.x % SPEC_ACC_BINS, r = threadIdx.x / SPEC_ACC_BINS;
-  const int k = blockIdx.x * SPEC_ACC_BINS + c;                                // nfft is a multiple of SPEC_ACC_BINS
-  double s = r == 0 ? sums[k] : 0.0, m = 0.0;
-  for (int64_t t0 = 0; t0 < nf; t0 += SPEC_ACC_TILE) {
-    double v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int64_t f = t0 + r * PER + i;
-      v[i] = f < nf ? rows[f * nfft + k] : 0.0;
-      if (peak && f < nf) m = fmax(m, peak_rows[f * nfft + k]);
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) tile[r * PER + i][c] = v[i];
-    __syncthreads();
-    if (r == 0) {
-      const int n = (int)(nf - t0 < SPEC_ACC_TILE ? nf - t0 : SPEC_ACC_TILE);
-      for (int q = 0; q < n; ++q) s += tile[q][c];
-    }
-    __syncthreads();
-  }
-  if (r == 0) sums[k] = s;
-  if (peak) {
-    tile[r][c] = m;
-    __syncthreads();
-    if (r == 0) {
-      double pm = peak[k];
-      for (int q = 0; q < SPEC_ACC_THREADS / SPEC_ACC_BINS; ++q) pm = fmax(pm, tile[q][c]);
-      peak[k] = pm;
-    }
-  }
+// rows [nf][nfft] (and peak_rows, optional) of a chunk into the point's accumulators sums [nfft] (and peak [nfft]): the column
+// workgroups of study_accumulate.hpp, every value added, the peak folded over peak_rows; no scalars, so no tail workgroup.
+__global__ __launch_bounds__(STUDY_ACC_THREADS) void spectrum_accumulate_kernel(const double* __restrict__ rows,
+                                                                                const double* __restrict__ peak_rows, int64_t nf,
+                                                                                int nfft, double* __restrict__ sums,
+                                                                                double* __restrict__ peak) {
+  __shared__ StudyAccTile tile;
+  study_accumulate_columns<false, ACC_PEAK_SECOND, false>(tile, rows, peak_rows, nullptr, nf, nfft, sums, nullptr, peak, nullptr);
 }
 
 template <typename T, int N>

@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "sync_core.hpp"
+#include "study_accumulate.hpp"
 #include "sync_plan.hpp"
 #include "txf_study.hpp"
 
@@ -140,80 +141,16 @@ __global__ __launch_bounds__(ACF_THREADS) void sync_capture_kernel(const cx<T>* 
   }
 }
 
-// s + e^2 as a rounded product and a rounded sum, never one fused operation: what a host that rebuilds the sum from the per-frame
-// errors computes.  The build contracts in the backend (-ffp-contract=fast), where a pragma on the statement does not reach, so
-// the product passes through an empty asm statement that the combiner cannot look through.
-__device__ __forceinline__ double add_square(double s, double e) {
-  double p = e * e;
-  asm volatile("" : "+v"(p));
-  return s + p;
-}
-
-// rows [nf][n_out] of a chunk into the point's accumulators sums / dropped [n_out] (and peak [n_out]); err [nf] into ffo [2].
-// A workgroup owns SYNC_ACC_LAGS lags.  The sum of a lag is one chain of additions, so the loads are what can overlap: the four
-// wavefronts stage SYNC_ACC_TILE rows at a time in LDS, then wavefront 0 adds the tile to its lags in frame order.  The peak is
-// order-free: every thread folds the rows it loaded.  The last workgroup does the same for the one column of wrapped errors.
-__global__ __launch_bounds__(SYNC_ACC_THREADS) void sync_accumulate_kernel(const double* __restrict__ rows, const double* __restrict__ err,
-                                                                           int64_t nf, int64_t n_out, double* __restrict__ sums,
-                                                                           unsigned long long* __restrict__ dropped,
-                                                                           double* __restrict__ peak, double* __restrict__ ffo) {
-  __shared__ double tile[SYNC_ACC_TILE][SYNC_ACC_LAGS];
-  if (blockIdx.x == gridDim.x - 1) {                  // the wrapped errors: SYNC_ACC_THREADS at a time, thread 0 adds in frame order
-    double* const flat = &tile[0][0];
-    double s1 = ffo[0], s2 = ffo[1];
-    for (int64_t t0 = 0; t0 < nf; t0 += SYNC_ACC_THREADS) {
-      const int64_t f = t0 + threadIdx.x;
-      flat[threadIdx.x] = f < nf ? err[f] : 0.0;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        const int n = (int)(nf - t0 < SYNC_ACC_THREADS ? nf - t0 : SYNC_ACC_THREADS);
-        for (int q = 0; q < n; ++q) {
-          const double e = flat[q];
-          s1 += fabs(e);
-          s2 = add_square(s2, e);
-        }
-      }
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) { ffo[0] = s1; ffo[1] = s2; }
-    return;
-  }
-  constexpr int PER = SYNC_ACC_TILE / (SYNC_ACC_THREADS / SYNC_ACC_LAGS);      // rows per thread and tile
-  const int c = threadIdx.x % SYNC_ACC_LAGS, r = threadIdx.x / SYNC_ACC_LAGS;
-  const int64_t k = (int64_t)blockIdx.x * SYNC_ACC_LAGS + c;
-  const bool live = k < n_out;                        // n_out is no multiple of SYNC_ACC_LAGS: the last workgroup's tail idles
-  double s = (r == 0 && live) ? sums[k] : 0.0, m = 0.0;
-  unsigned long long nd = 0;
-  for (int64_t t0 = 0; t0 < nf; t0 += SYNC_ACC_TILE) {
-    double v[PER];
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int64_t f = t0 + r * PER + i;
-      v[i] = (live && f < nf) ? rows[f * n_out + k] : 0.0;
-      m = fmax(m, v[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < PER; ++i) tile[r * PER + i][c] = v[i];
-    __syncthreads();
-    if (r == 0) {
-      const int n = (int)(nf - t0 < SYNC_ACC_TILE ? nf - t0 : SYNC_ACC_TILE);
-      for (int q = 0; q < n; ++q) {
-        const double a = tile[q][c];
-        if (isfinite(a)) s += a; else ++nd;
-      }
-    }
-    __syncthreads();
-  }
-  if (r == 0 && live) { sums[k] = s; dropped[k] += nd; }
-  if (peak) {
-    tile[r][c] = m;
-    __syncthreads();
-    if (r == 0 && live) {
-      double pm = peak[k];
-      for (int q = 0; q < SYNC_ACC_THREADS / SYNC_ACC_LAGS; ++q) pm = fmax(pm, tile[q][c]);
-      peak[k] = pm;
-    }
-  }
+// rows [nf][n_out] of a chunk into the point's accumulators sums / dropped [n_out] (and peak [n_out]); err [nf] into ffo [2]: the
+// column workgroups of study_accumulate.hpp, a value that is not finite dropped, the peak folded over the same rows; the tail
+// workgroup adds every wrapped error, finite or not.
+__global__ __launch_bounds__(STUDY_ACC_THREADS) void sync_accumulate_kernel(const double* __restrict__ rows, const double* __restrict__ err,
+                                                                            int64_t nf, int64_t n_out, double* __restrict__ sums,
+                                                                            unsigned long long* __restrict__ dropped,
+                                                                            double* __restrict__ peak, double* __restrict__ ffo) {
+  __shared__ StudyAccTile tile;
+  if (blockIdx.x == gridDim.x - 1) return study_accumulate_scalars<false, false>(tile, err, nullptr, nf, ffo, nullptr);
+  study_accumulate_columns<true, ACC_PEAK_ROWS, false>(tile, rows, nullptr, nullptr, nf, n_out, sums, dropped, peak, nullptr);
 }
 
 // the capture over nf frames at rx (device memory) in the plan's precision; a launch holds at most 65535 frames

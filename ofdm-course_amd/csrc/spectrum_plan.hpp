@@ -74,19 +74,14 @@ inline int64_t spectrum_chunk(const TxfShape& s, const TxfUse& u, int64_t frames
 
 // ---- the launch shape.  spectrum_kernel: a transform of Nfft / 8 threads per frame, every window of the frame in turn;
 // workgroups of at least 256 threads hold 256 / (Nfft / 8) frames (fft_core.hpp's rule, restated; ofdm_spectrum.hip asserts it).
-// spectrum_accumulate_kernel: workgroups of SPEC_ACC_THREADS threads own SPEC_ACC_BINS bins each (Nfft is a multiple of 64) and stage
-// SPEC_ACC_TILE rows at a time in LDS.
-constexpr int SPEC_ACC_THREADS = 256;
-constexpr int SPEC_ACC_BINS = 64;
-constexpr int SPEC_ACC_TILE = 64;
-
+// spectrum_accumulate_kernel: the studies' accumulate launch (txf_plan.hpp: STUDY_ACC_*) over the Nfft bins, no tail workgroup.
 struct SpecPass {
   int threads;               // per workgroup: max(256, Nfft / 8)
   int frames_per_wg;         // threads / (Nfft / 8)
   size_t lds;                // static LDS: frames_per_wg transforms of Nfft + Nfft / 8 + 8 padded elements
   unsigned grid;             // ceil(frames / frames_per_wg)
-  int acc_threads;           // SPEC_ACC_THREADS
-  unsigned acc_grid;         // Nfft / SPEC_ACC_BINS
+  int acc_threads;           // STUDY_ACC_THREADS
+  unsigned acc_grid;         // Nfft / STUDY_ACC_COLS
 };
 
 inline SpecPass spectrum_pass(const TxfShape& s, int64_t frames) {
@@ -95,8 +90,8 @@ inline SpecPass spectrum_pass(const TxfShape& s, int64_t frames) {
   p.frames_per_wg = p.threads / (s.nfft / 8);
   p.lds = (size_t)(s.f64 ? 16 : 8) * p.frames_per_wg * (size_t)(s.nfft + s.nfft / 8 + 8);
   p.grid = (unsigned)((frames + p.frames_per_wg - 1) / p.frames_per_wg);
-  p.acc_threads = SPEC_ACC_THREADS;
-  p.acc_grid = (unsigned)(s.nfft / SPEC_ACC_BINS);
+  p.acc_threads = STUDY_ACC_THREADS;
+  p.acc_grid = study_acc_grid(s.nfft, 0);
   return p;
 }
 

@@ -30,7 +30,6 @@ namespace ofdm {
 constexpr int SYNC_ACF_TILE = 1024;
 constexpr int SYNC_ACF_THREADS = 256;
 constexpr int SYNC_ACF_MAXW = 1024;
-constexpr size_t SYNC_LDS_LIMIT = 150 << 10;         // what every stage of this library keeps to
 
 // the refusals of the two entries: a TXF_REFUSE_* of txf_plan.hpp, or one of their own
 enum { SYNC_REFUSE_FRAMES = TXF_REFUSALS, SYNC_REFUSE_BOTH, SYNC_REFUSE_WIDTH, SYNC_REFUSE_SHORT, SYNC_REFUSE_OUTPUT, SYNC_REFUSALS };
@@ -92,12 +91,8 @@ inline int64_t sync_chunk(const TxfShape& s, const TxfUse& u, int64_t frames_per
 
 // ---- the launch shape.  sync_capture_kernel: one workgroup of SYNC_ACF_THREADS threads per frame; its dynamic LDS is the prefix
 // table of acf_tile, SYNC_ACF_TILE + WidthWindow + 1 entries of four sums in the plan's precision, and behind it one tile of rho.
-// sync_accumulate_kernel: workgroups of SYNC_ACC_THREADS threads own SYNC_ACC_LAGS lags each and stage SYNC_ACC_TILE rows at a time in
-// LDS; one more workgroup, the last, sums the chunk's wrapped errors.
-constexpr int SYNC_ACC_THREADS = 256;
-constexpr int SYNC_ACC_LAGS = 64;
-constexpr int SYNC_ACC_TILE = 64;
-
+// sync_accumulate_kernel: the studies' accumulate launch (txf_plan.hpp: STUDY_ACC_*) over the n_out lags, with the tail workgroup for
+// the chunk's wrapped errors.
 constexpr size_t sync_table_bytes(bool f64, int width) { return (f64 ? 32 : 16) * (size_t)(SYNC_ACF_TILE + width + 1); }
 constexpr size_t sync_capture_lds(bool f64, int width) { return sync_table_bytes(f64, width) + (f64 ? 16 : 8) * (size_t)SYNC_ACF_TILE; }
 
@@ -110,8 +105,8 @@ struct SyncPass {
   int threads;               // SYNC_ACF_THREADS
   unsigned grid;             // frames: one workgroup each (a chunk holds at most 65535)
   size_t lds;                // dynamic LDS of the capture kernel
-  int acc_threads;           // SYNC_ACC_THREADS
-  unsigned acc_grid;         // ceil(n_out / SYNC_ACC_LAGS) + 1
+  int acc_threads;           // STUDY_ACC_THREADS
+  unsigned acc_grid;         // ceil(n_out / STUDY_ACC_COLS) + 1
 };
 
 inline SyncPass sync_pass(const TxfShape& s, int64_t width, int64_t frames) {
@@ -119,8 +114,8 @@ inline SyncPass sync_pass(const TxfShape& s, int64_t width, int64_t frames) {
   p.threads = SYNC_ACF_THREADS;
   p.grid = (unsigned)frames;
   p.lds = sync_capture_lds(s.f64 != 0, (int)width);
-  p.acc_threads = SYNC_ACC_THREADS;
-  p.acc_grid = (unsigned)((sync_n_out(s, width) + SYNC_ACC_LAGS - 1) / SYNC_ACC_LAGS) + 1u;
+  p.acc_threads = STUDY_ACC_THREADS;
+  p.acc_grid = study_acc_grid(sync_n_out(s, width), 1);
   return p;
 }
 

@@ -198,6 +198,21 @@ inline int64_t txf_chunk_task4(const TxfShape& s, const TxfUse& u, int64_t n_fra
   return txf_chunk(s, u, n_frames, user_cap, 2 * TXF_WS_BUDGET, t4_frame_bytes(t4, s.frame_words) + (frame_mer ? 16 : 0));
 }
 
+// ---- the accumulate stage of the studies (study_accumulate.hpp; hest_accumulate_kernel keeps the same shape): workgroups of
+// STUDY_ACC_THREADS threads own STUDY_ACC_COLS columns of the chunk's rows each and stage STUDY_ACC_TILE rows at a time in LDS; where
+// a study has per-frame scalars to sum, one more workgroup, the last, takes them.
+constexpr size_t SYNC_LDS_LIMIT = 150 << 10;         // what every stage of this library keeps to
+constexpr int STUDY_ACC_THREADS = 256;
+constexpr int STUDY_ACC_COLS = 64;
+constexpr int STUDY_ACC_TILE = 64;
+constexpr size_t STUDY_ACC_LDS = sizeof(double) * STUDY_ACC_TILE * STUDY_ACC_COLS;
+
+static_assert(STUDY_ACC_THREADS % STUDY_ACC_COLS == 0 && STUDY_ACC_TILE % (STUDY_ACC_THREADS / STUDY_ACC_COLS) == 0, "rows per thread and tile");
+static_assert(STUDY_ACC_LDS == 32768 && STUDY_ACC_LDS <= SYNC_LDS_LIMIT, "the accumulating kernels' LDS");
+
+// the workgroups of an accumulate launch: ceil(cols / STUDY_ACC_COLS), and `tail` (0 or 1) more for the per-frame scalars
+inline unsigned study_acc_grid(int64_t cols, unsigned tail) { return (unsigned)((cols + STUDY_ACC_COLS - 1) / STUDY_ACC_COLS) + tail; }
+
 // ---- the channel pass of a chunk of nf frames: one workgroup per (segment of TXF_SEG samples, frame)
 enum { TXF_PASS_PLAIN, TXF_PASS_IMP, TXF_PASS_FADE, TXF_PASS_IMP_FADE };
 

@@ -108,6 +108,21 @@ def _study_args(plan, cfg, oracle, kind):
             "all": dict(fading=([0, 5], [1.0, 0.3]), Time_Delay=7, Freq_Shift="random", Register=REG)}[kind]
 
 
+def _rebuild(plan, ofdm, cfg, first, nw, snr, seed, fpp, f0, kw):
+    """One point of the study from the per-frame call: the power rows, their left-to-right float64 sum from 0, and the np.fmax
+    (from 0) over the frames and windows of the single-window power rows."""
+    rx = np.asarray(plan.tx_frames_fused(fpp, SNR=snr, seed=seed, frame0=f0, **kw)["rx"])
+    rows = ofdm.rx_spectrum(plan, rx, first=first, n_windows=nw, want_power=True)["power"]
+    acc = np.zeros(cfg.Nfft, np.float64)
+    for f in range(fpp):
+        acc = acc + rows[f]
+    pk = np.zeros(cfg.Nfft, np.float64)
+    for w in range(nw):
+        one = ofdm.rx_spectrum(plan, rx, first=first + w * (cfg.Nfft + cfg.T_guard), n_windows=1, want_power=True)["power"]
+        pk = np.fmax(pk, np.fmax.reduce(one, axis=0))
+    return dict(frame_power=rows, power_sums=acc, peak=pk)
+
+
 @pytest.mark.parametrize("precision", ["fp64", "fp32"])
 @pytest.mark.parametrize("kind", ["h", "clean", "fading", "random", "register", "all"])
 def test_study_equals_the_per_frame_call_bitwise(ofdm, oracle, kind, precision):
@@ -123,20 +138,11 @@ def test_study_equals_the_per_frame_call_bitwise(ofdm, oracle, kind, precision):
     st = plan.spectrum_study(snrs, fpp, seeds=seeds, frame0=f0, first=first, n_windows=nw, want_peak=True, want_frame_power=True,
                              **kw)
     assert st["power_sums"].shape == (2, cfg.Nfft) and st["frame_power"].shape == (2, fpp, cfg.Nfft)
-    stride = cfg.Nfft + cfg.T_guard
     for p in range(2):
-        rx = np.asarray(plan.tx_frames_fused(fpp, SNR=snrs[p], seed=seeds[p], frame0=f0, **kw)["rx"])
-        rows = ofdm.rx_spectrum(plan, rx, first=first, n_windows=nw, want_power=True)["power"]
-        assert np.array_equal(st["frame_power"][p], rows)
-        acc = np.zeros(cfg.Nfft, np.float64)
-        for f in range(fpp):
-            acc = acc + st["frame_power"][p, f]
-        assert np.array_equal(st["power_sums"][p], acc)
-        pk = np.zeros(cfg.Nfft, np.float64)
-        for w in range(nw):
-            one = ofdm.rx_spectrum(plan, rx, first=first + w * stride, n_windows=1, want_power=True)["power"]
-            pk = np.fmax(pk, np.fmax.reduce(one, axis=0))
-        assert np.array_equal(st["peak"][p], pk)
+        want = _rebuild(plan, ofdm, cfg, first, nw, snrs[p], seeds[p], fpp, f0, kw)
+        assert np.array_equal(st["frame_power"][p], want["frame_power"])
+        assert np.array_equal(st["power_sums"][p], want["power_sums"])
+        assert np.array_equal(st["peak"][p], want["peak"])
         assert np.array_equal(st["mean_power"][p], st["power_sums"][p] / (fpp * nw))
         assert np.array_equal(st["amp_rms"][p], np.sqrt(st["mean_power"][p]))
     assert not np.array_equal(st["power_sums"][0], st["power_sums"][1])
