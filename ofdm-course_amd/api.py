@@ -816,19 +816,51 @@ class RxPlan:
 
     @staticmethod
     def _points(SNRs, seeds, seed, what):
-        """The SNR row of a sweep and one Philox key per point (`seed` for every point when `seeds` is None)."""
+        """The SNR row of a sweep and one Philox key per point (`seed` for every point when `seeds` is None), as arrays (the
+        caller holds them until the call has returned) and as the two pointers the C entries take."""
         snr = np.ascontiguousarray(np.asarray(SNRs, dtype=np.float64).ravel())
         sd = np.full(snr.size, int(seed), dtype=np.uint64) if seeds is None else \
             np.ascontiguousarray(np.asarray(seeds, dtype=np.uint64).ravel())
         if sd.size != snr.size:
             raise OfdmError(f"{what}: seeds must have one entry per SNR point")
-        return snr, sd
+        return snr, sd, snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p)
+
+    def _sweep_channel(self, h, fading, Register, what):
+        """The channel and the register of a BER sweep: fading=(delays, powers) or h (both: refused here), then Register ->
+        (kept arrays, (h, h_len), (tap_delay, tap_power, n_taps), scr_reg15) as the C entries take them."""
+        if fading is not None:
+            keep_f, pdl, ppw, nt = self._fading_args(h, fading, what)
+            keep, _, _, pr = self._fused_args(None, Register, what)
+            return keep_f + keep, (None, 0), (pdl, ppw, nt), pr
+        keep, ph, nh, pr = self._fused_args(h, Register, what)
+        return keep, (ph, nh), (None, None, 0), pr
+
+    @staticmethod
+    def _density_args(density, what):
+        """density=dict(bins=, half_width=, skip=0) of a sweep -> (bins, half_width, skip)."""
+        try:
+            extra = set(density) - {"bins", "half_width", "skip"}
+            bins, half_width, skip = int(density["bins"]), float(density["half_width"]), int(density.get("skip", 0))
+        except (TypeError, KeyError, ValueError, AttributeError):
+            raise OfdmError(f"{what}: density must be dict(bins=, half_width=, skip=0)") from None
+        if extra:
+            raise OfdmError(f"{what}: unknown density keys {sorted(extra)}")
+        return bins, half_width, skip
+
+    def _density_outputs(self, device, n, bins):
+        """The density grids [n, bins, bins] and dropped counters [n] of a sweep -> (their two pointers, the result entries:
+        int64 views of the numpy arrays -- a count of 2^63 is out of reach -- the device tensors as they are)."""
+        nb = bins if bins > 0 else 0                              # (a bad count is the library's refusal)
+        (dens, drop), dptrs, _ = self._outputs(device, ((n, nb, nb), np.uint64), ((n,), np.uint64))
+        if device is None:
+            dens, drop = dens.view(np.int64), drop.view(np.int64)
+        return dptrs, dict(density=dens, density_dropped=drop)
 
     def _study_args(self, what, SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift):
         """The generator arguments every study entry takes, as its C signature groups them -> (keep, n_points, chan = (h, h_len,
         tap_delay, tap_power, n_taps), imp = (sto_mode, sto_value, cfo_mode, cfo_value), scr_reg15, pts = (snr_db, seeds,
         n_points)).  keep: the arrays behind the pointers; the caller holds it until the call has returned."""
-        snr, sd = self._points(SNRs, seeds, seed, what)
+        snr, sd, psnr, psd = self._points(SNRs, seeds, seed, what)
         keep, ph, nh, pr = self._fused_args(h, Register, what)
         pdl, ppw, nt = None, None, 0
         if fading is not None:                                   # (with h too: the library's refusal)
@@ -836,8 +868,7 @@ class RxPlan:
             keep += keep_f
         sm, sv = _imp_mode(Time_Delay, what)
         cm, cv = _imp_mode(Freq_Shift, what)
-        return (keep + (snr, sd), snr.size, (ph, nh, pdl, ppw, nt), (sm, int(sv), cm, float(cv)), pr,
-                (snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), snr.size))
+        return keep + (snr, sd), snr.size, (ph, nh, pdl, ppw, nt), (sm, int(sv), cm, float(cv)), pr, (psnr, psd, snr.size)
 
     @staticmethod
     def _counts(device, count, *tables):
@@ -1271,14 +1302,8 @@ class RxPlan:
         if (want_nmse or want_frame_nmse) and fading is None:
             raise OfdmError("ber_sweep: want_nmse / want_frame_nmse need fading")
         if density is not None:
-            try:
-                extra = set(density) - {"bins", "half_width", "skip"}
-                bins, half_width, skip = int(density["bins"]), float(density["half_width"]), int(density.get("skip", 0))
-            except (TypeError, KeyError, ValueError, AttributeError):
-                raise OfdmError("ber_sweep: density must be dict(bins=, half_width=, skip=0)") from None
-            if extra:
-                raise OfdmError(f"ber_sweep: unknown density keys {sorted(extra)}")
-        snr, sd = self._points(SNRs, seeds, seed, "ber_sweep")
+            bins, half_width, skip = self._density_args(density, "ber_sweep")
+        snr, sd, psnr, psd = self._points(SNRs, seeds, seed, "ber_sweep")
         n, fpp = snr.size, int(frames_per_point)
         (err, fe, ms, fm, ns, fn), ptrs, flags = self._outputs(
             device, ((n,), np.uint64), ((n, fpp), np.uint32) if want_frame_errors else None,
@@ -1286,31 +1311,16 @@ class RxPlan:
             ((n,), np.float64) if want_nmse else None, ((n, fpp), np.float64) if want_frame_nmse else None)
         own = {}
         if density is not None:
-            nb = bins if bins > 0 else 0                          # (a bad count is the library's refusal)
-            (dens, drop), dptrs, _ = self._outputs(device, ((n, nb, nb), np.uint64), ((n,), np.uint64))
-            if fading is not None:
-                keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep")
-                keep, ph, nh, pr = self._fused_args(None, Register, "ber_sweep")
-            else:
-                pdl, ppw, nt = None, None, 0
-                keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
-            L.check(self.lib.ofdm_ber_sweep_task5_scope(self.handle, pdl, ppw, nt, snr.ctypes.data_as(C.c_void_p),
-                                                        sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                        int(max_frames_per_chunk), *ptrs, ph, nh, *dptrs, bins, half_width,
-                                                        skip, flags), "ber_sweep_task5_scope")
-            own = dict(density=dens if device is not None else dens.view(np.int64),      # int64 views: a count of 2^63 is out of reach
-                       density_dropped=drop if device is not None else drop.view(np.int64))
+            dptrs, own = self._density_outputs(device, n, bins)
+        keep, chan, taps, pr = self._sweep_channel(h, fading, Register, "ber_sweep")
+        pts = (psnr, psd, n, fpp, int(frame0), pr, int(max_frames_per_chunk))
+        if density is not None:
+            L.check(self.lib.ofdm_ber_sweep_task5_scope(self.handle, *taps, *pts, *ptrs, *chan, *dptrs, bins, half_width, skip,
+                                                        flags), "ber_sweep_task5_scope")
         elif fading is not None:
-            keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep")
-            keep, _, _, pr = self._fused_args(None, Register, "ber_sweep")
-            L.check(self.lib.ofdm_ber_sweep_task5_fading(self.handle, pdl, ppw, nt, snr.ctypes.data_as(C.c_void_p),
-                                                         sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                         int(max_frames_per_chunk), *ptrs, flags), "ber_sweep_task5_fading")
+            L.check(self.lib.ofdm_ber_sweep_task5_fading(self.handle, *taps, *pts, *ptrs, flags), "ber_sweep_task5_fading")
         else:
-            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep")
-            L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, ph, nh, snr.ctypes.data_as(C.c_void_p),
-                                                     sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0), pr,
-                                                     int(max_frames_per_chunk), *ptrs[:4], flags),
+            L.check(self.lib.ofdm_ber_sweep_task5_ex(self.handle, *chan, *pts, *ptrs[:4], flags),
                     "ber_sweep_task5_ex" if want_mer else "ber_sweep_task5")
         return self._sweep_result(device, err, fpp, own, ns, fn, fe, ms, fm)
 
@@ -1369,14 +1379,8 @@ class RxPlan:
         if density is not None:
             if fading is not None:
                 raise OfdmError("ber_sweep_task4: density is not available with fading")
-            try:
-                extra = set(density) - {"bins", "half_width", "skip"}
-                bins, half_width, skip = int(density["bins"]), float(density["half_width"]), int(density.get("skip", 0))
-            except (TypeError, KeyError, ValueError, AttributeError):
-                raise OfdmError("ber_sweep_task4: density must be dict(bins=, half_width=, skip=0)") from None
-            if extra:
-                raise OfdmError(f"ber_sweep_task4: unknown density keys {sorted(extra)}")
-        snr, sd = self._points(SNRs, seeds, seed, "ber_sweep_task4")
+            bins, half_width, skip = self._density_args(density, "ber_sweep_task4")
+        snr, sd, psnr, psd = self._points(SNRs, seeds, seed, "ber_sweep_task4")
         n, fpp = snr.size, int(frames_per_point)
         sm, sv = _imp_mode(Time_Delay, "ber_sweep_task4")
         cm, cv = _imp_mode(Freq_Shift, "ber_sweep_task4")
@@ -1388,37 +1392,23 @@ class RxPlan:
             ((n, fpp), np.uint32) if want_frame_errors else None, ((n, 2), np.float64) if want_mer else None,
             ((n, fpp, 2), np.float64) if want_mer and want_frame_mer else None, ((n,), np.float64) if want_nmse else None,
             ((n, fpp), np.float64) if want_frame_nmse else None)
-        tail = (snr.ctypes.data_as(C.c_void_p), sd.ctypes.data_as(C.c_void_p), n, fpp, int(frame0))
-        mer = (int(mer_skip) if want_mer else 0, *ptrs[4:6])
-        dens = None
+        grids = {}
         if density is not None:
-            nb = bins if bins > 0 else 0                          # (a bad count is the library's refusal)
-            (dens, drop), dptrs, _ = self._outputs(device, ((n, nb, nb), np.uint64), ((n,), np.uint64))
-            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-            L.check(self.lib.ofdm_ber_sweep_task4_scope(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
-                                                        int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer,
-                                                        *ptrs[6:], *dptrs, bins, half_width, skip, flags),
+            dptrs, grids = self._density_outputs(device, n, bins)
+        keep, chan, taps, pr = self._sweep_channel(h, fading, Register, "ber_sweep_task4")
+        # what every entry takes behind its channel: up to frame_mer_sums_out, the arguments of ofdm_ber_sweep_task4_ex
+        head = (self.handle, *(chan if fading is None else taps), sm, int(sv), cm, float(cv), int(td), int(fd), int(md), psnr, psd,
+                n, fpp, int(frame0), pr, int(max_frames_per_chunk), *ptrs[:4], int(mer_skip) if want_mer else 0, *ptrs[4:6])
+        if density is not None:
+            L.check(self.lib.ofdm_ber_sweep_task4_scope(*head, *ptrs[6:], *dptrs, bins, half_width, skip, flags),
                     "ber_sweep_task4_scope")
         elif fading is not None:
-            keep_f, pdl, ppw, nt = self._fading_args(h, fading, "ber_sweep_task4")
-            keep, _, _, pr = self._fused_args(None, Register, "ber_sweep_task4")
-            L.check(self.lib.ofdm_ber_sweep_task4_fading(self.handle, pdl, ppw, nt, sm, int(sv), cm, float(cv), int(td),
-                                                         int(fd), int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4],
-                                                         *mer, *ptrs[6:], flags), "ber_sweep_task4_fading")
+            L.check(self.lib.ofdm_ber_sweep_task4_fading(*head, *ptrs[6:], flags), "ber_sweep_task4_fading")
         elif want_nmse:
-            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-            L.check(self.lib.ofdm_ber_sweep_task4_nmse(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
-                                                       int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer,
-                                                       *ptrs[6:], flags), "ber_sweep_task4_nmse")
+            L.check(self.lib.ofdm_ber_sweep_task4_nmse(*head, *ptrs[6:], flags), "ber_sweep_task4_nmse")
         else:
-            keep, ph, nh, pr = self._fused_args(h, Register, "ber_sweep_task4")
-            L.check(self.lib.ofdm_ber_sweep_task4_ex(self.handle, ph, nh, sm, int(sv), cm, float(cv), int(td), int(fd),
-                                                     int(md), *tail, pr, int(max_frames_per_chunk), *ptrs[:4], *mer, flags),
-                    "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
-        own = dict(status_counts=stc.astype(np.int64) if device is None else stc, cfo_abs_err=cae)
-        if dens is not None:                                      # int64 views: a count of 2^63 is out of reach
-            own.update(density=dens if device is not None else dens.view(np.int64),
-                       density_dropped=drop if device is not None else drop.view(np.int64))
+            L.check(self.lib.ofdm_ber_sweep_task4_ex(*head, flags), "ber_sweep_task4_ex" if want_mer else "ber_sweep_task4")
+        own = dict(status_counts=stc.astype(np.int64) if device is None else stc, cfo_abs_err=cae, **grids)
         return self._sweep_result(device, err, fpp, own, ns, fn, fe, ms, fm)
 
     def set_timing(self, enable=True):
@@ -1462,45 +1452,60 @@ def rx_chain_task5(plan: RxPlan, rx, ref_bits_packed=None, want_h=False, want_in
     equalised points get_payload(.)(:) of each frame from 0-based index first on -- what the demapper slices and MER_func sums;
     (nd, 332) is the scatterplot(RX_IQ(nd+1 : nd+332)) of T5/Main_model_Task_5.m:248-251.  The other outputs are those of the
     call with want_mer."""
+    call, nfr, iq, bits, errors, pbits = _rx_chain_front("rx_chain_task5", plan, rx, ref_bits_packed, iq_window)
+    H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
+    idx, pidx = (call._out((plan.taps, nfr), np.int32, torch.int32 if call.dev else None) if want_index else (None, None))
+    return _rx_chain_tail("rx_chain_task5", plan, call, rx, nfr, dict(bits=bits, errors=errors, H=H, index=idx),
+                          (*pbits, pH, pidx), want_mer, iq)
+
+
+def _rx_chain_front(what, plan, rx, ref_bits_packed, iq_window):
+    """What rx_chain_task4 and rx_chain_task5 (`what`) do alike before their own outputs: the row check, iq_window as (first,
+    count) or None, the packed bits [n_frames, frame_bytes] and, with reference bits, the errors [n_frames] -> (call, n_frames,
+    iq_window, bits, errors, the pointers (bits_out, ref_bits, errors_out))."""
     call = _Call(rx, f64=plan.f64)
     rows, nfr = _shape2(rx)
     if rows != plan.frame_samples:
-        raise OfdmError("rx_chain_task5: rx must have (Nfft+T_guard)*N_symb rows")
+        raise OfdmError(f"{what}: rx must have (Nfft+T_guard)*N_symb rows")
+    iq = None
     if iq_window is not None:
         try:
             iq_first, iq_count = (int(v) for v in iq_window)
         except (TypeError, ValueError):
-            raise OfdmError("rx_chain_task5: iq_window must be (first, count)") from None
+            raise OfdmError(f"{what}: iq_window must be (first, count)") from None
+        iq = (iq_first, iq_count)
     flat_bits, pbits = call._out((plan.frame_bytes * nfr,), np.uint8, torch.uint8 if call.dev else None)
     bits = flat_bits.reshape(nfr, plan.frame_bytes)
-    pref = None
-    errors, perr = None, None
+    pref, errors, perr = None, None, None
     if ref_bits_packed is not None:
         ref = ref_bits_packed
         if tuple(ref.shape) != (nfr, plan.frame_bytes):
-            raise OfdmError("rx_chain_task5: ref_bits_packed must be [n_frames, frame_bytes]")
+            raise OfdmError(f"{what}: ref_bits_packed must be [n_frames, frame_bytes]")
         ref = ref.contiguous().view(-1) if _is_torch(ref) else np.ascontiguousarray(ref).reshape(-1)
         pref = call._flat(ref, np.uint8, torch.uint8 if call.dev else None)[0]
         errors, perr = call._out((nfr,), np.uint32, torch.int32 if call.dev else None)
-    H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
-    idx, pidx = (call._out((plan.taps, nfr), np.int32, torch.int32 if call.dev else None) if want_index else (None, None))
-    if not want_mer and iq_window is None:
-        L.check(call.lib.ofdm_rx_chain_task5(plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, call.flags),
-                "rx_chain_task5")
-        return dict(bits=bits, errors=errors, H=H, index=idx)
-    out = dict(bits=bits, errors=errors, H=H, index=idx)
+    return call, nfr, iq, bits, errors, (pbits, pref, perr)
+
+
+def _rx_chain_tail(what, plan, call, rx, nfr, out, args, want_mer, iq, mer_args=()):
+    """The call itself and what it adds to `out`: ofdm_<what> without the MER sums and the window, else ofdm_<what>_ex or, with
+    the window iq = (first, count), ofdm_<what>_iq.  args: the receiver's own arguments and output pointers, as all three
+    entries take them behind n_frames; mer_args: what _ex and _iq take between those and mer_sums_out."""
+    if not want_mer and iq is None:
+        L.check(getattr(call.lib, f"ofdm_{what}")(plan.handle, call.cin(rx), nfr, *args, call.flags), what)
+        return out
     mer, pmer = None, None
     if want_mer:
         mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
         mer = mer.T
         out.update(mer_sums=mer)
-    head = (plan.handle, call.cin(rx), nfr, pbits, pref, perr, pH, pidx, pmer)
-    if iq_window is None:
-        L.check(call.lib.ofdm_rx_chain_task5_ex(*head, call.flags), "rx_chain_task5_ex")
+    head = (plan.handle, call.cin(rx), nfr, *args, *mer_args, pmer)
+    if iq is None:
+        L.check(getattr(call.lib, f"ofdm_{what}_ex")(*head, call.flags), f"{what}_ex")
     else:
-        iq, piq = call.cout((max(iq_count, 0), nfr))                                      # memory [n_frames][count]
-        L.check(call.lib.ofdm_rx_chain_task5_iq(*head, iq_first, iq_count, piq, call.flags), "rx_chain_task5_iq")
-        out.update(RX_IQ=iq.T)
+        buf, piq = call.cout((max(iq[1], 0), nfr))                                        # memory [n_frames][count]
+        L.check(getattr(call.lib, f"ofdm_{what}_iq")(*head, *iq, piq, call.flags), f"{what}_iq")
+        out.update(RX_IQ=buf.T)
     if want_mer:
         out.update(MER_dB=_mer_db(mer))
     return out
@@ -1521,52 +1526,16 @@ def rx_chain_task4(plan: RxPlan, rx, time_desync=1, freq_desync=1, mp_desync=1, 
     iq_window=(first, count) (ofdm_rx_chain_task4_iq): also RX_IQ=[n_frames, count] complex in the plan's precision, the
     equalised points get_payload(.)(:) of each frame from 0-based index first on -- what the demapper slices and MER_func sums;
     (nd, nd) is the scatterplot(RX_IQ(length(dataCarriers)+1 : 2*length(dataCarriers))) of T4/Main_model_Task_4.m:165."""
-    call = _Call(rx, f64=plan.f64)
-    rows, nfr = _shape2(rx)
-    if rows != plan.frame_samples:
-        raise OfdmError("rx_chain_task4: rx must have (Nfft+T_guard)*N_symb rows")
-    if iq_window is not None:
-        try:
-            iq_first, iq_count = (int(v) for v in iq_window)
-        except (TypeError, ValueError):
-            raise OfdmError("rx_chain_task4: iq_window must be (first, count)") from None
-    flat_bits, pbits = call._out((plan.frame_bytes * nfr,), np.uint8, torch.uint8 if call.dev else None)
-    bits = flat_bits.reshape(nfr, plan.frame_bytes)
-    pref, errors, perr = None, None, None
-    if ref_bits_packed is not None:
-        ref = ref_bits_packed
-        if tuple(ref.shape) != (nfr, plan.frame_bytes):
-            raise OfdmError("rx_chain_task4: ref_bits_packed must be [n_frames, frame_bytes]")
-        ref = ref.contiguous().view(-1) if _is_torch(ref) else np.ascontiguousarray(ref).reshape(-1)
-        pref = call._flat(ref, np.uint8, torch.uint8 if call.dev else None)[0]
-        errors, perr = call._out((nfr,), np.uint32, torch.int32 if call.dev else None)
+    call, nfr, iq, bits, errors, pbits = _rx_chain_front("rx_chain_task4", plan, rx, ref_bits_packed, iq_window)
     tg, ptg = call._out((nfr,), np.int64, torch.int64 if call.dev else None)
     fo, pfo = call._out((nfr,), np.float64, torch.float64 if call.dev else None)
     ifo, pifo = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     stt, pst = call._out((nfr,), np.int32, torch.int32 if call.dev else None)
     H, pH = (call.cout((plan.N_carrier, nfr)) if want_h else (None, None))
-    if not want_mer and iq_window is None:
-        L.check(call.lib.ofdm_rx_chain_task4(plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)),
-                                             int(bool(mp_desync)), pbits, pref, perr, ptg, pfo, pifo, pst, pH, call.flags),
-                "rx_chain_task4")
-        return dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
-    out = dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H)
-    mer, pmer = None, None
-    if want_mer:
-        mer, pmer = call._out((2, nfr), np.float64, torch.float64 if call.dev else None)     # memory [n_frames][2]
-        mer = mer.T
-        out.update(mer_sums=mer)
-    head = (plan.handle, call.cin(rx), nfr, int(bool(time_desync)), int(bool(freq_desync)), int(bool(mp_desync)), pbits, pref,
-            perr, ptg, pfo, pifo, pst, pH, int(mer_skip) if want_mer else 0, pmer)
-    if iq_window is None:
-        L.check(call.lib.ofdm_rx_chain_task4_ex(*head, call.flags), "rx_chain_task4_ex")
-    else:
-        iq, piq = call.cout((max(iq_count, 0), nfr))                                      # memory [n_frames][count]
-        L.check(call.lib.ofdm_rx_chain_task4_iq(*head, iq_first, iq_count, piq, call.flags), "rx_chain_task4_iq")
-        out.update(RX_IQ=iq.T)
-    if want_mer:
-        out.update(MER_dB=_mer_db(mer))
-    return out
+    return _rx_chain_tail("rx_chain_task4", plan, call, rx, nfr,
+                          dict(bits=bits, errors=errors, TgPosition=tg, FreqOffset=fo, IFO=ifo, status=stt, H=H),
+                          (int(bool(time_desync)), int(bool(freq_desync)), int(bool(mp_desync)), *pbits, ptg, pfo, pifo, pst, pH),
+                          want_mer, iq, mer_args=(int(mer_skip) if want_mer else 0,))
 
 
 def rx_spectrum(plan: RxPlan, rx, first=None, n_windows=1, want_power=False):

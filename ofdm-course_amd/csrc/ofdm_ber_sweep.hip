@@ -13,10 +13,14 @@
 //                                   reads them with a frame stride of 0 (ofdm_ber_sweep_task4_nmse, NMSE of T4:205-239)
 //
 // Host side: what a call decides -- its channel, the chunk, the argument checks in the entry's order -- is txf_plan.hpp's.
-// The sweeps share their outputs (txf_sweep_outputs), the point x chunk loop with the generation inside (txf_sweep_points of
-// txf_study.hpp, the receiver passed as a callable) and the MER reduction (txf_point_mer); each keeps its own outputs, scratch, chunk budget and
-// per-point reduction.  The Task-5 entries fill a TxfCall and forward to t5_sweep, the Task-4 entries to t4_sweep; a fading
-// entry's TxfCall names a tap-delay line, and the generator then draws a channel per frame.
+// The two sweep bodies (t5_sweep, t4_sweep) share the staging of the outputs both have -- errors, MER sums, channel-estimate
+// error sums, per point and per frame (SweepOuts, txf_sweep_outputs) --, the point x chunk loop with the generation inside
+// (txf_sweep_points of txf_study.hpp, the receiver passed as a callable), the fixed-order sums of the per-frame doubles
+// (txf_point_sums) and the constellation density (SweepScope; SweepScopeAcc owns where the grids live, their zeroing, the
+// capture of a receiver call and the copy back).  Each keeps its receiver's own outputs, scratch, chunk budget and per-point
+// reduction.  Every extern "C" entry is one call of its receiver's t5_entry / t4_entry, which fills the TxfCall from the
+// entry's channel (SweepChan: a static h, or a tap-delay line, for which the generator draws a channel per frame), points and
+// outputs, or forwards to the entry whose arguments contain its own.
 #include <algorithm>
 #include <cmath>
 
@@ -151,27 +155,38 @@ __global__ __launch_bounds__(256) void t4_point_mer_kernel(const double* __restr
 // host side
 // ---------------------------------------------------------------------------------------------
 
-// the outputs both sweeps have: per point the bit errors and MER sums, per frame the errors and MER sums
+// what a caller of a sweep may ask for beside its receiver's own outputs: per point the bit errors, the MER sums and the
+// channel-estimate error sums, per frame the same three (errors: mandatory; every other: null = not wanted)
+struct SweepOuts {
+  uint64_t* errors;
+  uint32_t* frame_errors;
+  double *mer_sums, *frame_mer_sums, *nmse_sums, *frame_nmse;
+};
+
+// those outputs as the kernels see them
 struct TxfSweepOut {
-  void *err = nullptr, *fe = nullptr, *mer = nullptr, *fm = nullptr;
+  void *err = nullptr, *fe = nullptr, *mer = nullptr, *fm = nullptr, *ns = nullptr, *fn = nullptr;
 };
 
 // stages the common outputs; with no frames the per-point sums are zeroed, else the per-frame values of every point
 // (reduced once after the last chunk) get scratch where the caller wants none
-static int txf_sweep_outputs(Stage& st, int64_t n_points, int64_t frames_per_point, uint64_t* errors_out,
-                             uint32_t* frame_errors_out, double* mer_sums_out, double* frame_mer_sums_out, TxfSweepOut& o) {
+static int txf_sweep_outputs(Stage& st, int64_t n_points, int64_t frames_per_point, const SweepOuts& out, TxfSweepOut& o) {
   const size_t np = (size_t)n_points, nf = (size_t)(n_points * frames_per_point);
-  OFDM_TRY(st.out(errors_out, sizeof(uint64_t) * np, &o.err));
-  OFDM_TRY(st.out(frame_errors_out, sizeof(uint32_t) * nf, &o.fe));
-  OFDM_TRY(st.out(mer_sums_out, sizeof(double) * 2 * np, &o.mer));
-  OFDM_TRY(st.out(frame_mer_sums_out, sizeof(double) * 2 * nf, &o.fm));
+  OFDM_TRY(st.out(out.errors, sizeof(uint64_t) * np, &o.err));
+  OFDM_TRY(st.out(out.frame_errors, sizeof(uint32_t) * nf, &o.fe));
+  OFDM_TRY(st.out(out.mer_sums, sizeof(double) * 2 * np, &o.mer));
+  OFDM_TRY(st.out(out.frame_mer_sums, sizeof(double) * 2 * nf, &o.fm));
+  OFDM_TRY(st.out(out.nmse_sums, sizeof(double) * np, &o.ns));
+  OFDM_TRY(st.out(out.frame_nmse, sizeof(double) * nf, &o.fn));
   if (frames_per_point == 0) {
     OFDM_HIP(hipMemsetAsync(o.err, 0, sizeof(uint64_t) * np, ctx().stream));
     if (o.mer) OFDM_HIP(hipMemsetAsync(o.mer, 0, sizeof(double) * 2 * np, ctx().stream));
+    if (o.ns) OFDM_HIP(hipMemsetAsync(o.ns, 0, sizeof(double) * np, ctx().stream));
     return OFDM_OK;
   }
   if (!o.fe) OFDM_TRY(st.scratch(sizeof(uint32_t) * nf, &o.fe));
   if (o.mer && !o.fm) OFDM_TRY(st.scratch(sizeof(double) * 2 * nf, &o.fm));
+  if (o.ns && !o.fn) OFDM_TRY(st.scratch(sizeof(double) * nf, &o.fn));
   return OFDM_OK;
 }
 
@@ -196,10 +211,6 @@ int txf_static_amps(const TxfChannel& ch, c64* damp) {
   for (int t = 0; t < n_taps; ++t) sa.a[t] = mk<double>(ch.amp[t].x, ch.amp[t].y);
   hipLaunchKernelGGL(tx_static_amp_kernel, dim3(1), dim3(64), 0, ctx().stream, damp, sa, n_taps);
   return check_launch("tx_static_amp_kernel");
-}
-
-static int txf_point_mer(const TxfSweepOut& o, int64_t n_points, int64_t frames_per_point) {
-  return txf_point_sums<2>(o.fm, n_points, frames_per_point, o.mer);
 }
 
 // the channel-estimate error of the chunk's nf frames against the channel of taps dl / amplitudes amp (t5_frame_nmse_kernel)
@@ -234,19 +245,23 @@ static int txf_sweep_prelude(ofdm_rx_plan* pl, TxfCall& c, TxfShape& s, const vo
   return txf_refused(prelude(c, ch, fade.gains, why), why);
 }
 
-// the constellation density of a Task-5 sweep's points (ofdm_ber_sweep_task5_scope)
+// the constellation density of a sweep's points (ofdm_ber_sweep_task5_scope, ofdm_ber_sweep_task4_scope)
 struct SweepScope {
   bool on = false;
   int bins = 0;
   double half_width = 0.0;
   int64_t skip = 0;
   uint64_t *density_out = nullptr, *dropped_out = nullptr;
+  SweepScope() = default;
+  SweepScope(int bins_, double half_width_, int64_t skip_, uint64_t* density_out_, uint64_t* dropped_out_)
+      : on(true), bins(bins_), half_width(half_width_), skip(skip_), density_out(density_out_), dropped_out(dropped_out_) {}
 };
 
-// The density grids [n_points][bins][bins] and the dropped counters [n_points] are accumulators of the symbol stages' global
-// atomics: the caller's device outputs themselves; host outputs, and dropped counters nobody asked for, in a buffer of the
-// plan's own (pl->ws_scope -- not the generator workspace, whose regions are per chunk).  Zeroed on the launch stream
-// before the first chunk; host outputs are copied back in front of st.finish()'s synchronisation (finish()).
+// The density grids [n_points][bins][bins] and the dropped counters [n_points] are accumulators of the global atomics of the
+// Task-5 symbol stages and of the Task-4 receiver's eq_demap_kernel: the caller's device outputs themselves; host outputs, and
+// dropped counters nobody asked for, in a buffer of the plan's own (pl->ws_scope -- not the generator workspace, whose regions
+// are per chunk).  Zeroed on the launch stream before the first chunk; host outputs are copied back in front of st.finish()'s
+// synchronisation (finish()).
 struct SweepScopeAcc {
   unsigned long long *dens = nullptr, *drop = nullptr;
   size_t grid_elems = 0;
@@ -289,15 +304,13 @@ struct SweepScopeAcc {
 };
 
 // the body of the Task-5 sweep entries: the checks of txf_task5_prelude, then c's static channel, or the delay line of a
-// channel per frame; nmse_sums_out / frame_nmse_out (fading only): the channel-estimate error sums; sw: the density of
+// channel per frame; out.nmse_sums / out.frame_nmse (fading only): the channel-estimate error sums; sw: the density of
 // ofdm_ber_sweep_task5_scope
-static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t* frame_errors_out, double* mer_sums_out,
-                    double* frame_mer_sums_out, double* nmse_sums_out, double* frame_nmse_out, int flags,
-                    const SweepScope& sw = SweepScope{}) {
+static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, const SweepOuts& out, int flags, const SweepScope& sw) {
   TxfShape s{};
   TxfChannel ch;
   TxfFade fade;
-  OFDM_TRY(txf_sweep_prelude(pl, c, s, errors_out, flags, txf_task5_prelude, ch, fade));
+  OFDM_TRY(txf_sweep_prelude(pl, c, s, out.errors, flags, txf_task5_prelude, ch, fade));
   const int64_t decisions = (int64_t)s.nd * s.n_symb;
   if (sw.on) {                                                  // behind every check of the entry without a density
     int stage = SYM_EQ_DEMAP;
@@ -313,24 +326,18 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
   if (n_points == 0) return OFDM_OK;
   Stage st(flags);
   TxfSweepOut o;
-  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
-                             o));
-  void *dns, *dfn;
-  OFDM_TRY(st.out(nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
-  OFDM_TRY(st.out(frame_nmse_out, sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
+  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, out, o));
   SweepScopeAcc acc;
   if (sw.on) OFDM_TRY(acc.begin(pl, sw, st.device_mode(), n_points));
   if (frames_per_point == 0) {
-    if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, ctx().stream));
     if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
     return st.finish();
   }
-  if (dns && !dfn) OFDM_TRY(st.scratch(sizeof(double) * (size_t)(n_points * frames_per_point), &dfn));
   TxfUse u;
   u.scr = c.scr_reg15 != nullptr;
   u.sweep = true;
   u.fade_taps = c.fading ? (int)ch.delay.size() : 0;
-  u.hest = dfn != nullptr;
+  u.hest = o.fn != nullptr;
   int64_t CH = txf_chunk(s, u, frames_per_point, c.max_chunk);
   // a density: a chunk holds at most 2^32 - 1 points, so that no uint32 bin of a workgroup's grid can wrap (counts are integers:
   // the result does not depend on the chunking)
@@ -348,14 +355,14 @@ static int t5_sweep(ofdm_rx_plan* pl, TxfCall c, uint64_t* errors_out, uint32_t*
                                                           (uint32_t*)o.fe + k, b.hest, nullptr,
                                                           o.fm ? (double*)o.fm + 2 * k : nullptr, rxflags, inv_snr,
                                                           sw.on ? &sc : nullptr));
-                              if (!dfn) return (int)OFDM_OK;
-                              return txf_frame_nmse(pl, b.amp, b.hest, dl, (int64_t)dl.n, nf, (double*)dfn + k);
+                              if (!o.fn) return (int)OFDM_OK;
+                              return txf_frame_nmse(pl, b.amp, b.hest, dl, (int64_t)dl.n, nf, (double*)o.fn + k);
                             }));
   hipLaunchKernelGGL(ber_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, ctx().stream, (const uint32_t*)o.fe,
                      frames_per_point, (unsigned long long*)o.err);
   OFDM_TRY(check_launch("ber_point_reduce_kernel"));
-  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
-  OFDM_TRY(txf_point_sums<1>(dfn, n_points, frames_per_point, dns));
+  OFDM_TRY(txf_point_sums<2>(o.fm, n_points, frames_per_point, o.mer));
+  OFDM_TRY(txf_point_sums<1>(o.fn, n_points, frames_per_point, o.ns));
   if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
   return st.finish();
 }
@@ -366,29 +373,23 @@ struct T4SweepArgs {
   int time_desync, freq_desync, mp_desync;
   uint64_t* status_counts_out;
   double* cfo_abs_err_out;
-  double *nmse_sums_out, *frame_nmse_out;
-  // ofdm_ber_sweep_task4_scope: the constellation density of every point
-  bool scope = false;
-  int bins = 0;
-  double half_width = 0.0;
-  int64_t scope_skip = 0;
-  uint64_t *density_out = nullptr, *dropped_out = nullptr;
+  SweepScope sw;                                                // ofdm_ber_sweep_task4_scope: the density of every point
 };
 
 // the body of the Task-4 sweep entries: the checks of txf_task4_prelude, then c's static channel, or the delay line of a
-// channel per frame; nmse_sums_out / frame_nmse_out (optional): the channel-estimate error sums against the channel's H
+// channel per frame; out.nmse_sums / out.frame_nmse (optional): the channel-estimate error sums against the channel's H
 // (static: one H for every frame) or the frame's own H_f (fading)
-static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t* errors_out, uint32_t* frame_errors_out,
-                    double* mer_sums_out, double* frame_mer_sums_out, int flags) {
-  c.nmse_out = a.nmse_sums_out || a.frame_nmse_out;
+static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, const SweepOuts& out, int flags) {
+  const SweepScope& sw = a.sw;
+  c.nmse_out = out.nmse_sums || out.frame_nmse;
   c.mp_desync = a.mp_desync;
   TxfShape s{};
   TxfChannel ch;
   TxfFade fade;
-  OFDM_TRY(txf_sweep_prelude(pl, c, s, errors_out, flags, txf_task4_prelude, ch, fade));
-  if (a.scope) {                                                // behind every check of the entry without a density
+  OFDM_TRY(txf_sweep_prelude(pl, c, s, out.errors, flags, txf_task4_prelude, ch, fade));
+  if (sw.on) {                                                  // behind every check of the entry without a density
     ScopeWhy why;
-    OFDM_TRY(scope_refused(scope_density_check(a.density_out != nullptr, a.bins, a.half_width, a.scope_skip, s.f64 != 0,
+    OFDM_TRY(scope_refused(scope_density_check(sw.density_out != nullptr, sw.bins, sw.half_width, sw.skip, s.f64 != 0,
                                                s.n_carrier, (int64_t)s.nd * s.n_symb, why), why));
   }
   const TxfPoints pt{c.snr_db, c.seeds, c.n_points, c.n_frames, c.frame0};
@@ -397,50 +398,17 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   Stage st(flags);
   const int64_t NF = n_points * frames_per_point;
   TxfSweepOut o;
-  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out,
-                             o));
-  void *dsc, *dabs, *dns, *dfn;
+  OFDM_TRY(txf_sweep_outputs(st, n_points, frames_per_point, out, o));
+  void *dsc, *dabs;
   OFDM_TRY(st.out(a.status_counts_out, sizeof(uint64_t) * 4 * (size_t)n_points, &dsc));
   OFDM_TRY(st.out(a.cfo_abs_err_out, sizeof(double) * (size_t)n_points, &dabs));
-  OFDM_TRY(st.out(a.nmse_sums_out, sizeof(double) * (size_t)n_points, &dns));
-  OFDM_TRY(st.out(a.frame_nmse_out, sizeof(double) * (size_t)NF, &dfn));
   hipStream_t stream = ctx().stream;
-  // The density grids [n_points][bins][bins] and the dropped counters [n_points] are accumulators of eq_demap_kernel's global
-  // atomics: the caller's device outputs themselves; host outputs, and dropped counters nobody asked for, in a buffer of the
-  // plan's own (pl->ws_scope -- not the generator workspace, whose regions are per chunk).  Zeroed on the launch stream
-  // before the first chunk; host outputs are copied back in front of st.finish()'s synchronisation.
-  const size_t grid_elems = (size_t)a.bins * (size_t)a.bins;
-  unsigned long long *ddens = nullptr, *ddrop = nullptr;
-  const bool scope_dev = st.device_mode();
-  if (a.scope) {
-    const size_t own = sizeof(uint64_t) * (scope_dev ? (a.dropped_out ? 0 : (size_t)n_points) : (size_t)n_points * (grid_elems + 1));
-    if (pl->ws_scope_bytes < own) {
-      OFDM_HIP(hipStreamSynchronize(stream));
-      if (pl->ws_scope) { (void)hipFree(pl->ws_scope); pl->ws_scope = nullptr; pl->ws_scope_bytes = 0; }
-      OFDM_HIP(hipMalloc(&pl->ws_scope, own));
-      pl->ws_scope_bytes = own;
-    }
-    if (scope_dev) {
-      ddens = (unsigned long long*)a.density_out;
-      ddrop = a.dropped_out ? (unsigned long long*)a.dropped_out : (unsigned long long*)pl->ws_scope;
-    } else {
-      ddens = (unsigned long long*)pl->ws_scope;
-      ddrop = ddens + (size_t)n_points * grid_elems;
-    }
-    OFDM_HIP(hipMemsetAsync(ddens, 0, sizeof(uint64_t) * (size_t)n_points * grid_elems, stream));
-    OFDM_HIP(hipMemsetAsync(ddrop, 0, sizeof(uint64_t) * (size_t)n_points, stream));
-  }
-  auto scope_finish = [&]() -> int {
-    if (!a.scope || scope_dev) return OFDM_OK;
-    OFDM_HIP(hipMemcpyAsync(a.density_out, ddens, sizeof(uint64_t) * (size_t)n_points * grid_elems, hipMemcpyDeviceToHost, stream));
-    if (a.dropped_out) OFDM_HIP(hipMemcpyAsync(a.dropped_out, ddrop, sizeof(uint64_t) * (size_t)n_points, hipMemcpyDeviceToHost, stream));
-    return OFDM_OK;
-  };
+  SweepScopeAcc acc;
+  if (sw.on) OFDM_TRY(acc.begin(pl, sw, st.device_mode(), n_points));
   if (frames_per_point == 0) {
     if (dsc) OFDM_HIP(hipMemsetAsync(dsc, 0, sizeof(uint64_t) * 4 * (size_t)n_points, stream));
     if (dabs) OFDM_HIP(hipMemsetAsync(dabs, 0, sizeof(double) * (size_t)n_points, stream));
-    if (dns) OFDM_HIP(hipMemsetAsync(dns, 0, sizeof(double) * (size_t)n_points, stream));
-    OFDM_TRY(scope_finish());
+    if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
     return st.finish();
   }
   // the per-frame values of every point, reduced once after the last chunk
@@ -451,14 +419,13 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   OFDM_TRY(st.scratch(sizeof(int32_t) * (size_t)NF, &dstat));
   OFDM_TRY(st.scratch(sizeof(int64_t) * (size_t)NF, &dsto));
   OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dcfo));
-  if (dns && !dfn) OFDM_TRY(st.scratch(sizeof(double) * (size_t)NF, &dfn));
   const int n_taps = (int)ch.delay.size();
   TxfUse u;
   u.scr = c.scr_reg15 != nullptr;
   u.sweep = true;
   u.imp = true;
   u.fade_taps = c.fading ? n_taps : 0;
-  u.hest = dfn != nullptr;
+  u.hest = o.fn != nullptr;
   const int64_t CH = txf_chunk_task4(s, u, frames_per_point, c.max_chunk, o.fm != nullptr);
   const int rxflags = OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0);
   TxfImp imp = a.imp;
@@ -466,7 +433,7 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   imp.cfo = (double*)dcfo;
   TxfDelays dl{};
   void* dstatic = nullptr;                                      // NMSE against a static channel: its taps, read with stride 0
-  if (dfn) {
+  if (o.fn) {
     dl = txf_delays(ch);
     if (!c.fading) {
       OFDM_TRY(st.scratch(sizeof(c64) * (size_t)std::max(n_taps, 1), &dstatic));   // an all-zero h has no taps: H = 0
@@ -475,29 +442,62 @@ static int t4_sweep(ofdm_rx_plan* pl, TxfCall c, const T4SweepArgs& a, uint64_t*
   }
   OFDM_TRY(txf_sweep_points(pl, ch, pt, c.scr_reg15, CH, &imp, c.fading ? &fade : nullptr, u,
                             [&](const TxfBuffers& b, int64_t nf, int64_t p, int64_t k) {
-                              ScopeCall sc;                     // a chunk holds frames of one point: one grid per receiver call
-                              if (a.scope) {
-                                sc.bins = a.bins; sc.skip = a.scope_skip; sc.half_width = a.half_width;
-                                sc.scale = scope_scale(a.bins, a.half_width);
-                                sc.density = ddens + (size_t)p * grid_elems; sc.dropped = ddrop + p;
-                              }
+                              ScopeCall sc;
+                              if (sw.on) sc = acc.call(sw, p);
                               OFDM_TRY(rx_chain_task4_run(pl, b.rx, nf, a.time_desync, a.freq_desync, a.mp_desync, nullptr,
                                                           (const uint8_t*)b.ref, (uint32_t*)o.fe + k, (int64_t*)dtg + k,
                                                           (double*)dfo + k, (int32_t*)difo + k, (int32_t*)dstat + k,
                                                           b.hest, c.mer_skip, o.fm ? (double*)o.fm + 2 * k : nullptr,
-                                                          a.scope ? &sc : nullptr, rxflags));
-                              if (!dfn) return (int)OFDM_OK;
+                                                          sw.on ? &sc : nullptr, rxflags));
+                              if (!o.fn) return (int)OFDM_OK;
                               return txf_frame_nmse(pl, c.fading ? (const c64*)b.amp : (const c64*)dstatic, b.hest, dl,
-                                                    c.fading ? n_taps : 0, nf, (double*)dfn + k);
+                                                    c.fading ? n_taps : 0, nf, (double*)o.fn + k);
                             }));
   hipLaunchKernelGGL(t4_point_reduce_kernel, dim3((unsigned)n_points), dim3(256), 0, stream, (const uint32_t*)o.fe,
                      (const int32_t*)dstat, (const double*)dfo, (const int32_t*)difo, (const double*)dcfo, frames_per_point,
                      a.freq_desync ? 1 : 0, (unsigned long long*)o.err, (unsigned long long*)dsc, (double*)dabs);
   OFDM_TRY(check_launch("t4_point_reduce_kernel"));
-  OFDM_TRY(txf_point_mer(o, n_points, frames_per_point));
-  OFDM_TRY(txf_point_sums<1>(dfn, n_points, frames_per_point, dns));
-  OFDM_TRY(scope_finish());
+  OFDM_TRY(txf_point_sums<2>(o.fm, n_points, frames_per_point, o.mer));
+  OFDM_TRY(txf_point_sums<1>(o.fn, n_points, frames_per_point, o.ns));
+  if (sw.on) OFDM_TRY(acc.finish(sw, st.device_mode(), n_points));
   return st.finish();
+}
+
+// what every sweep entry builds its TxfCall from: the channel as the static h / h_len or, with `fading`, as a tap-delay line
+struct SweepChan {
+  bool fading;
+  const void* h;
+  int h_len;
+  const int32_t* tap_delay;
+  const double* tap_power;
+  int n_taps;
+};
+static SweepChan chan_static(const void* h, int h_len) { return SweepChan{false, h, h_len, nullptr, nullptr, 0}; }
+static SweepChan chan_fading(const int32_t* tap_delay, const double* tap_power, int n_taps) {
+  return SweepChan{true, nullptr, 0, tap_delay, tap_power, n_taps};
+}
+
+static TxfCall sweep_call(const char* what, const SweepChan& ch, const TxfPoints& pt, const uint8_t* scr_reg15, int64_t max_chunk) {
+  TxfCall c(what, pt.frame0, pt.frames_per_point, scr_reg15);
+  if (ch.fading) c.with_fading(ch.tap_delay, ch.tap_power, ch.n_taps);
+  else c.with_h(ch.h, ch.h_len);
+  return c.with_points(pt.snr_db, pt.seeds, pt.n_points, max_chunk);
+}
+
+// the one body of the Task-5 entries
+static int t5_entry(ofdm_rx_plan* pl, const SweepChan& ch, const TxfPoints& pt, const uint8_t* scr_reg15, int64_t max_chunk,
+                    const SweepOuts& out, int flags, const SweepScope& sw = SweepScope{}) {
+  return t5_sweep(pl, sweep_call(ch.fading ? "ber_sweep_task5_fading" : "ber_sweep_task5", ch, pt, scr_reg15, max_chunk), out,
+                  flags, sw);
+}
+
+// the one body of the Task-4 entries; a: the impairments, the receiver's flags and outputs, the density
+static int t4_entry(ofdm_rx_plan* pl, const SweepChan& ch, const TxfPoints& pt, const uint8_t* scr_reg15, int64_t max_chunk,
+                    int64_t mer_skip, const T4SweepArgs& a, const SweepOuts& out, int flags) {
+  TxfCall c = sweep_call(ch.fading ? "ber_sweep_task4_fading" : "ber_sweep_task4", ch, pt, scr_reg15, max_chunk)
+                  .with_imp(a.imp.sto_mode, a.imp.cfo_mode);
+  c.mer_skip = mer_skip;
+  return t4_sweep(pl, c, a, out, flags);
 }
 
 }  // namespace ofdm
@@ -508,9 +508,9 @@ extern "C" int ofdm_ber_sweep_task5_ex(ofdm_rx_plan* pl, const void* h, int h_le
                                        int64_t n_points, int64_t frames_per_point, int64_t frame0, const uint8_t* scr_reg15,
                                        int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
                                        double* mer_sums_out, double* frame_mer_sums_out, int flags) {
-  return t5_sweep(pl, TxfCall("ber_sweep_task5", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
-                          .with_points(snr_db, seeds, n_points, max_frames_per_chunk),
-                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nullptr, nullptr, flags);
+  return t5_entry(pl, chan_static(h, h_len), TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0}, scr_reg15,
+                  max_frames_per_chunk, SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nullptr, nullptr},
+                  flags);
 }
 
 extern "C" int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
@@ -519,9 +519,9 @@ extern "C" int ofdm_ber_sweep_task5_fading(ofdm_rx_plan* pl, const int32_t* tap_
                                            int64_t max_frames_per_chunk, uint64_t* errors_out, uint32_t* frame_errors_out,
                                            double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
                                            double* frame_nmse_out, int flags) {
-  return t5_sweep(pl, TxfCall("ber_sweep_task5_fading", frame0, frames_per_point, scr_reg15)
-                          .with_fading(tap_delay, tap_power, n_taps).with_points(snr_db, seeds, n_points, max_frames_per_chunk),
-                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out, flags);
+  return t5_entry(pl, chan_fading(tap_delay, tap_power, n_taps), TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0},
+                  scr_reg15, max_frames_per_chunk,
+                  SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out}, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task5_scope(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
@@ -536,17 +536,11 @@ extern "C" int ofdm_ber_sweep_task5_scope(ofdm_rx_plan* pl, const int32_t* tap_d
   // one channel: the static h / h_len (h = NULL: none), or the delay line of n_taps > 0 taps
   OFDM_ARG(!(n_taps > 0 && (h || h_len)), "ber_sweep_task5_scope: give the static channel h / h_len or the tap-delay line (n_taps > 0), not both");
   OFDM_ARG(n_taps >= 0, "ber_sweep_task5_scope: n_taps must be >= 0 (%d)", n_taps);
-  SweepScope sw;
-  sw.on = true; sw.bins = bins; sw.half_width = half_width; sw.skip = scope_skip;
-  sw.density_out = density_out; sw.dropped_out = density_dropped_out;
-  if (n_taps > 0)
-    return t5_sweep(pl, TxfCall("ber_sweep_task5_fading", frame0, frames_per_point, scr_reg15)
-                            .with_fading(tap_delay, tap_power, n_taps).with_points(snr_db, seeds, n_points, max_frames_per_chunk),
-                    errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out, flags, sw);
-  OFDM_ARG(!nmse_sums_out && !frame_nmse_out, "ber_sweep_task5_scope: the NMSE outputs need the tap-delay line (n_taps > 0)");
-  return t5_sweep(pl, TxfCall("ber_sweep_task5", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
-                          .with_points(snr_db, seeds, n_points, max_frames_per_chunk),
-                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nullptr, nullptr, flags, sw);
+  OFDM_ARG(n_taps > 0 || (!nmse_sums_out && !frame_nmse_out), "ber_sweep_task5_scope: the NMSE outputs need the tap-delay line (n_taps > 0)");
+  return t5_entry(pl, n_taps > 0 ? chan_fading(tap_delay, tap_power, n_taps) : chan_static(h, h_len),
+                  TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0}, scr_reg15, max_frames_per_chunk,
+                  SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out}, flags,
+                  SweepScope(bins, half_width, scope_skip, density_out, density_dropped_out));
 }
 
 extern "C" int ofdm_ber_sweep_task5(ofdm_rx_plan* pl, const void* h, int h_len, const double* snr_db, const uint64_t* seeds,
@@ -564,12 +558,11 @@ extern "C" int ofdm_ber_sweep_task4_nmse(ofdm_rx_plan* pl, const void* h, int h_
                                          double* cfo_abs_err_out, uint32_t* frame_errors_out, int64_t mer_skip,
                                          double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
                                          double* frame_nmse_out, int flags) {
-  TxfCall c = TxfCall("ber_sweep_task4", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
-                  .with_imp(sto_mode, cfo_mode).with_points(snr_db, seeds, n_points, max_frames_per_chunk);
-  c.mer_skip = mer_skip;
-  return t4_sweep(pl, c, T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
-                                     status_counts_out, cfo_abs_err_out, nmse_sums_out, frame_nmse_out},
-                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, flags);
+  return t4_entry(pl, chan_static(h, h_len), TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0}, scr_reg15,
+                  max_frames_per_chunk, mer_skip,
+                  T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
+                              status_counts_out, cfo_abs_err_out, SweepScope{}},
+                  SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out}, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4_scope(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,
@@ -581,14 +574,12 @@ extern "C" int ofdm_ber_sweep_task4_scope(ofdm_rx_plan* pl, const void* h, int h
                                           double* mer_sums_out, double* frame_mer_sums_out, double* nmse_sums_out,
                                           double* frame_nmse_out, uint64_t* density_out, uint64_t* density_dropped_out, int bins,
                                           double half_width, int64_t scope_skip, int flags) {
-  TxfCall c = TxfCall("ber_sweep_task4", frame0, frames_per_point, scr_reg15).with_h(h, h_len)
-                  .with_imp(sto_mode, cfo_mode).with_points(snr_db, seeds, n_points, max_frames_per_chunk);
-  c.mer_skip = mer_skip;
-  T4SweepArgs a{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
-                status_counts_out, cfo_abs_err_out, nmse_sums_out, frame_nmse_out};
-  a.scope = true; a.bins = bins; a.half_width = half_width; a.scope_skip = scope_skip;
-  a.density_out = density_out; a.dropped_out = density_dropped_out;
-  return t4_sweep(pl, c, a, errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, flags);
+  return t4_entry(pl, chan_static(h, h_len), TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0}, scr_reg15,
+                  max_frames_per_chunk, mer_skip,
+                  T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
+                              status_counts_out, cfo_abs_err_out,
+                              SweepScope(bins, half_width, scope_skip, density_out, density_dropped_out)},
+                  SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out}, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* pl, const int32_t* tap_delay, const double* tap_power, int n_taps,
@@ -599,12 +590,11 @@ extern "C" int ofdm_ber_sweep_task4_fading(ofdm_rx_plan* pl, const int32_t* tap_
                                            uint64_t* status_counts_out, double* cfo_abs_err_out, uint32_t* frame_errors_out,
                                            int64_t mer_skip, double* mer_sums_out, double* frame_mer_sums_out,
                                            double* nmse_sums_out, double* frame_nmse_out, int flags) {
-  TxfCall c = TxfCall("ber_sweep_task4_fading", frame0, frames_per_point, scr_reg15).with_fading(tap_delay, tap_power, n_taps)
-                  .with_imp(sto_mode, cfo_mode).with_points(snr_db, seeds, n_points, max_frames_per_chunk);
-  c.mer_skip = mer_skip;
-  return t4_sweep(pl, c, T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
-                                     status_counts_out, cfo_abs_err_out, nmse_sums_out, frame_nmse_out},
-                  errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, flags);
+  return t4_entry(pl, chan_fading(tap_delay, tap_power, n_taps), TxfPoints{snr_db, seeds, n_points, frames_per_point, frame0},
+                  scr_reg15, max_frames_per_chunk, mer_skip,
+                  T4SweepArgs{TxfImp(sto_mode, sto_value, cfo_mode, cfo_value), time_desync, freq_desync, mp_desync,
+                              status_counts_out, cfo_abs_err_out, SweepScope{}},
+                  SweepOuts{errors_out, frame_errors_out, mer_sums_out, frame_mer_sums_out, nmse_sums_out, frame_nmse_out}, flags);
 }
 
 extern "C" int ofdm_ber_sweep_task4_ex(ofdm_rx_plan* pl, const void* h, int h_len, int sto_mode, int64_t sto_value,

@@ -55,7 +55,7 @@ struct ofdm_rx_plan {
   int t4_bw = 0, t4_span = 0;
   void* ws_t4 = nullptr;   // ofdm_rx_chain_task4: arena for its per-batch intermediates
   size_t ws_t4_bytes = 0;
-  void* ws_scope = nullptr; // ofdm_ber_sweep_task4_scope: the density grids and dropped counters of a call whose outputs are host memory
+  void* ws_scope = nullptr; // ofdm_ber_sweep_task4_scope / _task5_scope: the density grids and dropped counters of a call whose outputs are host memory
   size_t ws_scope_bytes = 0; // (or whose dropped counters are not wanted); never part of ws_txf
   void* ws_raw = nullptr;  // raw packed decisions of a batch when the DeScrambler runs as a pass of its own (descr_pass_kernel)
   size_t ws_raw_bytes = 0;

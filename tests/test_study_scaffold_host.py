@@ -48,3 +48,6 @@ def test_the_studies_share_one_scaffold():
     assert "inline int txf_study_prelude(" in plan and "inline TxfUse txf_study_use(" in plan
     sweep = _code(_read("ofdm_ber_sweep.hip"))                             # the BER sweeps: the same loop, no copy of it
     assert '#include "txf_study.hpp"' in sweep and "txf_sweep_points(" in sweep and "txf_generate(" not in sweep
+    # ... and one density accumulator for both: the plan's buffer grows in one place, a receiver call's capture is made in one
+    for once in ("pl->ws_scope_bytes <", "hipMalloc(&pl->ws_scope", "scope_scale("):
+        assert sweep.count(once) == 1, once
