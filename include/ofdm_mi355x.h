@@ -1144,6 +1144,44 @@ int ofdm_error_study(ofdm_rx_plan* plan, int receiver,        /* 4 | 5 */
                      uint64_t* map_out,                        /* optional [n_points][N_symb][nd] */
                      int flags);
 
+/* The estimator comparison of Task 5 as one device-resident call: LS_CE, MMSE_CE, MP_estimate and OMP_estimate on the same
+ * received frame of every channel realisation (T5/Task5_part2.m:148-205, :269-304; over SNR T5/Main_model_Task_5.m:303-346).  For
+ * every point p the frames frame0 .. frame0 + frames_per_point - 1 of ofdm_tx_frames_fused(h, h_len, snr_db[p], seeds[p]) -- or,
+ * with tap_delay / tap_power / n_taps in place of h, of ofdm_tx_frames_fading, a channel realisation per frame --, bit for bit,
+ * through the estimator stages of ofdm_task5_part2_tile: OFDM_demodulator, Y = X(pilots, 1) ./ pilotValues(:, 1)
+ * (Task5_part2.m:190), the four estimates, and equalize_signal -> get_payload -> demapping -> BER_func against the frame's own
+ * payload for each of them (:269-304).  Every [4] below is in the order LS, MMSE, MP, OMP.  The receiver ofdm_rx_chain_task5 and
+ * its route are not involved; the study runs unscrambled, as Task5_part2.m:104-114 does.
+ *   mmse_mode 0: MMSE_CE with h = ifft(H_est_LS) of the frame at the point's SNR (Main_model_Task_5.m:314-315);
+ *   mmse_mode 1: MMSE_CE with the frame's true impulse response (Task5_part2.m:176-177): tau_rms of MMSE_CE.m:19-24 over the taps
+ *     with a delay below N_carrier, r2 - r^2 clamped at 0.  A frame with no such tap has no tau_rms: its MMSE estimate is NaN and
+ *     the frame is counted in nmse_dropped_out; nothing is refused for what the device drew.
+ *   nmse_sums_out[p][e]: the sum over the point's frames, in frame order, of sum_k |fft(h_f, Nfft)(k) - H_e,f(k)|^2 on carriers
+ *     1..N_carrier in double (Task5_part2.m:202-205 before the division by N_carrier); a frame whose sum is not finite is left out
+ *     and counted in nmse_dropped_out[p][e].  frame_nmse_out keeps every frame's sum, finite or not.
+ * The outputs are overwritten.  Chunks of one point's frames: the generator's workspace, the estimator stages' arena and the
+ * study's rows on twice the workspace budget (max_frames_per_chunk > 0 caps the frames of a chunk, at most 65535); every output
+ * is bitwise independent of the chunking, and a call over frames frame0 .. equals the calls over its parts with the integers
+ * added.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of the workspaces.  OFDM_ERR_ARG, before
+ * anything is launched or written, in this order: what every study refuses of the generator's arguments and the plan (bad
+ * arguments, snr_db / seeds, the plan's device, precision, data carriers, pilots, Nfft, the stream range, h and taps together,
+ * the channel); a plan with a DeScrambler; mmse_mode 0 / 1; an output is given; then what ofdm_task5_part2_tile refuses of a
+ * plan, in its words (two pilots, the equalise stage's LDS, at most 585 pilots, K >= Np for MP_estimate, the MP stage's LDS).
+ * Without errors_out and frame_errors_out no equaliser runs, and H of MP and OMP is the transform of their taps, as in
+ * ofdm_task5_mse_tile. */
+int ofdm_estimator_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                         const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                         const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                         int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                         int mmse_mode,                            /* 0 ls | 1 genie */
+                         int64_t max_frames_per_chunk,
+                         uint64_t* errors_out,                     /* optional [n_points][4] */
+                         double* nmse_sums_out,                    /* optional [n_points][4] */
+                         uint64_t* nmse_dropped_out,               /* optional [n_points][4] */
+                         uint32_t* frame_errors_out,               /* optional [n_points][frames_per_point][4] */
+                         double* frame_nmse_out,                   /* optional [n_points][frames_per_point][4] */
+                         int flags);
+
 #ifdef __cplusplus
 }
 #endif

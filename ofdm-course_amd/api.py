@@ -1273,6 +1273,46 @@ class RxPlan:
                                           int(frame0), pr, sd_, gb, int(max_frames_per_chunk), *ptrs, flags), "error_study")
         return _error_result(self, device is not None, max(fpp, 0), arrs)
 
+    def estimator_study(self, SNRs, frames_per_point, h=None, fading=None, mmse="ls", seeds=None, seed=1, frame0=0, device=None,
+                        want_frames=False, max_frames_per_chunk=0):
+        """The estimator comparison of Task 5 in one device-resident call (ofdm_estimator_study): LS_CE, MMSE_CE, MP_estimate and
+        OMP_estimate on the same received frame of every channel realisation (T5/Task5_part2.m:148-205, :269-304; over SNR
+        T5/Main_model_Task_5.m:303-346).  For every SNR of `SNRs` the frames frame0 .. frame0 + frames_per_point - 1 of
+        tx_frames_fused(h or fading, SNR, seeds[p]), bit for bit, through the estimator stages of task5_part2_tile, each estimate
+        equalised and demapped against the frame's own payload.  The plan's receiver modes (MMSE, mmse-ls, OMP route) are not read;
+        a plan with a DeScrambler is refused.  mmse="ls": MMSE_CE with h = ifft(H_LS) of the frame at the point's SNR
+        (Main_model_Task_5.m:314-315); mmse="genie": with the frame's true taps (Task5_part2.m:176-177), a frame with no tap below
+        N_carrier counted in nmse_dropped.
+        Returns dict(rows=("LS", "MMSE", "MP", "OMP"), the order of every trailing 4; errors=[n_points, 4] int64 bit errors,
+        bits=bits counted per point and row, BER = errors / bits; nmse_sums=[n_points, 4] float64, per point the sum over its
+        frames, in frame order, of sum_k |fft(h_f, Nfft)(k) - H_e,f(k)|^2 on carriers 1..N_carrier, a frame whose sum is not
+        finite left out and counted in nmse_dropped=[n_points, 4] int64; NMSE = nmse_sums / ((frames_per_point - nmse_dropped)
+        * N_carrier), the normalisation of ber_sweep(want_nmse=True) with the dropped frames taken out (+ frame_errors=[n_points,
+        frames_per_point, 4] int64 / uint32, frame_nmse=[n_points, frames_per_point, 4] float64 with want_frames)); torch tensors
+        on `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on
+        max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace)."""
+        try:
+            mode = {"ls": 0, "genie": 1}[mmse]
+        except (KeyError, TypeError):
+            raise OfdmError('estimator_study: mmse must be "ls" or "genie"') from None
+        keep, n, chan, _, _, pts = self._study_args("estimator_study", SNRs, seeds, seed, h, fading, None, None, None)
+        fpp = int(frames_per_point)
+        fa = max(fpp, 0)
+        (err, ns, drop, fe, fn), ptrs, flags = self._outputs(
+            device, ((n, 4), np.uint64), ((n, 4), np.float64), ((n, 4), np.uint64), ((n, fa, 4), np.uint32) if want_frames else None,
+            ((n, fa, 4), np.float64) if want_frames else None)
+        L.check(self.lib.ofdm_estimator_study(self.handle, *chan, *pts, fpp, int(frame0), mode, int(max_frames_per_chunk), *ptrs,
+                                              flags), "estimator_study")
+        (err, drop), _, f64 = self._counts(device, None, err, drop)
+        bits = fa * self.frame_bits
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
+            ber = f64(err) / float(bits) if bits else f64(err) * float("nan")
+            nmse = ns / (f64(fpp - drop) * float(self.N_carrier))
+        out = dict(rows=("LS", "MMSE", "MP", "OMP"), errors=err, bits=bits, BER=ber, nmse_sums=ns, nmse_dropped=drop, NMSE=nmse)
+        if want_frames:
+            out.update(frame_errors=fe, frame_nmse=fn)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):

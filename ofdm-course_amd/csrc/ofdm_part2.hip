@@ -12,8 +12,12 @@
 //   NMSE of the four estimates                     (:202-205)      p2_nmse_kernel against H = fft(h_jj)
 //   equalize_signal -> get_payload -> demapping -> BER_func, four times (:269-304)   eq_demap_kernel (ofdm_chain_split.hip)
 // Nothing returns to the host but 4 x n NMSE values and 4 x n error counts.
+// From the demodulator to the four H buffers and the four error rows the stages are ONE body, est_body_run (est_body.hpp), that this
+// tile, the MSE(SNR) tile below and the estimator study (ofdm_est_study.hip) call; each has its own front end and its own error
+// kernel behind it.
 #include <algorithm>
 
+#include "est_body.hpp"
 #include "mmse_levinson.hpp"
 #include "mmse_tau.hpp"
 #include "omp_wide_host.hpp"
@@ -259,99 +263,27 @@ __global__ __launch_bounds__(256) void p2_nmse_kernel(const int32_t* __restrict_
 template <typename T>
 static int part2_tile_run(ofdm_rx_plan* pl, const void* dtx, const int32_t* ddelay, const c64* damp, int n_ch, int64_t F,
                           const double* dcvals, double inv_snr, const void* dref1, double* dnmse, uint32_t* derrs) {
-  const int N = pl->nfft, Tg = pl->t_guard, S = pl->n_symb, np = pl->np, nc = pl->n_carrier, taps = pl->taps;
-  const int64_t len = (int64_t)(N + Tg) * S;
-  const bool f64 = std::is_same<T, double>::value;
+  const int N = pl->nfft, nc = pl->n_carrier;
+  const int64_t len = (int64_t)(N + pl->t_guard) * pl->n_symb;
   hipStream_t st = ctx().stream;
-  // arena
-  size_t need = 0;
-  auto reserve = [&](size_t bytes) { const size_t o = need; need += (bytes + 255) & ~size_t(255); return o; };
-  const size_t o_rx = reserve(sizeof(cx<T>) * (size_t)len * F), o_x = reserve(sizeof(cx<T>) * (size_t)nc * S * F);
-  const size_t o_v = reserve(sizeof(cx<T>) * (size_t)np * F), o_ref = reserve((size_t)pl->frame_words * 4 * F);
-  size_t o_h[4];
-  for (int e = 0; e < 4; ++e) o_h[e] = reserve(sizeof(cx<T>) * (size_t)nc * F);
-  if (pl->ws_t4_bytes < need) {                                     // the Task-4 arena doubles as this entry's
-    OFDM_HIP(hipStreamSynchronize(st));
-    if (pl->ws_t4) { (void)hipFree(pl->ws_t4); pl->ws_t4 = nullptr; pl->ws_t4_bytes = 0; }
-    OFDM_HIP(hipMalloc(&pl->ws_t4, need));
-    pl->ws_t4_bytes = need;
-  }
-  unsigned char* arena = (unsigned char*)pl->ws_t4;
-  cx<T>* drx = (cx<T>*)(arena + o_rx);
-  cx<T>* dxk = (cx<T>*)(arena + o_x);
-  cx<T>* dv = (cx<T>*)(arena + o_v);
-  uint32_t* dref = (uint32_t*)(arena + o_ref);
-  cx<T>* dh[4];
-  for (int e = 0; e < 4; ++e) dh[e] = (cx<T>*)(arena + o_h[e]);
-  // spline operator of interpolate.m (LS_CE.m:31, MMSE_CE.m:38): built once per plan, double
-  if (!pl->d_p2_sop) {
-    std::vector<double> W;
-    OFDM_TRY(build_interpolate_operator(pl->pilot_loc.data(), np, nc, 's', W));
-    OFDM_HIP(hipMalloc(&pl->d_p2_sop, sizeof(double) * W.size()));
-    OFDM_HIP(hipMemcpy(pl->d_p2_sop, W.data(), sizeof(double) * W.size(), hipMemcpyHostToDevice));
-  }
-  FastPlanView pv;
-  make_plan_view(pl, pv);
-  pv.ev = nullptr;
-  pv.d_wt = nullptr;
-  pv.mmse_ls = 0;
-  FastParams<T> P;
-  const void* tw = nullptr;
-  OFDM_TRY(get_twiddles(N, f64, &tw));
-  OFDM_TRY(fast_params_prepare<T>(pv, tw, F, P));
-  // channel, demodulator, pilot LS values
+  // the front end's share of the arena: the realisations' frames and the reference bits of each
+  const size_t o_ref = (sizeof(cx<T>) * (size_t)len * F + 255) & ~size_t(255);
+  unsigned char *front, *body;
+  OFDM_TRY(est_arena(pl, o_ref + (size_t)pl->frame_words * 4 * F, F, &front, &body));
+  cx<T>* drx = (cx<T>*)front;
+  uint32_t* dref = (uint32_t*)(front + o_ref);
+  const EstBodyArgs a{"task5_part2_tile", 585, 585, dref, derrs, dcvals, inv_snr, nullptr};
+  OFDM_TRY(est_body_check(pl, a.what, a.mmse_max_np, a.mmse_named_np, a.cvals == nullptr));
+  // channel (:160-166); every realisation compares against the one reference
   hipLaunchKernelGGL(fir_multi_kernel<T>, dim3((unsigned)std::min<int64_t>((len + 255) / 256, 256), (unsigned)F), dim3(256), 0, st,
                      (const cx<T>*)dtx, len, ddelay, damp, n_ch, drx);
   OFDM_TRY(check_launch("fir_multi_kernel"));
-  OFDM_TRY(demod_keep_device(drx, dxk, N, F * S, Tg, nc, f64));
-  hipLaunchKernelGGL(p2_pilot_ls_kernel<T>, dim3(cdiv_u(F * np, 256)), dim3(256), 0, st, (const cx<T>*)dxk, (const int32_t*)pl->d_pc0,
-                     (const cx<T>*)pl->d_pilots, P.ypil, np, S, nc, F);
   hipLaunchKernelGGL(p2_replicate_kernel<T>, dim3(cdiv_u(F * pl->frame_words, 256)), dim3(256), 0, st, (const uint32_t*)dref1, dref,
                      pl->frame_words, F);
-  // LS: H = Sop * Y
-  const dim3 og(cdiv_u(nc, 128), cdiv_u(F, P2_FT));
-  hipLaunchKernelGGL(p2_apply_operator_kernel<T>, og, dim3(128), sizeof(cx<T>) * np * P2_FT, st, (const double*)pl->d_p2_sop,
-                     (const cx<T>*)P.ypil, dh[0], nc, np, F);
-  // MMSE: v = rf2 (rf2 + I/snr)^-1 Y per realisation, H = Sop * v
-  {
-    const size_t dyn = sizeof(c64) * 4 * (size_t)np * 4;
-    OFDM_ARG(np <= 585, "task5_part2_tile: MMSE stage supports at most 585 pilots");
-    OFDM_HIP(hipFuncSetAttribute((const void*)mmse_wave_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(mmse_wave_kernel<T>, dim3(cdiv_u(F, 4)), dim3(256), dyn, st, (const cx<T>*)P.ypil, dcvals, inv_snr, np, dv, F);
-    hipLaunchKernelGGL(p2_apply_operator_kernel<T>, og, dim3(128), sizeof(cx<T>) * np * P2_FT, st, (const double*)pl->d_p2_sop,
-                       (const cx<T>*)dv, dh[1], nc, np, F);
-  }
-  OFDM_TRY(check_launch("LS / MMSE stage"));
-  // MP: taps -> equalise (H written to dh[2])
-  {
-    OFDM_ARG(pl->k_atoms >= np, "MP_estimate: the loop bound is Np columns (MP_estimate.m:10) but the dictionary has fewer");
-    const int kc = np;
-    const MpLayout lay = mp_layout<T>(np, kc, taps);
-    OFDM_ARG(lay.total <= 150 * 1024, "task5_part2_tile: MP stage needs %u bytes of LDS", lay.total);
-    const unsigned grid = cdiv_u(F, 4 * lay.fpw);
-    const bool mfma = !f64 && (kc % 16 == 0) && (np % 4 == 0) && !getenv("OFDM_MP_NO_MFMA");
-    if (mfma) {
-      if constexpr (!f64) {
-        OFDM_HIP(hipFuncSetAttribute((const void*)mp_batch_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
-        hipLaunchKernelGGL((mp_batch_kernel<float, true>), dim3(grid), dim3(256), lay.total, st, P, lay, kc, F);
-      }
-    } else {
-      OFDM_HIP(hipFuncSetAttribute((const void*)mp_batch_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
-      hipLaunchKernelGGL((mp_batch_kernel<T, false>), dim3(grid), dim3(256), lay.total, st, P, lay, kc, F);
-    }
-    OFDM_TRY(check_launch("mp_batch_kernel"));
-    OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, dref, derrs + 2 * F, dh[2], nullptr, nullptr, 0, 0));
-  }
-  // OMP
-  OFDM_TRY(omp_stage_run<T>(P, N, F));
-  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, dref, derrs + 3 * F, dh[3], nullptr, nullptr, 0, 0));
-  // LS, MMSE: equalise with the given H
-  P.h_in = dh[0];
-  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, true, F, nullptr, dref, derrs + 0 * F, nullptr, nullptr, nullptr, 0, 0));
-  P.h_in = dh[1];
-  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, true, F, nullptr, dref, derrs + 1 * F, nullptr, nullptr, nullptr, 0, 0));
-  hipLaunchKernelGGL(p2_nmse_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, ddelay, damp, n_ch, N, nc, (const cx<T>*)dh[0],
-                     (const cx<T>*)dh[1], (const cx<T>*)dh[2], (const cx<T>*)dh[3], dnmse, F);
+  EstBodyOut<T> o;
+  OFDM_TRY(est_body_run<T>(pl, a, drx, F, body, o));
+  hipLaunchKernelGGL(p2_nmse_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, ddelay, damp, n_ch, N, nc, (const cx<T>*)o.h[0],
+                     (const cx<T>*)o.h[1], (const cx<T>*)o.h[2], (const cx<T>*)o.h[3], dnmse, F);
   return check_launch("p2_nmse_kernel");
 }
 
@@ -428,36 +360,68 @@ __global__ __launch_bounds__(256) void mse_taps_to_h_kernel(const int32_t* __res
   }
 }
 
-template <typename T>
-static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, int h_len, const int32_t* ddelay, const c64* damp,
-                        int n_ch, const double* snr_db_host, const double* dinv_snr, int64_t F, uint64_t seed, uint32_t stream0,
-                        double* dmse, int flags) {
-  const int N = pl->nfft, Tg = pl->t_guard, S = pl->n_symb, np = pl->np, nc = pl->n_carrier, taps = pl->taps;
-  const int64_t len = (int64_t)(N + Tg) * S;
-  const bool f64 = std::is_same<T, double>::value;
-  hipStream_t st = ctx().stream;
-  const int devflags = (flags & ~OFDM_DEVICE) | OFDM_DEVICE;
-  size_t need = 0;
-  auto reserve = [&](size_t bytes) { const size_t o = need; need += (bytes + 255) & ~size_t(255); return o; };
-  const size_t o_a = reserve(sizeof(cx<T>) * (size_t)len * F), o_b = reserve(sizeof(cx<T>) * (size_t)len * F);
-  const size_t o_x = reserve(sizeof(cx<T>) * (size_t)nc * S * F), o_v = reserve(sizeof(cx<T>) * (size_t)np * F);
-  const size_t o_c = reserve(sizeof(double) * (size_t)F);
-  size_t o_h[4];
-  for (int e = 0; e < 4; ++e) o_h[e] = reserve(sizeof(cx<T>) * (size_t)nc * F);
-  if (pl->ws_t4_bytes < need) {                                     // the Task-4 arena doubles as this entry's
-    OFDM_HIP(hipStreamSynchronize(st));
+// ---- the estimator body (est_body.hpp): its share of the arena, its refusals, its stages
+struct EstBodyLayout {
+  size_t o_x, o_v, o_c, o_h[4], total;
+};
+
+static EstBodyLayout est_body_layout(const ofdm_rx_plan* pl, int64_t F) {
+  const size_t cs = pl->f64 ? sizeof(c64) : sizeof(c32), nc = (size_t)pl->n_carrier, nf = (size_t)F;
+  EstBodyLayout l{};
+  auto reserve = [&](size_t bytes) { const size_t o = l.total; l.total += (bytes + 255) & ~size_t(255); return o; };
+  l.o_x = reserve(cs * nc * pl->n_symb * nf);
+  l.o_v = reserve(cs * (size_t)pl->np * nf);
+  l.o_c = reserve(sizeof(double) * nf);
+  for (int e = 0; e < 4; ++e) l.o_h[e] = reserve(cs * nc * nf);
+  return l;
+}
+
+size_t est_body_bytes(const ofdm_rx_plan* pl, int64_t F) { return est_body_layout(pl, F).total; }
+
+int est_arena(ofdm_rx_plan* pl, size_t front, int64_t F, unsigned char** front_out, unsigned char** body_out) {
+  front = (front + 255) & ~size_t(255);
+  const size_t need = front + est_body_bytes(pl, F);
+  if (pl->ws_t4_bytes < need) {                                     // the Task-4 arena doubles as these entries'
+    OFDM_HIP(hipStreamSynchronize(ctx().stream));
     if (pl->ws_t4) { (void)hipFree(pl->ws_t4); pl->ws_t4 = nullptr; pl->ws_t4_bytes = 0; }
     OFDM_HIP(hipMalloc(&pl->ws_t4, need));
     pl->ws_t4_bytes = need;
   }
-  unsigned char* arena = (unsigned char*)pl->ws_t4;
-  cx<T>* da = (cx<T>*)(arena + o_a);
-  cx<T>* db = (cx<T>*)(arena + o_b);
-  cx<T>* dxk = (cx<T>*)(arena + o_x);
-  cx<T>* dv = (cx<T>*)(arena + o_v);
-  double* dcv = (double*)(arena + o_c);
-  cx<T>* dh[4];
-  for (int e = 0; e < 4; ++e) dh[e] = (cx<T>*)(arena + o_h[e]);
+  *front_out = (unsigned char*)pl->ws_t4;
+  *body_out = (unsigned char*)pl->ws_t4 + front;
+  return OFDM_OK;
+}
+
+// wavefronts per workgroup of mmse_wave_kernel: 4 while their state fits the LDS, fewer for many pilots
+static int mmse_wpw(int np) {
+  int wpw = 4;
+  while (wpw > 1 && sizeof(c64) * 4 * (size_t)np * wpw > 150 * 1024) wpw >>= 1;
+  return wpw;
+}
+
+int est_body_check(const ofdm_rx_plan* pl, const char* what, int mmse_max_np, int mmse_named_np, bool ls_tau) {
+  const int np = pl->np;
+  if (ls_tau) OFDM_ARG(sizeof(c64) * 2 * (size_t)pl->n_carrier <= 150 * 1024, "%s: N_carrier beyond 4800", what);
+  OFDM_ARG(np <= mmse_max_np, "%s: MMSE stage supports at most %d pilots", what, mmse_named_np);
+  OFDM_ARG(pl->k_atoms >= np, "MP_estimate: the loop bound is Np columns (MP_estimate.m:10) but the dictionary has fewer");
+  const unsigned mp_lds = pl->f64 ? mp_layout<double>(np, np, pl->taps).total : mp_layout<float>(np, np, pl->taps).total;
+  OFDM_ARG(mp_lds <= 150 * 1024, "%s: MP stage needs %u bytes of LDS", what, mp_lds);
+  return OFDM_OK;
+}
+
+template <typename T>
+int est_body_run(ofdm_rx_plan* pl, const EstBodyArgs& a, const void* drx, int64_t F, unsigned char* body, EstBodyOut<T>& out) {
+  const int N = pl->nfft, Tg = pl->t_guard, S = pl->n_symb, np = pl->np, nc = pl->n_carrier, taps = pl->taps;
+  const bool f64 = std::is_same<T, double>::value;
+  hipStream_t st = ctx().stream;
+  OFDM_TRY(est_body_check(pl, a.what, a.mmse_max_np, a.mmse_named_np, a.cvals == nullptr));
+  const EstBodyLayout l = est_body_layout(pl, F);
+  cx<T>* dxk = (cx<T>*)(body + l.o_x);
+  cx<T>* dv = (cx<T>*)(body + l.o_v);
+  double* dcv = (double*)(body + l.o_c);
+  cx<T>** dh = out.h;
+  for (int e = 0; e < 4; ++e) dh[e] = (cx<T>*)(body + l.o_h[e]);
+  // spline operator of interpolate.m (LS_CE.m:31, MMSE_CE.m:38): built once per plan, double
   if (!pl->d_p2_sop) {
     std::vector<double> W;
     OFDM_TRY(build_interpolate_operator(pl->pilot_loc.data(), np, nc, 's', W));
@@ -473,45 +437,37 @@ static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, 
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(N, f64, &tw));
   OFDM_TRY(fast_params_prepare<T>(pv, tw, F, P));
-  // Tx for every point -> Noise at the point's SNR (:307) -> conv truncated (:308-309) -> demodulator (:311) -> Y (:328)
-  const int words = (int)(len * (int64_t)(sizeof(cx<T>) / 4));
-  OFDM_ARG((int64_t)words * F < ((int64_t)1 << 40), "task5_mse_tile: tile too large");
-  hipLaunchKernelGGL(p2_replicate_kernel<T>, dim3(cdiv_u((int64_t)F * words, 256)), dim3(256), 0, st, (const uint32_t*)dtx, (uint32_t*)da,
-                     words, F);
-  OFDM_TRY(check_launch("p2_replicate_kernel"));
-  OFDM_TRY(ofdm_Noise_frames_snr(snr_db_host, da, len, F, seed, stream0, da, devflags));
-  OFDM_TRY(ofdm_channel_conv_frames(da, len, F, h_dense, h_len, db, devflags));
-  OFDM_TRY(demod_keep_device(db, dxk, N, F * S, Tg, nc, f64));
+  // demodulator, pilot LS values Y
+  OFDM_TRY(demod_keep_device(drx, dxk, N, F * S, Tg, nc, f64));
   hipLaunchKernelGGL(p2_pilot_ls_kernel<T>, dim3(cdiv_u(F * np, 256)), dim3(256), 0, st, (const cx<T>*)dxk, (const int32_t*)pl->d_pc0,
                      (const cx<T>*)pl->d_pilots, P.ypil, np, S, nc, F);
-  // LS_CE (:313): H = Sop * Y
+  // LS_CE: H = Sop * Y
   const dim3 og(cdiv_u(nc, 128), cdiv_u(F, P2_FT));
   hipLaunchKernelGGL(p2_apply_operator_kernel<T>, og, dim3(128), sizeof(cx<T>) * np * P2_FT, st, (const double*)pl->d_p2_sop,
                      (const cx<T>*)P.ypil, dh[0], nc, np, F);
-  // MMSE_CE (:314-315): tau_rms of ifft(H_est_LS), then v = rf2 (rf2 + I/snr_i)^-1 Y, H = Sop * v
+  // MMSE_CE: [tau_rms of ifft(H_est_LS),] v = rf2 (rf2 + I/snr)^-1 Y per frame, H = Sop * v
   {
-    const size_t tdyn = sizeof(c64) * 2 * (size_t)nc;
-    OFDM_ARG(tdyn <= 150 * 1024, "task5_mse_tile: N_carrier beyond 4800");
-    OFDM_HIP(hipFuncSetAttribute((const void*)mse_tau_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tdyn));
-    const double nps = (double)pl->pilot_loc[1] - (double)pl->pilot_loc[0];                    // MMSE_CE.m:15
-    hipLaunchKernelGGL(mse_tau_kernel<T>, dim3((unsigned)F), dim3(256), tdyn, st, (const cx<T>*)dh[0], nc, nps, dcv);
-    int wpw = 4;
-    while (wpw > 1 && sizeof(c64) * 4 * (size_t)np * wpw > 150 * 1024) wpw >>= 1;
+    const double* cv = a.cvals;
+    if (!cv) {
+      const size_t tdyn = sizeof(c64) * 2 * (size_t)nc;
+      OFDM_HIP(hipFuncSetAttribute((const void*)mse_tau_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tdyn));
+      const double nps = (double)pl->pilot_loc[1] - (double)pl->pilot_loc[0];                    // MMSE_CE.m:15
+      hipLaunchKernelGGL(mse_tau_kernel<T>, dim3((unsigned)F), dim3(256), tdyn, st, (const cx<T>*)dh[0], nc, nps, dcv);
+      cv = dcv;
+    }
+    const int wpw = mmse_wpw(np);
     const size_t dyn = sizeof(c64) * 4 * (size_t)np * wpw;
-    OFDM_ARG(dyn <= 150 * 1024, "task5_mse_tile: MMSE stage supports at most 2343 pilots");
     OFDM_HIP(hipFuncSetAttribute((const void*)mmse_wave_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(mmse_wave_kernel<T>, dim3(cdiv_u(F, wpw)), dim3(64 * wpw), dyn, st, (const cx<T>*)P.ypil, (const double*)dcv, 0.0, np,
-                       dv, F, dinv_snr);
+    hipLaunchKernelGGL(mmse_wave_kernel<T>, dim3(cdiv_u(F, wpw)), dim3(64 * wpw), dyn, st, (const cx<T>*)P.ypil, cv, a.inv_snr, np, dv, F,
+                       a.inv_snr_v);
     hipLaunchKernelGGL(p2_apply_operator_kernel<T>, og, dim3(128), sizeof(cx<T>) * np * P2_FT, st, (const double*)pl->d_p2_sop,
                        (const cx<T>*)dv, dh[1], nc, np, F);
   }
   OFDM_TRY(check_launch("LS / MMSE stage"));
-  // MP_estimate (:330)
+  // MP_estimate: the picks and coefficients into the plan's tap workspace
   {
-    OFDM_ARG(pl->k_atoms >= np, "MP_estimate: the loop bound is Np columns (MP_estimate.m:10) but the dictionary has fewer");
     const int kc = np;
     const MpLayout lay = mp_layout<T>(np, kc, taps);
-    OFDM_ARG(lay.total <= 150 * 1024, "task5_mse_tile: MP stage needs %u bytes of LDS", lay.total);
     const unsigned grid = cdiv_u(F, 4 * lay.fpw);
     const bool mfma = !f64 && (kc % 16 == 0) && (np % 4 == 0) && !getenv("OFDM_MP_NO_MFMA");
     if (mfma) {
@@ -523,17 +479,63 @@ static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, 
       OFDM_HIP(hipFuncSetAttribute((const void*)mp_batch_kernel<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total));
       hipLaunchKernelGGL((mp_batch_kernel<T, false>), dim3(grid), dim3(256), lay.total, st, P, lay, kc, F);
     }
-    hipLaunchKernelGGL(mse_taps_to_h_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, (const int32_t*)P.tap_idx, (const c64*)P.tap_x, taps, N, nc,
-                       dh[2]);
-    OFDM_TRY(check_launch("MP stage"));
+    OFDM_TRY(check_launch("mp_batch_kernel"));
   }
-  // OMP_estimate (:331)
+  // The tap workspace holds one pursuit at a time, so MP's taps are turned into H before OMP_estimate overwrites them.  The body
+  // ends in one of two tails.
+  if (!a.ref) {
+    // estimates only: H of MP and OMP is the transform of their taps
+    auto taps_to_h = [&](cx<T>* h) {
+      hipLaunchKernelGGL(mse_taps_to_h_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, (const int32_t*)P.tap_idx, (const c64*)P.tap_x, taps, N,
+                         nc, h);
+    };
+    taps_to_h(dh[2]);
+    OFDM_TRY(omp_stage_run<T>(P, N, F));
+    taps_to_h(dh[3]);
+    return check_launch("mse_taps_to_h_kernel");
+  }
+  // with the equaliser: the equalise stage writes H of MP and OMP beside their bit errors; LS and MMSE are equalised with their H
+  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, a.ref, a.errs + 2 * F, dh[2], nullptr, nullptr, 0, 0));
   OFDM_TRY(omp_stage_run<T>(P, N, F));
-  hipLaunchKernelGGL(mse_taps_to_h_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, (const int32_t*)P.tap_idx, (const c64*)P.tap_x, taps, N, nc,
-                     dh[3]);
+  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, false, F, nullptr, a.ref, a.errs + 3 * F, dh[3], nullptr, nullptr, 0, 0));
+  P.h_in = dh[0];
+  OFDM_TRY(eq_demap_run<T>(pv, P, dxk, nc, true, F, nullptr, a.ref, a.errs + 0 * F, nullptr, nullptr, nullptr, 0, 0));
+  P.h_in = dh[1];
+  return eq_demap_run<T>(pv, P, dxk, nc, true, F, nullptr, a.ref, a.errs + 1 * F, nullptr, nullptr, nullptr, 0, 0);
+}
+template int est_body_run<float>(ofdm_rx_plan*, const EstBodyArgs&, const void*, int64_t, unsigned char*, EstBodyOut<float>&);
+template int est_body_run<double>(ofdm_rx_plan*, const EstBodyArgs&, const void*, int64_t, unsigned char*, EstBodyOut<double>&);
+
+template <typename T>
+static int mse_tile_run(ofdm_rx_plan* pl, const void* dtx, const void* h_dense, int h_len, const int32_t* ddelay, const c64* damp,
+                        int n_ch, const double* snr_db_host, const double* dinv_snr, int64_t F, uint64_t seed, uint32_t stream0,
+                        double* dmse, int flags) {
+  const int N = pl->nfft, nc = pl->n_carrier;
+  const int64_t len = (int64_t)(N + pl->t_guard) * pl->n_symb;
+  hipStream_t st = ctx().stream;
+  const int devflags = (flags & ~OFDM_DEVICE) | OFDM_DEVICE;
+  // the front end's share of the arena: the points' noisy frames, and the received ones
+  const size_t o_b = (sizeof(cx<T>) * (size_t)len * F + 255) & ~size_t(255);
+  unsigned char *front, *body;
+  OFDM_TRY(est_arena(pl, 2 * o_b, F, &front, &body));
+  cx<T>* da = (cx<T>*)front;
+  cx<T>* db = (cx<T>*)(front + o_b);
+  // no equaliser (:334-344 compare estimates only); tau_rms of ifft(H_est_LS), every point at its own SNR (:314-315)
+  const EstBodyArgs a{"task5_mse_tile", 2400, 2343, nullptr, nullptr, nullptr, 0.0, dinv_snr};
+  OFDM_TRY(est_body_check(pl, a.what, a.mmse_max_np, a.mmse_named_np, a.cvals == nullptr));
+  // Tx for every point -> Noise at the point's SNR (:307) -> conv truncated (:308-309)
+  const int words = (int)(len * (int64_t)(sizeof(cx<T>) / 4));
+  OFDM_ARG((int64_t)words * F < ((int64_t)1 << 40), "task5_mse_tile: tile too large");
+  hipLaunchKernelGGL(p2_replicate_kernel<T>, dim3(cdiv_u((int64_t)F * words, 256)), dim3(256), 0, st, (const uint32_t*)dtx, (uint32_t*)da,
+                     words, F);
+  OFDM_TRY(check_launch("p2_replicate_kernel"));
+  OFDM_TRY(ofdm_Noise_frames_snr(snr_db_host, da, len, F, seed, stream0, da, devflags));
+  OFDM_TRY(ofdm_channel_conv_frames(da, len, F, h_dense, h_len, db, devflags));
+  EstBodyOut<T> o;
+  OFDM_TRY(est_body_run<T>(pl, a, db, F, body, o));
   // the four errors against fft(h)(1..N_carrier) (:334-344)
-  hipLaunchKernelGGL(p2_nmse_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, ddelay, damp, n_ch, N, nc, (const cx<T>*)dh[0],
-                     (const cx<T>*)dh[1], (const cx<T>*)dh[2], (const cx<T>*)dh[3], dmse, F);
+  hipLaunchKernelGGL(p2_nmse_kernel<T>, dim3((unsigned)F), dim3(256), 0, st, ddelay, damp, n_ch, N, nc, (const cx<T>*)o.h[0],
+                     (const cx<T>*)o.h[1], (const cx<T>*)o.h[2], (const cx<T>*)o.h[3], dmse, F);
   return check_launch("p2_nmse_kernel");
 }
 
