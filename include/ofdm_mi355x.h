@@ -1182,6 +1182,65 @@ int ofdm_estimator_study(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, 
                          double* frame_nmse_out,                   /* optional [n_points][frames_per_point][4] */
                          int flags);
 
+/* The estimator comparison of Task 5 with its two pictures, as one device-resident call: ofdm_estimator_study (the same arguments,
+ * the same frames, the same launches; errors_out .. frame_nmse_out are its outputs bit for bit) and, summed over the frames of
+ * every point, |H_freq| against |H_est_LS|, |H_est_MMSE|, |H_est_MP|, |H_est_OMP| over the carriers
+ * (T5/Main_model_Task_5.m:207-231) and |H_tau| against the delays OMP_estimate picked (:238-242), with the histogram of the
+ * frames' error.  Every [4] is in the order LS, MMSE, MP, OMP; K is the plan's dictionary columns, T its dominant_taps.
+ *   per carrier: true_amp_sums_out[p][k] = sum_f |H_f(k)| over all frames; est_amp_sums_out[p][e][k] = sum_f |H_e,f(k)|,
+ *     err_sums_out = sum_f |H_f(k) - H_e,f(k)|^2, amp_err_sums_out = sum_f (|H_e,f(k)| - |H_f(k)|)^2, in frame order, a frame whose
+ *     frame_nmse[f][e] is not finite left out of the three sums of e: the rule and the count of nmse_dropped_out[p][e].
+ *     |z| = sqrt(re re + im im) in double, the products and the sum rounded one by one.
+ *   the histogram: nmse_hist_out[p][e][b] counts the frames by 10 log10(frame_nmse / N_carrier) on hist_bins bins of equal width
+ *     on [hist_lo_db, hist_hi_db), compared against the table of linear thresholds N_carrier 10^(edge / 10) as ofdm_hest_study
+ *     does (thresholds_out, HOST [hist_bins + 1] whatever the flags); nmse_below_out / nmse_above_out / nmse_nan_out: the frames
+ *     under the grid, over it, and those whose error is not finite (= nmse_dropped_out); the four sum to frames_per_point.
+ *   per delay, OMP_estimate only: pick_hist_out[p][k] counts the pick slots whose 0-based delay is k (index - 1 of
+ *     OMP_estimate.m:11), tap_amp_sums_out[p][k] = sum |x| of those slots in frame order (a pick repeated later holds 0 in its
+ *     earlier slot, so this is sum_f |est_fade_chan_f(k)|); n_picks_hist_out[p][j]: the frames that made j picks (the
+ *     relative-change stop of OMP_estimate.m:20); true_tap_amp_sums_out[p][k] = sum_f |a_f,t| of the channel tap with delay
+ *     d_t = k < K (the frame's own amplitudes with tap_delay / tap_power, the static channel's otherwise); true_outside_out[p]:
+ *     the channel taps with d_t >= K, counted per frame; support_out[p] = {hits, misses, false}: the delays in both the frame's
+ *     true support (d_t < K) and its distinct picks, in the true support only, in the picks only, summed over the frames.
+ *     picks_out (1-based, 0 = not made) and tap_x_out (complex double whatever the plan's precision) keep every frame's slots.
+ *   MP_estimate's delay-domain curve is not offered: the tap workspace holds one pursuit at a time, and the estimator stages turn
+ *     MP's taps into H before OMP_estimate overwrites them.  MP's per-carrier rows are there.
+ * The outputs are overwritten; every output is bitwise independent of the chunking, and a call over frames frame0 .. equals the
+ * calls over its parts with the integers added.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth of
+ * the workspaces.  OFDM_ERR_ARG, before anything is launched or written: what ofdm_estimator_study refuses, in its words under
+ * the name estimator_profile (up to and including mmse_mode); hist_bins 1 .. 4096 and finite hist_lo_db < hist_hi_db; an output is
+ * given; then what ofdm_task5_part2_tile refuses of a plan, in its words. */
+int ofdm_estimator_profile(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST, complex in the plan's precision, or NULL / 0 */
+                           const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                           const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                           int64_t n_points, int64_t frames_per_point, int64_t frame0,
+                           int mmse_mode,                            /* 0 ls | 1 genie */
+                           int64_t max_frames_per_chunk,
+                           int hist_bins, double hist_lo_db, double hist_hi_db,
+                           uint64_t* errors_out,                     /* optional [n_points][4] */
+                           double* nmse_sums_out,                    /* optional [n_points][4] */
+                           uint64_t* nmse_dropped_out,               /* optional [n_points][4] */
+                           uint32_t* frame_errors_out,               /* optional [n_points][frames_per_point][4] */
+                           double* frame_nmse_out,                   /* optional [n_points][frames_per_point][4] */
+                           double* true_amp_sums_out,                /* optional [n_points][N_carrier] */
+                           double* est_amp_sums_out,                 /* optional [n_points][4][N_carrier] */
+                           double* err_sums_out,                     /* optional [n_points][4][N_carrier] */
+                           double* amp_err_sums_out,                 /* optional [n_points][4][N_carrier] */
+                           uint64_t* nmse_hist_out,                  /* optional [n_points][4][hist_bins] */
+                           uint64_t* nmse_below_out,                 /* optional [n_points][4] */
+                           uint64_t* nmse_above_out,                 /* optional [n_points][4] */
+                           uint64_t* nmse_nan_out,                   /* optional [n_points][4] */
+                           double* thresholds_out,                   /* optional HOST [hist_bins + 1] */
+                           uint64_t* pick_hist_out,                  /* optional [n_points][K] */
+                           double* tap_amp_sums_out,                 /* optional [n_points][K] */
+                           uint64_t* n_picks_hist_out,               /* optional [n_points][T + 1] */
+                           double* true_tap_amp_sums_out,            /* optional [n_points][K] */
+                           uint64_t* true_outside_out,               /* optional [n_points] */
+                           uint64_t* support_out,                    /* optional [n_points][3] */
+                           int32_t* picks_out,                       /* optional [n_points][frames_per_point][T] */
+                           void* tap_x_out,                          /* optional [n_points][frames_per_point][T] complex double */
+                           int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,7 @@ SIGNATURES = {
     "ofdm_error_study": [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _i64, _vp, _i, _i, _i64,
                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_estimator_study": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i],
+    "ofdm_estimator_profile": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _i64, _i, _d, _d] + [_vp] * 22 + [_i],
 }
 _RESTYPES = {"ofdm_last_error_string": C.c_char_p, "ofdm_rx_plan_frame_bytes": C.c_int64}
 

@@ -1313,6 +1313,79 @@ class RxPlan:
             out.update(frame_errors=fe, frame_nmse=fn)
         return out
 
+    def estimator_profile(self, SNRs, frames_per_point, h=None, fading=None, mmse="ls", bins=dict(n=60, lo=-50.0, hi=10.0), seeds=None,
+                          seed=1, frame0=0, device=None, want_frames=False, max_frames_per_chunk=0):
+        """estimator_study with its two pictures, in one device-resident call (ofdm_estimator_profile): per point the curves
+        |H_freq| against |H_est_LS|, |H_est_MMSE|, |H_est_MP|, |H_est_OMP| over the carriers (T5/Main_model_Task_5.m:207-231) and
+        |H_tau| against the delays OMP_estimate picked (:238-242), summed over the point's frames, with the histogram of the
+        frames' error.  The arguments of estimator_study plus bins = dict(n, lo, hi), the histogram of the frames by
+        10 log10(frame_nmse / N_carrier) in dB; the same frames, the same refusals under the name estimator_profile.
+        Returns everything estimator_study returns for the same arguments, bit for bit (rows, errors, bits, BER, nmse_sums,
+        nmse_dropped, NMSE (+ frame_errors, frame_nmse with want_frames)), and, with nc = N_carrier, K = the plan's dictionary
+        columns, T = dominant_taps:
+        true_amp_sums=[n_points, nc] float64 = sum_f |H_f(k)| over all frames; est_amp_sums, err_sums, amp_err_sums=[n_points, 4,
+        nc] = sum_f |H_e,f(k)|, sum_f |H_f(k) - H_e,f(k)|^2, sum_f (|H_e,f(k)| - |H_f(k)|)^2 in frame order, a frame whose
+        frame_nmse[e] is not finite left out (the rule and the count of nmse_dropped); mean_true_amp = true_amp_sums /
+        frames_per_point, mean_est_amp = est_amp_sums / (frames_per_point - nmse_dropped), nmse_profile = err_sums /
+        (frames_per_point - nmse_dropped);
+        nmse_hist=[n_points, 4, bins.n], nmse_below, nmse_above, nmse_nan=[n_points, 4] int64 (their sum is frames_per_point;
+        nmse_nan = nmse_dropped), edges=[bins.n + 1] in dB and thresholds=[bins.n + 1] = N_carrier 10^(edges / 10), the table the
+        frames were compared against (numpy, made on the host);
+        for OMP_estimate: pick_hist=[n_points, K] int64, the pick slots whose 0-based delay is k; tap_amp_sums=[n_points, K]
+        float64 = sum |x| of those slots (sum_f |est_fade_chan_f(k)|); n_picks_hist=[n_points, T + 1] int64, the frames by the
+        number of picks made; true_tap_amp_sums=[n_points, K] = sum_f |a_f,t| at each channel tap's delay d_t < K;
+        true_outside=[n_points] int64, the channel taps with d_t >= K counted per frame; support_hits, support_misses,
+        support_false=[n_points] int64: the delays in both the frame's true support (d_t < K) and its distinct picks, in the
+        true support only, in the picks only (+ picks=[n_points, frames_per_point, T] int32, 1-based, 0 = not made, and
+        tap_x=[n_points, frames_per_point, T] complex128 with want_frames).  MP_estimate's delay-domain curve is not offered: the
+        tap workspace holds one pursuit at a time; its per-carrier rows are there.
+        torch tensors on `device` (no host synchronisation) when it is given, numpy arrays otherwise.  No output depends on
+        max_frames_per_chunk (> 0: the frames of a chunk of the plan-owned workspace)."""
+        try:
+            mode = {"ls": 0, "genie": 1}[mmse]
+        except (KeyError, TypeError):
+            raise OfdmError('estimator_profile: mmse must be "ls" or "genie"') from None
+        try:
+            extra = set(bins) - {"n", "lo", "hi"}
+            bn, blo, bhi = int(bins["n"]), float(bins["lo"]), float(bins["hi"])
+        except (TypeError, KeyError, ValueError):
+            raise OfdmError("estimator_profile: bins must be dict(n=, lo=, hi=)") from None
+        if extra:
+            raise OfdmError(f"estimator_profile: unknown bins keys {sorted(extra)}")
+        keep, n, chan, _, _, pts = self._study_args("estimator_profile", SNRs, seeds, seed, h, fading, None, None, None)
+        fpp = int(frames_per_point)
+        fa, nb = max(fpp, 0), bn if 1 <= bn <= 4096 else 0       # (a bad count is the library's refusal)
+        nc, K, T = self.N_carrier, self.K, self.taps
+        fr = lambda shape, dt: (shape, dt) if want_frames else None
+        (err, ns, drop, fe, fn, tsum, esum, esq, aerr, hist, below, above, hnan, pick, tamp, npk, ttamp, outside, supp, picks, tx), \
+            ptrs, flags = self._outputs(
+                device, ((n, 4), np.uint64), ((n, 4), np.float64), ((n, 4), np.uint64), fr((n, fa, 4), np.uint32),
+                fr((n, fa, 4), np.float64), ((n, nc), np.float64), ((n, 4, nc), np.float64), ((n, 4, nc), np.float64),
+                ((n, 4, nc), np.float64), ((n, 4, nb), np.uint64), ((n, 4), np.uint64), ((n, 4), np.uint64), ((n, 4), np.uint64),
+                ((n, K), np.uint64), ((n, K), np.float64), ((n, T + 1), np.uint64), ((n, K), np.float64), ((n,), np.uint64),
+                ((n, 3), np.uint64), fr((n, fa, T), np.int32), fr((n, fa, T), np.complex128))
+        thr = np.zeros(nb + 1, np.float64)
+        L.check(self.lib.ofdm_estimator_profile(self.handle, *chan, *pts, fpp, int(frame0), mode, int(max_frames_per_chunk), bn, blo,
+                                                bhi, *ptrs[:13], thr.ctypes.data_as(C.c_void_p), *ptrs[13:], flags),
+                "estimator_profile")
+        (err, drop, hist, below, above, hnan, pick, npk, outside, supp), count, f64 = self._counts(
+            device, fpp, err, drop, hist, below, above, hnan, pick, npk, outside, supp)
+        bits = fa * self.frame_bits
+        with np.errstate(divide="ignore", invalid="ignore"):     # no frame counted: NaN, the mean of nothing
+            ber = f64(err) / float(bits) if bits else f64(err) * float("nan")
+            nmse = ns / (f64(fpp - drop) * float(nc))
+            kept = f64(fpp - drop)[..., None]
+            mean_true, mean_est, profile = tsum / count, esum / kept, esq / kept
+        out = dict(rows=("LS", "MMSE", "MP", "OMP"), errors=err, bits=bits, BER=ber, nmse_sums=ns, nmse_dropped=drop, NMSE=nmse,
+                   true_amp_sums=tsum, est_amp_sums=esum, err_sums=esq, amp_err_sums=aerr, mean_true_amp=mean_true,
+                   mean_est_amp=mean_est, nmse_profile=profile, nmse_hist=hist, nmse_below=below, nmse_above=above, nmse_nan=hnan,
+                   edges=np.linspace(blo, bhi, nb + 1), thresholds=thr, pick_hist=pick, tap_amp_sums=tamp, n_picks_hist=npk,
+                   true_tap_amp_sums=ttamp, true_outside=outside, support_hits=supp[:, 0], support_misses=supp[:, 1],
+                   support_false=supp[:, 2])
+        if want_frames:
+            out.update(frame_errors=fe, frame_nmse=fn, picks=picks, tap_x=tx)
+        return out
+
     def ber_sweep(self, SNRs, frames_per_point, h=None, seeds=None, seed=1, frame0=0, Register=None, device=None,
                   want_frame_errors=False, max_frames_per_chunk=0, want_mer=False, want_frame_mer=False, fading=None,
                   want_nmse=False, want_frame_nmse=False, density=None):

@@ -1,6 +1,6 @@
 // The four estimators of Task 5 on a batch of received frames (ofdm_part2.hip): from "received frames drx[F]" to "four H buffers
-// and four error rows".  One body for its three users: ofdm_task5_part2_tile, ofdm_task5_mse_tile and ofdm_estimator_study
-// (ofdm_est_study.hip).  What differs between them is in front of it (how the frames were made) and in EstBodyArgs.
+// and four error rows".  One body for its users: ofdm_task5_part2_tile, ofdm_task5_mse_tile and, through est_study_run
+// (ofdm_est_study.hip), ofdm_estimator_study and ofdm_estimator_profile.  What differs between them is in front of it (how the frames were made) and in EstBodyArgs.
 #pragma once
 
 #include "rx_plan.hpp"
@@ -31,6 +31,8 @@ int est_body_check(const ofdm_rx_plan* pl, const char* what, int mmse_max_np, in
 template <typename T>
 struct EstBodyOut {
   cx<T>* h[4];                   // [F][N_carrier] each: LS, MMSE, MP, OMP
+  const int32_t* tap_idx;        // [F][taps] the plan's tap workspace as the body leaves it: OMP's picks, 0-based, -1 = not made
+  const c64* tap_x;              // [F][taps] their coefficients (a pick repeated later holds 0 in its earlier slot)
 };
 
 // drx: [F][(Nfft + T_guard) N_symb] received frames in the plan's precision; body: est_arena's body_out

@@ -32,8 +32,9 @@ struct EstWanted {
 //   of one point --, h and taps together, the channel) -> a plan with a DeScrambler (the study runs unscrambled, as
 //   Task5_part2.m:104-114 does; the entry takes no Register) -> mmse_mode 0 / 1 -> an output is given.
 // The generator needs data carriers, so a plan without them (comb 1) is the front's refusal whatever the outputs.
-inline int est_study_prelude(const TxfCall& c, bool both_channels, const EstWanted& e, TxfChannel& ch, TxfGains& g, TxfWhy& w) {
-  static const char* const WHAT = "estimator_study";
+// WHAT: the entry as its refusals name it (ofdm_estimator_profile, est_profile_plan.hpp, makes the same checks under its own name).
+inline int est_study_prelude(const TxfCall& c, bool both_channels, const EstWanted& e, TxfChannel& ch, TxfGains& g, TxfWhy& w,
+                             const char* WHAT = "estimator_study") {
   if (const int id = txf_study_prelude(c, both_channels, EST_REFUSE_BOTH, WHAT, ch, g, w, 65535)) return id;
   if (c.plan->descr & TXF_DESCR_ON)
     return txf_refuse(w, EST_REFUSE_DESCR,

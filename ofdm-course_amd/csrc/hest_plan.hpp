@@ -45,6 +45,15 @@ struct HestCapture {
   bool out = false;          // an output is given
 };
 
+// bins of a histogram in dB: n 1 .. 4096, lo < hi, both finite; the refusal in one wording for every entry that takes them
+inline bool hest_bins_ok(const HestBins& b) {
+  return b.n >= 1 && b.n <= HEST_MAX_BINS && b.lo < b.hi && b.lo - b.lo == 0.0 && b.hi - b.hi == 0.0;
+}
+
+inline int hest_refuse_bins(TxfWhy& w, int id, const char* what, const HestBins& b) {
+  return txf_refuse(w, id, "%s: bins must have n 1 .. %d and finite lo < hi (%d, %g, %g)", what, HEST_MAX_BINS, b.n, b.lo, b.hi);
+}
+
 // The capture checks, the last of both entries, in this order: time_desync 0 / 1 -> freq_desync 0 / 1 -> at least two pilots (the
 // spline of estimate_channel.m:8 needs two knots) -> what else the receiver's route refuses for (time_desync, freq_desync,
 // mp_desync 1), in its words -> [the study: bins n 1 .. 4096, lo < hi, both finite] -> an output is given.
@@ -58,10 +67,7 @@ inline int hest_check_capture(const TxfShape& s, const HestCapture& c, const cha
   T4Route r;
   const char* why = nullptr;
   if (t4_route_choose(t4, r, &why) != T4_ROUTE_OK) return txf_refuse(w, HEST_REFUSE_ROUTE, "%s: %s", what, why);
-  if (c.study && !(c.bins.n >= 1 && c.bins.n <= HEST_MAX_BINS && c.bins.lo < c.bins.hi && c.bins.lo - c.bins.lo == 0.0 &&
-                   c.bins.hi - c.bins.hi == 0.0))
-    return txf_refuse(w, HEST_REFUSE_BINS, "%s: bins must have n 1 .. %d and finite lo < hi (%d, %g, %g)", what, HEST_MAX_BINS, c.bins.n,
-                      c.bins.lo, c.bins.hi);
+  if (c.study && !hest_bins_ok(c.bins)) return hest_refuse_bins(w, HEST_REFUSE_BINS, what, c.bins);
   if (!c.out) return txf_refuse(w, HEST_REFUSE_OUTPUT, "%s: no output is given", what);
   return TXF_OK;
 }

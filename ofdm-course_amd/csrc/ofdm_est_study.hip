@@ -21,12 +21,14 @@
 // Task-5 tiles on it (est_body_run, ofdm_part2.hip) with the generator's per-frame reference bits.  mmse = ls: the body's own
 // h = ifft(H_LS) stage (mse_tau_kernel) at the point's SNR (Main_model_Task_5.m:314-315).  The receiver and its route are not
 // involved.  Host side: the checks, the chunk and the launch shapes are est_plan.hpp's; the body's refusals come in the part-2
-// tile's words.
+// tile's words.  The call itself is est_study_run (est_study.hpp), which ofdm_estimator_profile (ofdm_est_profile.hip) shares: the
+// same frames, the same launches in the same order, and its own kernels behind each chunk.
 #include <algorithm>
 #include <cmath>
 
 #include "est_body.hpp"
 #include "est_plan.hpp"
+#include "est_study.hpp"
 #include "mmse_tau.hpp"
 #include "study_accumulate.hpp"
 #include "txf_study.hpp"
@@ -124,7 +126,7 @@ static int est_truth(const ofdm_rx_plan* pl, const c64* amp, int64_t amp_stride,
 template <typename T>
 static int est_chunk_run(ofdm_rx_plan* pl, const EstBodyArgs& a, const void* drx, int64_t nf, unsigned char* body, const c64* htrue,
                          int64_t h_stride, double* frame_nmse, unsigned long long* errors, uint32_t* frame_errors, double* sums,
-                         unsigned long long* dropped) {
+                         unsigned long long* dropped, EstChunkDone& done) {
   EstBodyOut<T> o;
   OFDM_TRY(est_body_run<T>(pl, a, drx, nf, body, o));
   const EstPass p = est_pass(nf);
@@ -134,63 +136,64 @@ static int est_chunk_run(ofdm_rx_plan* pl, const EstBodyArgs& a, const void* drx
   OFDM_TRY(check_launch("est_reduce_kernel"));
   hipLaunchKernelGGL(est_accumulate_kernel, dim3(p.acc_grid), dim3(p.acc_threads), 0, ctx().stream, (const double*)frame_nmse, nf, sums,
                      dropped);
+  for (int e = 0; e < EST_ROWS; ++e) done.h[e] = o.h[e];
+  done.tap_idx = o.tap_idx;
+  done.tap_x = o.tap_x;
   return check_launch("est_accumulate_kernel");
 }
 
-}  // namespace ofdm
-
-using namespace ofdm;
-
-extern "C" int ofdm_estimator_study(ofdm_rx_plan* pl, const void* h, int h_len, const int32_t* tap_delay, const double* tap_power,
-                                    int n_taps, const double* snr_db, const uint64_t* seeds, int64_t n_points,
-                                    int64_t frames_per_point, int64_t frame0, int mmse_mode, int64_t max_frames_per_chunk,
-                                    uint64_t* errors_out, double* nmse_sums_out, uint64_t* nmse_dropped_out,
-                                    uint32_t* frame_errors_out, double* frame_nmse_out, int flags) {
+int est_study_run(const EstStudyCall& call, EstStudyHook* hook) {
+  ofdm_rx_plan* const pl = call.pl;
+  const TxfStudyArgs& g = call.g;
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
-  const TxfStudyArgs g{h, h_len, tap_delay, tap_power, n_taps, 0, 0, 0, 0.0, nullptr, snr_db, seeds, n_points, frames_per_point, frame0,
-                       max_frames_per_chunk, flags};
   const bool fading = g.fading();
   EstWanted want;
-  want.mmse_mode = mmse_mode;
-  want.out = errors_out || nmse_sums_out || nmse_dropped_out || frame_errors_out || frame_nmse_out;
+  want.mmse_mode = call.mmse_mode;
+  want.out = call.errors_out || call.nmse_sums_out || call.nmse_dropped_out || call.frame_errors_out || call.frame_nmse_out ||
+             (hook && hook->out());
   TxfChannel ch;
   TxfFade fade;
   TxfWhy why;
-  OFDM_TRY(txf_refused(est_study_prelude(g.call("estimator_study", pl ? &s : nullptr), g.both_channels(), want, ch, fade.gains, why), why));
+  const TxfCall front = g.call(hook ? hook->what() : "estimator_study", pl ? &s : nullptr);
+  OFDM_TRY(txf_refused(hook ? hook->prelude(front, g.both_channels(), want, ch, fade.gains, why)
+                            : est_study_prelude(front, g.both_channels(), want, ch, fade.gains, why), why));
   // what the part-2 tile refuses of a plan, in its words, before anything is written
-  const bool want_err = errors_out || frame_errors_out;
-  const bool genie = mmse_mode == EST_TAU_GENIE;
+  const bool want_err = call.errors_out || call.frame_errors_out;
+  const bool genie = call.mmse_mode == EST_TAU_GENIE;
   EstBodyArgs ba{"task5_part2_tile", 585, 585, nullptr, nullptr, nullptr, 0.0, nullptr};
   OFDM_ARG(pl->np >= 2, "task5_part2_tile: needs at least two pilots, all inside 1..N_carrier");
   OFDM_ARG(!want_err || chain_split_fits(pl->taps, pl->bps, pl->n_carrier, (int64_t)pl->nd * pl->n_symb, pl->f64 != 0),
            "task5_part2_tile: the frame's decisions do not fit the equalise stage's LDS");
   OFDM_TRY(est_body_check(pl, ba.what, ba.mmse_max_np, ba.mmse_named_np, !genie));
-  if (n_points == 0) return OFDM_OK;
-  const size_t np = (size_t)n_points, fpp = (size_t)frames_per_point, nc = (size_t)pl->n_carrier;
-  Stage st(flags);
+  if (g.n_points == 0) return OFDM_OK;
+  const size_t np = (size_t)g.n_points, fpp = (size_t)g.frames_per_point, nc = (size_t)pl->n_carrier;
+  Stage st(g.flags);
   unsigned long long *derr, *ddrop;
   double* dsum;
   TxfFrameOut<uint32_t> fe;
   TxfFrameOut<double> fn;
-  OFDM_TRY(txf_table(st, errors_out, EST_ROWS * np, derr));
-  OFDM_TRY(txf_table(st, nmse_sums_out, EST_ROWS * np, dsum));
-  OFDM_TRY(txf_table(st, nmse_dropped_out, EST_ROWS * np, ddrop));
-  OFDM_TRY(fe.out(st, frame_errors_out, EST_ROWS * np * fpp));
-  OFDM_TRY(fn.out(st, frame_nmse_out, EST_ROWS * np * fpp));
-  if (frames_per_point == 0) return st.finish();
+  OFDM_TRY(txf_table(st, call.errors_out, EST_ROWS * np, derr));
+  OFDM_TRY(txf_table(st, call.nmse_sums_out, EST_ROWS * np, dsum));
+  OFDM_TRY(txf_table(st, call.nmse_dropped_out, EST_ROWS * np, ddrop));
+  OFDM_TRY(fe.out(st, call.frame_errors_out, EST_ROWS * np * fpp));
+  OFDM_TRY(fn.out(st, call.frame_nmse_out, EST_ROWS * np * fpp));
+  if (hook) OFDM_TRY(hook->tables(st, np, fpp));
+  if (g.frames_per_point == 0) return st.finish();
   const int taps = (int)ch.delay.size();
   const TxfUse u = g.use(ch);
-  const int64_t CH = est_chunk(s, u, pl->taps, frames_per_point, max_frames_per_chunk);
+  const int64_t CH = hook ? hook->chunk(s, u, pl->taps, g.frames_per_point, g.max_frames_per_chunk)
+                          : est_chunk(s, u, pl->taps, g.frames_per_point, g.max_frames_per_chunk);
   const size_t chn = (size_t)CH;
   OFDM_TRY(fn.scratch(st, EST_ROWS * chn));
   void *dtrue, *dcv = nullptr, *drows = nullptr, *dstatic = nullptr;
   OFDM_TRY(st.scratch(sizeof(c64) * nc * (fading ? chn : 1), &dtrue));
   if (genie) OFDM_TRY(st.scratch(sizeof(double) * chn, &dcv));
   if (want_err) OFDM_TRY(st.scratch(sizeof(uint32_t) * EST_ROWS * chn, &drows));
-  unsigned char *front, *body;
-  OFDM_TRY(est_arena(pl, 0, CH, &front, &body));
+  unsigned char *front_bytes, *body;
+  OFDM_TRY(est_arena(pl, 0, CH, &front_bytes, &body));
   const TxfDelays dl = txf_delays(ch);
+  if (hook) OFDM_TRY(hook->begin(st, dl, CH));
   if (!fading) {                                                  // a static channel: its taps, its H(k) and its c, once
     OFDM_TRY(st.scratch(sizeof(c64) * (size_t)std::max(taps, 1), &dstatic));   // an all-zero h has no taps: H = 0
     OFDM_TRY(txf_static_amps(ch, (c64*)dstatic));
@@ -203,14 +206,34 @@ extern "C" int ofdm_estimator_study(ofdm_rx_plan* pl, const void* h, int h_len, 
     if (fading) OFDM_TRY(est_truth(pl, (const c64*)b.amp, taps, dl, nf, (c64*)dtrue, (double*)dcv));
     EstBodyArgs a = ba;
     a.ref = want_err ? b.ref : nullptr;
-    a.inv_snr = 1.0 / std::pow(10.0, snr_db[p] * 0.1);                           // MMSE_CE.m:13, the point's own SNR
+    a.inv_snr = 1.0 / std::pow(10.0, g.snr_db[p] * 0.1);                         // MMSE_CE.m:13, the point's own SNR
     const int64_t hs = fading ? (int64_t)nc : 0;
     uint32_t* const ferr = fe.sweep ? fe.at(EST_ROWS * (size_t)at) : nullptr;
+    double* const fnm = fn.at(EST_ROWS * (size_t)at);
+    EstChunkDone done{nf, p, at, {}, nullptr, nullptr, (const c64*)dtrue, hs, fnm,
+                      fading ? (const c64*)b.amp : (const c64*)dstatic, fading ? (int64_t)taps : 0};
     if (pl->f64)
-      return est_chunk_run<double>(pl, a, b.rx, nf, body, (const c64*)dtrue, hs, fn.at(EST_ROWS * (size_t)at), derr + EST_ROWS * p,
-                                   ferr, dsum + EST_ROWS * p, ddrop + EST_ROWS * p);
-    return est_chunk_run<float>(pl, a, b.rx, nf, body, (const c64*)dtrue, hs, fn.at(EST_ROWS * (size_t)at), derr + EST_ROWS * p, ferr,
-                                dsum + EST_ROWS * p, ddrop + EST_ROWS * p);
+      OFDM_TRY(est_chunk_run<double>(pl, a, b.rx, nf, body, (const c64*)dtrue, hs, fnm, derr + EST_ROWS * p, ferr, dsum + EST_ROWS * p,
+                                     ddrop + EST_ROWS * p, done));
+    else
+      OFDM_TRY(est_chunk_run<float>(pl, a, b.rx, nf, body, (const c64*)dtrue, hs, fnm, derr + EST_ROWS * p, ferr, dsum + EST_ROWS * p,
+                                    ddrop + EST_ROWS * p, done));
+    return hook ? hook->frames(done) : OFDM_OK;
   }));
   return st.finish();
+}
+
+}  // namespace ofdm
+
+using namespace ofdm;
+
+extern "C" int ofdm_estimator_study(ofdm_rx_plan* pl, const void* h, int h_len, const int32_t* tap_delay, const double* tap_power,
+                                    int n_taps, const double* snr_db, const uint64_t* seeds, int64_t n_points,
+                                    int64_t frames_per_point, int64_t frame0, int mmse_mode, int64_t max_frames_per_chunk,
+                                    uint64_t* errors_out, double* nmse_sums_out, uint64_t* nmse_dropped_out,
+                                    uint32_t* frame_errors_out, double* frame_nmse_out, int flags) {
+  const TxfStudyArgs g{h, h_len, tap_delay, tap_power, n_taps, 0, 0, 0, 0.0, nullptr, snr_db, seeds, n_points, frames_per_point, frame0,
+                       max_frames_per_chunk, flags};
+  return est_study_run(EstStudyCall{pl, g, mmse_mode, errors_out, nmse_sums_out, nmse_dropped_out, frame_errors_out, frame_nmse_out},
+                       nullptr);
 }

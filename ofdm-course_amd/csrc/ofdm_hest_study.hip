@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "hest_plan.hpp"
+#include "hest_point.hpp"
 #include "txf_study.hpp"
 
 namespace ofdm {
@@ -40,14 +41,6 @@ struct HestRows {
   uint8_t* pmask;
 };
 
-// sqrt(re^2 + im^2) as two rounded products, a rounded sum and a root, never a fused operation: what a host that rebuilds the value
-// from H_est computes (the build contracts in the backend, where a pragma does not reach: the products pass through an empty asm)
-__device__ __forceinline__ double hest_abs(double re, double im) {
-  double p = re * re, q = im * im;
-  asm volatile("" : "+v"(p), "+v"(q));
-  return sqrt(p + q);
-}
-
 __global__ __launch_bounds__(256) void hest_static_table_kernel(const c64* __restrict__ amp, TxfDelays dl, int nfft, int n_carrier,
                                                                 c64* __restrict__ htab) {
   const int k = blockIdx.x * 256 + threadIdx.x;
@@ -55,25 +48,6 @@ __global__ __launch_bounds__(256) void hest_static_table_kernel(const c64* __res
   double hr, hi;
   channel_resp(amp, dl, k, nfft, 2.0 / (double)nfft, hr, hi);
   htab[k] = mk<double>(hr, hi);
-}
-
-// one carrier (or pilot) of one frame: the true H against the estimate e
-struct HestPoint {
-  double est_amp, true_amp, err, amp_err;
-  uint8_t bad;
-};
-
-template <typename T>
-__device__ __forceinline__ HestPoint hest_point(double hr, double hi, cx<T> e) {
-  const double er = (double)e.x, ei = (double)e.y;
-  HestPoint p;
-  p.bad = (er - er == 0.0 && ei - ei == 0.0) ? 0 : 1;
-  p.est_amp = hest_abs(er, ei);
-  p.true_amp = hest_abs(hr, hi);
-  const double dr = hr - er, di = hi - ei, d = p.est_amp - p.true_amp;
-  p.err = dr * dr + di * di;
-  p.amp_err = d * d;
-  return p;
 }
 
 template <typename T>
@@ -207,6 +181,16 @@ struct HestThrPart {
 
 __global__ __launch_bounds__(HEST_THR_PART) void hest_thresholds_kernel(double* __restrict__ thr, HestThrPart part, int n) {
   if ((int)threadIdx.x < n) thr[threadIdx.x] = part.v[threadIdx.x];
+}
+
+int study_thresholds_device(const double* thr, size_t n, double* dthr) {
+  for (size_t i0 = 0; i0 < n; i0 += HEST_THR_PART) {
+    const int m = (int)std::min<size_t>(HEST_THR_PART, n - i0);
+    HestThrPart part{};
+    std::copy(thr + i0, thr + i0 + m, part.v);
+    hipLaunchKernelGGL(hest_thresholds_kernel, dim3(1), dim3(HEST_THR_PART), 0, ctx().stream, dthr + i0, part, m);
+  }
+  return check_launch("hest_thresholds_kernel");
 }
 
 // every frame of the sweep: its error sum on the table of thresholds, its status
@@ -359,13 +343,7 @@ extern "C" int ofdm_hest_study(ofdm_rx_plan* pl, const void* h, int h_len, const
   OFDM_TRY(st.scratch(sizeof(int32_t) * chn, &cifo));
   OFDM_TRY(st.scratch(sizeof(int32_t) * NF, &dstat));                    // every frame's status, counted after the last chunk
   OFDM_TRY(st.scratch(sizeof(double) * (nb + 1), &dthr));
-  for (size_t i0 = 0; i0 <= nb; i0 += HEST_THR_PART) {
-    const int n = (int)std::min<size_t>(HEST_THR_PART, nb + 1 - i0);
-    HestThrPart part{};
-    std::copy(thr.begin() + i0, thr.begin() + i0 + n, part.v);
-    hipLaunchKernelGGL(hest_thresholds_kernel, dim3(1), dim3(HEST_THR_PART), 0, stream, (double*)dthr + i0, part, n);
-  }
-  OFDM_TRY(check_launch("hest_thresholds_kernel"));
+  OFDM_TRY(study_thresholds_device(thr.data(), nb + 1, (double*)dthr));
   const TxfDelays dl = txf_delays(ch);
   if (!fading) {                                                          // a static channel: its taps and its H(k), once
     OFDM_TRY(st.scratch(sizeof(c64) * (size_t)std::max(taps, 1), &dstatic));   // an all-zero h has no taps: H = 0

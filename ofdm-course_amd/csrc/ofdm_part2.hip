@@ -437,6 +437,8 @@ int est_body_run(ofdm_rx_plan* pl, const EstBodyArgs& a, const void* drx, int64_
   const void* tw = nullptr;
   OFDM_TRY(get_twiddles(N, f64, &tw));
   OFDM_TRY(fast_params_prepare<T>(pv, tw, F, P));
+  out.tap_idx = P.tap_idx;
+  out.tap_x = P.tap_x;
   // demodulator, pilot LS values Y
   OFDM_TRY(demod_keep_device(drx, dxk, N, F * S, Tg, nc, f64));
   hipLaunchKernelGGL(p2_pilot_ls_kernel<T>, dim3(cdiv_u(F * np, 256)), dim3(256), 0, st, (const cx<T>*)dxk, (const int32_t*)pl->d_pc0,

@@ -38,12 +38,14 @@ enum { ACC_PEAK_OFF, ACC_PEAK_ROWS, ACC_PEAK_SECOND };
 // counted in dropped[k] and not added; otherwise it is added like any other.  PEAK: peak[k] = fmax(peak[k], the rows' or
 // peak_rows' entries), only where `peak` is given.  COUNT: counts[k] += the bytes flags[f][k].  The pointers a switch leaves unused
 // may be null.  Column k >= cols of the last workgroup idles (it still meets every barrier).
-template <bool DROP, int PEAK, bool COUNT>
-__device__ __forceinline__ void study_accumulate_columns(StudyAccTile& tile, const double* __restrict__ rows,
-                                                         const double* __restrict__ peak_rows, const uint8_t* __restrict__ flags,
-                                                         int64_t nf, int64_t cols, double* __restrict__ sums,
-                                                         unsigned long long* __restrict__ dropped, double* __restrict__ peak,
-                                                         unsigned long long* __restrict__ counts) {
+// The rows come from `load(f, k)`, the value of frame f of the chunk in column k: a chunk's rows in memory (below), or what a study
+// forms of its buffers on the way (the estimator profile, ofdm_est_profile.hip).  With DROP, `dropped` may be null: the values left
+// out are then not counted.
+template <bool DROP, int PEAK, bool COUNT, typename Load>
+__device__ __forceinline__ void study_accumulate_columns_from(StudyAccTile& tile, Load load, const double* __restrict__ peak_rows,
+                                                              const uint8_t* __restrict__ flags, int64_t nf, int64_t cols,
+                                                              double* __restrict__ sums, unsigned long long* __restrict__ dropped,
+                                                              double* __restrict__ peak, unsigned long long* __restrict__ counts) {
   static_assert(PEAK == ACC_PEAK_OFF || !COUNT, "one order-free partial goes through the tile");
   constexpr int RW = STUDY_ACC_THREADS / STUDY_ACC_COLS;                     // row groups: 4
   constexpr int PER = STUDY_ACC_TILE / RW;                                   // rows per thread and tile
@@ -58,7 +60,7 @@ __device__ __forceinline__ void study_accumulate_columns(StudyAccTile& tile, con
     for (int i = 0; i < PER; ++i) {
       const int64_t f = t0 + r * PER + i;
       const bool in = live && f < nf;
-      v[i] = in ? rows[f * cols + k] : 0.0;
+      v[i] = in ? load(f, k) : 0.0;
       if (PEAK == ACC_PEAK_ROWS) m = fmax(m, v[i]);
       if (PEAK == ACC_PEAK_SECOND && peak && in) m = fmax(m, peak_rows[f * cols + k]);
       if (COUNT) nc += in ? (unsigned long long)flags[f * cols + k] : 0ull;
@@ -77,7 +79,7 @@ __device__ __forceinline__ void study_accumulate_columns(StudyAccTile& tile, con
   }
   if (r == 0 && live) {
     sums[k] = s;
-    if (DROP) dropped[k] += nd;
+    if (DROP && dropped) dropped[k] += nd;
   }
   if (PEAK != ACC_PEAK_OFF && peak) {                 // the tile is free again: [RW][STUDY_ACC_COLS] partials
     tile[r][c] = m;
@@ -98,6 +100,17 @@ __device__ __forceinline__ void study_accumulate_columns(StudyAccTile& tile, con
       counts[k] = t;
     }
   }
+}
+
+// rows [nf][cols] of doubles in memory
+template <bool DROP, int PEAK, bool COUNT>
+__device__ __forceinline__ void study_accumulate_columns(StudyAccTile& tile, const double* __restrict__ rows,
+                                                         const double* __restrict__ peak_rows, const uint8_t* __restrict__ flags,
+                                                         int64_t nf, int64_t cols, double* __restrict__ sums,
+                                                         unsigned long long* __restrict__ dropped, double* __restrict__ peak,
+                                                         unsigned long long* __restrict__ counts) {
+  study_accumulate_columns_from<DROP, PEAK, COUNT>(
+      tile, [rows, cols](int64_t f, int64_t k) { return rows[f * cols + k]; }, peak_rows, flags, nf, cols, sums, dropped, peak, counts);
 }
 
 // one per-frame scalar into {sum f(v), sum v^2}: f is fabs (an error) or the identity (a signed value)

@@ -118,4 +118,8 @@ struct TxfFrameOut {
   T* at(size_t i) const { return sweep ? sweep + i : chunk; }
 };
 
+// a host table of n histogram thresholds into device memory on the launch stream, as kernel arguments: no copy the host waits for
+// (ofdm_hest_study.hip)
+int study_thresholds_device(const double* thr, size_t n, double* dthr);
+
 }  // namespace ofdm

@@ -14,6 +14,12 @@ The channel is the tap-delay-line stand-in of drivers/common.py (fading_profile:
 per tap and frame, no Doppler), not lteFadingChannel, whose fractional-delay filter is closed source.  The counts this driver
 reports below the 5 % threshold are therefore the driver's own: they need not be the report's 16 / 16 / 8 / 8.
 
+With `--curves` the first replay goes through `RxPlan.estimator_profile` (ofdm_estimator_profile), the same call with the pictures
+of `Task 5/Main_model_Task_5.m:207-231, :238-242`: for the SNR points `--curve-snrs` (default 0,10,20,30; points of the 0:0.5:30
+grid) the JSON adds, under curves.pictures, |H| and the four |H_est| over the carriers as means over the frames, the error per
+carrier, the histogram of the frames' error, and OMP's picks and the channel's taps per delay with the support counts.  Without
+`--curves` the output is what it was.
+
 Under `python -m torch.distributed.run` every process takes one GPU and the tiles of `--frames-per-tile` frames dealt to its rank
 through `frame0`, as drivers/task4_hest.py deals them; one SUM all-reduce of the int64 tables and one of the float64 sums end each
 call.
@@ -40,6 +46,8 @@ NFFT, N_CARRIER, N_SYMB, SAMPLING_RATE = 1024, 640, 7, 4e7                      
 DEFAULT_COUNTS = (8, 16, 32, 64, 128)
 MAX_PILOTS = 585                                                                   # the MMSE stage of the estimator body
 MMSE_MODES = ("ls", "genie")
+PICTURE_SNRS = (0.0, 10.0, 20.0, 30.0)                                             # --curve-snrs
+PICTURE_BINS = dict(n=60, lo=-50.0, hi=10.0)
 
 
 def check_layout(pilots, counts, comb, n_carrier=N_CARRIER, n_paths=1):
@@ -99,6 +107,69 @@ def study_call(plan, my_tiles, n_points, reduce, **kw):
     return dict(errors=counts[:, :4], nmse_dropped=counts[:, 4:], nmse_sums=sums)
 
 
+def check_curve_snrs(snrs):
+    """The points of --curve-snrs are points of the curves' grid; the text of the refusal, or None."""
+    if not snrs:
+        return "--curve-snrs needs at least one SNR"
+    for v in snrs:
+        if v not in CURVE_SNRS:
+            return f"--curve-snrs: {v:g} is not a point of the grid {CURVE_SNRS[0]:g}:{CURVE_SNRS[1] - CURVE_SNRS[0]:g}:{CURVE_SNRS[-1]:g}"
+    return None
+
+
+# the tables of estimator_profile the driver adds up: (key, trailing shape per point as a function of nc, K, T, bins)
+_PROFILE_COUNTS = (("errors", lambda nc, K, T, nb: (4,)), ("nmse_dropped", lambda nc, K, T, nb: (4,)),
+                   ("nmse_hist", lambda nc, K, T, nb: (4, nb)), ("nmse_below", lambda nc, K, T, nb: (4,)),
+                   ("nmse_above", lambda nc, K, T, nb: (4,)), ("nmse_nan", lambda nc, K, T, nb: (4,)),
+                   ("pick_hist", lambda nc, K, T, nb: (K,)), ("n_picks_hist", lambda nc, K, T, nb: (T + 1,)),
+                   ("true_outside", lambda nc, K, T, nb: ()), ("support_hits", lambda nc, K, T, nb: ()),
+                   ("support_misses", lambda nc, K, T, nb: ()), ("support_false", lambda nc, K, T, nb: ()))
+_PROFILE_SUMS = (("nmse_sums", lambda nc, K, T, nb: (4,)), ("true_amp_sums", lambda nc, K, T, nb: (nc,)),
+                 ("est_amp_sums", lambda nc, K, T, nb: (4, nc)), ("err_sums", lambda nc, K, T, nb: (4, nc)),
+                 ("tap_amp_sums", lambda nc, K, T, nb: (K,)), ("true_tap_amp_sums", lambda nc, K, T, nb: (K,)))
+
+
+def profile_call(plan, my_tiles, n_points, reduce, nc, K, T, bins=PICTURE_BINS, **kw):
+    """estimator_profile over this rank's tiles, its tables added up and reduced over the ranks: the new int64 tables join the one
+    int64 table of study_call, the new float64 sums its one float64 table.  -> dict of numpy arrays over all frames of all ranks:
+    what study_call returns and the tables of _PROFILE_COUNTS / _PROFILE_SUMS, each [n_points, ...]."""
+    nb = bins["n"]
+    cshape = [(k, f(nc, K, T, nb)) for k, f in _PROFILE_COUNTS]
+    sshape = [(k, f(nc, K, T, nb)) for k, f in _PROFILE_SUMS]
+    width = lambda shapes: sum(int(np.prod(sh)) for _, sh in shapes)                  # noqa: E731
+    flat = lambda out, shapes: np.concatenate([_np(out[k]).reshape(n_points, -1) for k, _ in shapes], axis=1)   # noqa: E731
+    counts = np.zeros((n_points, width(cshape)), dtype=np.int64)
+    sums = np.zeros((n_points, width(sshape)), dtype=np.float64)
+    for frame0, nf in my_tiles:
+        out = plan.estimator_profile(frames_per_point=nf, frame0=frame0, bins=bins, **kw)
+        counts += flat(out, cshape).astype(np.int64)
+        sums += flat(out, sshape)
+    counts, sums = reduce(counts, sums)
+    res = {}
+    for table, shapes in ((counts, cshape), (sums, sshape)):
+        at = 0
+        for k, sh in shapes:
+            n = int(np.prod(sh))
+            res[k] = table[:, at:at + n].reshape((n_points,) + sh)
+            at += n
+    return res
+
+
+def pictures(out, frames, snrs, bins=PICTURE_BINS):
+    """The pictures of the points `snrs` of the curves' grid from profile_call's tables: means over the frames, a dropped frame out
+    of its estimator's denominator."""
+    at = [CURVE_SNRS.index(v) for v in snrs]
+    kept = (frames - out["nmse_dropped"][at]).astype(np.float64)[..., None]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        res = dict(SNR_dB=list(snrs), mean_true_amp=out["true_amp_sums"][at] / float(frames), mean_est_amp=out["est_amp_sums"][at] / kept,
+                   nmse_profile=out["err_sums"][at] / kept, edges_dB=np.linspace(bins["lo"], bins["hi"], bins["n"] + 1),
+                   mean_tap_amp=out["tap_amp_sums"][at] / float(frames), mean_true_tap_amp=out["true_tap_amp_sums"][at] / float(frames))
+    for k in ("nmse_hist", "nmse_below", "nmse_above", "nmse_nan", "pick_hist", "n_picks_hist", "true_outside", "support_hits",
+              "support_misses", "support_false"):
+        res[k] = out[k][at]
+    return res
+
+
 def figures(out, frames, frame_bits, n_carrier):
     """BER and NMSE [n, 4] of a call: NMSE as RxPlan.estimator_study forms it, the dropped frames out of the denominator."""
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -115,13 +186,15 @@ def make_plan(lib, pc, dc, K, n_paths, Constellation, n_symb, precision, nfft=NF
 
 def run(profile="EPA", frames=100, mmse="ls", pilots="regular", counts=DEFAULT_COUNTS, comb=4, seed=1, precision="fp64",
         Constellation="16QAM", device_index=0, max_frames_per_chunk=0, lib=None, frames_per_tile=4096, rank=0, world=1,
-        reduce=reduce_over_ranks):
+        reduce=reduce_over_ranks, curves=False, curve_snrs=PICTURE_SNRS):
     """Returns (on every rank) {"curves": {SNR_dB, comb, n_pilots, BER, NMSE, nmse_dropped} with BER / NMSE [61, 4] in the order of
     `rows`, "pilots": {SNR_dB, layout, counts, n_pilots, BER, NMSE [len(counts), 4], nmse_dropped, smallest_count_below_5_percent},
     ...}: one estimator_study call per tile of this rank and scenario, reduced over the ranks by `reduce`.  lib: the library module
-    (default: ofdm_course_amd)."""
+    (default: ofdm_course_amd).  curves: the first replay through estimator_profile, and "curves" gains "pictures" (the dict of
+    `pictures`) for the points curve_snrs."""
     delays, powers = c.fading_profile(profile, SAMPLING_RATE)
-    bad = check_args(frames, frames_per_tile) or check_layout(pilots, list(counts), comb, N_CARRIER, len(delays))
+    bad = check_args(frames, frames_per_tile) or check_layout(pilots, list(counts), comb, N_CARRIER, len(delays)) or \
+        (check_curve_snrs(list(curve_snrs)) if curves else None)
     if bad:
         raise ValueError(bad)
     if mmse not in MMSE_MODES:
@@ -137,10 +210,17 @@ def run(profile="EPA", frames=100, mmse="ls", pilots="regular", counts=DEFAULT_C
            "n_gpus": world, "frames_per_tile": frames_per_tile, "tiles_this_rank": len(mine)}
     # the curves over SNR at one layout
     _, pc, dc = c.layout_comb(NFFT, N_CARRIER, comb)
-    plan = make_plan(lib, pc, dc, max(min(NFFT // comb, 256), len(pc)), len(delays), Constellation, N_SYMB, precision)
-    fig = figures(study_call(plan, mine, len(CURVE_SNRS), reduce, SNRs=list(CURVE_SNRS), **common), frames, plan.frame_bits, N_CARRIER)
+    K = max(min(NFFT // comb, 256), len(pc))
+    plan = make_plan(lib, pc, dc, K, len(delays), Constellation, N_SYMB, precision)
+    if curves:
+        out = profile_call(plan, mine, len(CURVE_SNRS), reduce, N_CARRIER, K, len(delays), SNRs=list(CURVE_SNRS), **common)
+    else:
+        out = study_call(plan, mine, len(CURVE_SNRS), reduce, SNRs=list(CURVE_SNRS), **common)
+    fig = figures(out, frames, plan.frame_bits, N_CARRIER)
     plan.close()
     res["curves"] = dict(SNR_dB=list(CURVE_SNRS), comb=comb, n_pilots=len(pc), **fig)
+    if curves:
+        res["curves"]["pictures"] = dict(K=K, dominant_taps=len(delays), **pictures(out, frames, list(curve_snrs)))
     # the pilot-count table at 20 dB
     ber, nmse, drop, n_pilots = [], [], [], []
     for n in counts:
@@ -163,6 +243,10 @@ def parser():
     ap.add_argument("--pilots", choices=["regular", "random"], default="regular", help="the layouts of the pilot-count table")
     ap.add_argument("--counts", type=int, nargs="+", default=list(DEFAULT_COUNTS), help="pilot counts of the table, ascending")
     ap.add_argument("--comb", type=int, default=4, help="the comb of the curves over SNR")
+    ap.add_argument("--curves", action="store_true", help="the curves over SNR through estimator_profile, with the per-carrier and "
+                    "per-delay pictures of --curve-snrs in the JSON")
+    ap.add_argument("--curve-snrs", type=lambda t: [float(v) for v in t.split(",") if v], default=list(PICTURE_SNRS), metavar="A,B,..",
+                    help="the SNR points of the pictures, points of the grid 0:0.5:30 (default 0,10,20,30)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--precision", choices=["fp32", "fp64"], default="fp64")
     ap.add_argument("--frames-per-tile", type=int, default=4096, help="frames of one estimator_study call: the unit dealt to the ranks")
@@ -177,7 +261,8 @@ def parse_args(argv=None):
     ap = parser()
     a = ap.parse_args(argv)
     bad = check_args(a.frames, a.frames_per_tile) or check_layout(a.pilots, a.counts, a.comb, N_CARRIER,
-                                                                  len(c.fading_profile(a.profile, SAMPLING_RATE)[0]))
+                                                                  len(c.fading_profile(a.profile, SAMPLING_RATE)[0])) or \
+        (check_curve_snrs(a.curve_snrs) if a.curves else None)
     if bad:
         ap.error(bad)
     return a
@@ -201,7 +286,7 @@ def main(argv=None, lib=None):
         else:
             dist.init_process_group(a.backend)
     res = run(a.profile, a.frames, a.mmse, a.pilots, tuple(a.counts), a.comb, a.seed, a.precision, device_index=dev_index, lib=lib,
-              frames_per_tile=a.frames_per_tile, rank=rank, world=world, reduce=reduce)
+              frames_per_tile=a.frames_per_tile, rank=rank, world=world, reduce=reduce, curves=a.curves, curve_snrs=tuple(a.curve_snrs))
     if rank == 0:
         text = json.dumps(c.to_jsonable(res))
         if a.json:
