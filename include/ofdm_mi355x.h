@@ -1241,6 +1241,70 @@ int ofdm_estimator_profile(ofdm_rx_plan* plan, const void* h, int h_len, /* HOST
                            void* tap_x_out,                          /* optional [n_points][frames_per_point][T] complex double */
                            int flags);
 
+/* The fused generator with a given payload: ofdm_tx_frames_fused_ex (h, h_len) or ofdm_tx_frames_fading_ex (tap_delay, tap_power,
+ * n_taps in place of h) with the payload draw replaced by the caller's bits -- what file_reader.m hands the chain of every driver
+ * of the reference (T3/Main_model_Task_3.m:26-32).  payload: a packed bit stream where `flags` says, stream bit i in bit
+ * 7 - i % 8 of byte i / 8 (the library's packing), ceil(n_bits / 8) bytes.  Frame f of the call carries the stream bits
+ * (first_frame + f) frame_bits .. + frame_bits - 1 with frame_bits = nd N_symb bps, in general no multiple of 8; bits at or beyond
+ * n_bits are 0 (the padding display_pic.m:5-6 assumes), a frame wholly beyond the payload is all zeros.  The noise, STO / CFO and
+ * fading draws of frame f are those of Philox stream frame0 + f, as in the other generator entries: only the bit source changes.
+ * For bits equal to the Philox payload of (seed, frame0 + f) every output equals the existing entry's, bit for bit.  With both
+ * modes 0 and no sto_out / cfo_out the channel pass is that of ofdm_tx_frames_fused / _fading.  Outputs as there (taps_out only
+ * with a tap-delay line).  OFDM_ERR_ARG, before anything is launched or written, in this order: payload given and n_bits >= 1;
+ * first_frame 0 .. 2^32 - 1; h and taps together; what the generator entries refuse, in their order and words under the name
+ * tx_frames_payload; a frame of more than 2^31 - 1 bits. */
+int ofdm_tx_frames_payload(ofdm_rx_plan* plan, const uint8_t* payload, /* [ceil(n_bits / 8)], where flags says */
+                           int64_t n_bits, int64_t first_frame,
+                           const void* h, int h_len,                 /* HOST, complex in the plan's precision, or NULL / 0 */
+                           const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                           double snr_db, uint64_t seed, int64_t frame0, int64_t n_frames,
+                           const uint8_t* scr_reg15,                 /* HOST uint8[15] or NULL */
+                           int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                           void* rx_out,                             /* [n_frames][frame_samples] */
+                           uint8_t* ref_bits_out,                    /* optional [n_frames][frame_bytes] */
+                           uint8_t* sc_ref_bits_out,                 /* optional [n_frames][frame_bytes], needs scr_reg15 */
+                           double* taps_out,                         /* optional [n_frames][n_taps] complex double */
+                           int64_t* sto_out, double* cfo_out,        /* optional [n_frames] */
+                           int flags);
+
+/* Payload transport as one device-resident call: the caller's bits through the generator and a receiver and back as one stream,
+ * at every point of a sweep (T3/Main_model_Task_3.m:26-32, :160-185: file_reader.m -> the chain -> DeScrambler -> BER_func ->
+ * display_pic.m).  Let F = ceil(n_bits / frame_bits).  For every point p and repeat r the frames i = 0 .. F - 1 of
+ * ofdm_tx_frames_payload(payload, n_bits, first_frame = 0) with snr_db[p], seeds[p] on Philox stream frame0 + r F + i, decoded as
+ * the matching sweep decodes them -- receiver 5: ofdm_rx_chain_task5 as in ofdm_ber_sweep_task5 / _fading (the plan's route, its
+ * MMSE, h = ifft(H_LS) and OMP-route modes, the DeScrambler rule; sto_mode, cfo_mode, time_desync and freq_desync must be 0 and
+ * mp_desync 1); receiver 4: ofdm_rx_chain_task4(time_desync, freq_desync, mp_desync) as in ofdm_ber_sweep_task4 / _fading.  No
+ * sample and no bit leaves the device between the payload and the tables.
+ *   decoded_out [n_points][repeats][ceil(n_bits / 8)]: the received stream, the frames' decisions joined at bit offset
+ *     i frame_bits and cut at n_bits, packed as the payload; the spare bits of the last byte are 0.
+ *   errors_out [n_points][repeats]: the wrong bits among the payload's n_bits, BER_func(input_bits, dsc_bits); the zero padding of
+ *     the last frame is transmitted but not counted.  frame_errors_out [n_points][repeats][F]: per frame, over its share of n_bits.
+ *   ones_out [n_points][n_bits]: the sum over the repeats of decoded bit i (the mean received picture is ones / repeats).
+ * The outputs are overwritten.  Chunks of whole frames of one point's F repeats frames, which may cut a repeat, budgeted as the
+ * matching sweep budgets them with the chunk's decisions beside them (max_frames_per_chunk > 0 caps the frames of a chunk); every
+ * output is bitwise independent of the chunking.  With OFDM_DEVICE nothing synchronises the host, apart from a first-call growth
+ * of the workspace.  OFDM_ERR_ARG, before anything is launched or written, in this order: receiver 4 / 5; plan and payload given;
+ * the plan has data carriers; n_bits >= 1; repeats >= 1; F repeats and frame0 + F repeats inside the 32-bit stream range; h and
+ * taps together; receiver 5 with an impairment or a flag ofdm_ber_sweep_task5 does not have; every refusal of the matching sweep
+ * in its order and words under the name transport (the Task-4 sweep names itself ber_sweep_task4 behind its channel check); a
+ * frame of more than 2^31 - 1 bits; an output is wanted. */
+int ofdm_payload_transport(ofdm_rx_plan* plan, int receiver,      /* 4 | 5 */
+                           const uint8_t* payload,                   /* [ceil(n_bits / 8)], where flags says */
+                           int64_t n_bits, int64_t repeats,
+                           const void* h, int h_len,                 /* HOST, complex in the plan's precision, or NULL / 0 */
+                           const int32_t* tap_delay, const double* tap_power, int n_taps, /* HOST, or NULL / NULL / 0 */
+                           int sto_mode, int64_t sto_value, int cfo_mode, double cfo_value,
+                           int time_desync, int freq_desync, int mp_desync,
+                           const double* snr_db, const uint64_t* seeds, /* HOST [n_points] */
+                           int64_t n_points, int64_t frame0,
+                           const uint8_t* scr_reg15,                 /* HOST uint8[15] or NULL */
+                           int64_t max_frames_per_chunk,
+                           uint8_t* decoded_out,                     /* optional [n_points][repeats][ceil(n_bits / 8)] */
+                           uint64_t* errors_out,                     /* optional [n_points][repeats] */
+                           uint32_t* frame_errors_out,               /* optional [n_points][repeats][F] */
+                           uint32_t* ones_out,                       /* optional [n_points][n_bits] */
+                           int flags);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,10 @@ SIGNATURES = {
                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_estimator_study": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _i64, _vp, _vp, _vp, _vp, _vp, _i],
     "ofdm_estimator_profile": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _i64, _i, _d, _d] + [_vp] * 22 + [_i],
+    "ofdm_tx_frames_payload": [_vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _i, _d, C.c_uint64, _i64, _i64, _vp, _i, _i64, _i, _d, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _i],
+    "ofdm_payload_transport": [_vp, _i, _vp, _i64, _i64, _vp, _i, _vp, _vp, _i, _i, _i64, _i, _d, _i, _i, _i, _vp, _vp, _i64, _i64, _vp,
+                               _i64, _vp, _vp, _vp, _vp, _i],
 }
 _RESTYPES = {"ofdm_last_error_string": C.c_char_p, "ofdm_rx_plan_frame_bytes": C.c_int64}
 

@@ -881,8 +881,53 @@ class RxPlan:
         div = None if count is None else torch.full((1,), float(count), dtype=torch.float64, device=torch.device(device))
         return list(tables), div, lambda a: a.double()
 
+    @staticmethod
+    def _payload(device, payload_bits, payload_packed, what):
+        """The caller's payload as the C entries take it: payload_bits (a 0 / 1 array or tensor of any length and shape, read
+        in C order) packed MSB first, or payload_packed=(bytes, n_bits) as it is -> (the packed buffer: a torch uint8 tensor on
+        `device` when it is given, a numpy array otherwise; its pointer; n_bits).  Packing is byte plumbing: numpy's packbits on
+        the host, the same weights in torch for a CUDA tensor, which never leaves the device."""
+        if (payload_bits is None) == (payload_packed is None):
+            raise OfdmError(f"{what}: give payload_bits or payload_packed=(bytes, n_bits), not both")
+        if payload_packed is not None:
+            try:
+                raw, n_bits = payload_packed
+                n_bits = int(n_bits)
+            except (TypeError, ValueError):
+                raise OfdmError(f"{what}: payload_packed must be (bytes, n_bits)") from None
+            if _is_torch(raw):
+                buf = raw.contiguous().view(-1)
+                if buf.dtype != torch.uint8:
+                    raise OfdmError(f"{what}: payload_packed bytes must be uint8")
+            elif isinstance(raw, (bytes, bytearray, memoryview)):
+                buf = np.frombuffer(raw, dtype=np.uint8)
+            else:
+                buf = np.ascontiguousarray(np.asarray(raw, dtype=np.uint8).ravel())
+            if 8 * int(buf.numel() if _is_torch(buf) else buf.size) < n_bits:
+                raise OfdmError(f"{what}: payload_packed holds fewer than n_bits = {n_bits} bits")
+        elif _is_torch(payload_bits) and payload_bits.is_cuda:
+            b = (payload_bits.reshape(-1) != 0).to(torch.uint8)
+            n_bits = int(b.numel())
+            b = torch.nn.functional.pad(b, (0, (-n_bits) % 8)).view(-1, 8)
+            w = torch.tensor([128, 64, 32, 16, 8, 4, 2, 1], dtype=torch.uint8, device=b.device)
+            buf = (b * w).sum(dim=1).to(torch.uint8)
+        else:
+            b = np.asarray(payload_bits.numpy() if _is_torch(payload_bits) else payload_bits).ravel() != 0
+            n_bits = int(b.size)
+            buf = np.packbits(b)
+        if (buf.numel() if _is_torch(buf) else buf.size) == 0:       # (no bits: a byte to point at, the count is the library's refusal)
+            buf = np.zeros(1, np.uint8)
+        if device is not None:
+            buf = (buf if _is_torch(buf) else torch.from_numpy(np.array(buf))).to(torch.device(device)).contiguous()
+            return buf, C.c_void_p(buf.data_ptr()), n_bits
+        if _is_torch(buf):
+            buf = buf.cpu().numpy()
+        buf = np.ascontiguousarray(buf)
+        return buf, buf.ctypes.data_as(C.c_void_p), n_bits
+
     def tx_frames_fused(self, n_frames, h=None, SNR=20.0, seed=1, frame0=0, device=None, Register=None, Time_Delay=None,
-                        Freq_Shift=None, want_draws=False, fading=None, want_taps=False):
+                        Freq_Shift=None, want_draws=False, fading=None, want_taps=False, payload_bits=None, payload_frame0=0,
+                        payload_packed=None):
         """Reference-order frames in three sample passes (ofdm_tx_frames_fused): payload -> [Scrambler(Register, .) per
         frame] -> mapping -> OFDM_map_carriers -> OFDM_modulator -> Noise(SNR) -> conv(h) truncated
         (T5/Main_model_Task_5.m:50-127, T5/Task5_part2.m:134,:152).  The draws of tx_frames(noise_first=True): the same
@@ -901,8 +946,14 @@ class RxPlan:
         (ofdm_tx_frames_fading_ex): Noise -> add_STO -> add_CFO -> conv with the frame's own taps, the two per-frame draws
         independent of each other.
         The C entry: ofdm_tx_frames_fused, with fading ofdm_tx_frames_fading; given Time_Delay, Freq_Shift or want_draws their
-        _ex forms.  The plain entries launch no STO / CFO draw kernel and the channel pass without impairments."""
+        _ex forms.  The plain entries launch no STO / CFO draw kernel and the channel pass without impairments.
+        payload_bits (a 0 / 1 array or torch tensor of any length) or payload_packed=(bytes, n_bits) (packed MSB first, as
+        `packed` is) replace the payload draw (ofdm_tx_frames_payload): frame f carries the stream bits (payload_frame0 + f)
+        frame_bits .. + frame_bits - 1, zeros at and beyond the stream's end (display_pic.m:5-6); the noise, STO / CFO and
+        fading draws stay those of (seed, frame0 + f), and for the Philox bits of (seed, frame0 + f) every output is the one
+        without a payload, bit for bit.  With neither, the function is what it was."""
         n_frames = int(n_frames)
+        given = payload_bits is not None or payload_packed is not None
         fade = fading is not None
         if fade:
             keep_f, pdl, ppw, nt = self._fading_args(h, fading, "tx_frames_fused")
@@ -920,7 +971,15 @@ class RxPlan:
         if not fade:
             chan, name = (ph, nh), "tx_frames_fused"
         p_bits, p_taps, p_draws = ptrs[:3], ptrs[3:4] if fade else [], ptrs[4:]
-        if ex:
+        if given:
+            pbuf, pp, n_bits = self._payload(device, payload_bits, payload_packed, "tx_frames_fused")
+            sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
+            cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
+            ch5 = (None, 0, *chan) if fade else (*chan, None, None, 0)
+            L.check(self.lib.ofdm_tx_frames_payload(self.handle, pp, n_bits, int(payload_frame0), *ch5, float(SNR), int(seed),
+                                                    int(frame0), n_frames, pr, sm, int(sv), cm, float(cv), *ptrs, flags),
+                    "tx_frames_payload")
+        elif ex:
             sm, sv = _imp_mode(Time_Delay, "tx_frames_fused")
             cm, cv = _imp_mode(Freq_Shift, "tx_frames_fused")
             L.check(getattr(self.lib, f"ofdm_{name}_ex")(self.handle, *chan, float(SNR), int(seed), int(frame0), n_frames, pr,
@@ -1272,6 +1331,62 @@ class RxPlan:
         L.check(self.lib.ofdm_error_study(self.handle, rcv, *chan, *imp, int(time_desync), int(freq_desync), int(mp_desync), *pts, fpp,
                                           int(frame0), pr, sd_, gb, int(max_frames_per_chunk), *ptrs, flags), "error_study")
         return _error_result(self, device is not None, max(fpp, 0), arrs)
+
+    def transport(self, payload_bits=None, SNRs=(20.0,), repeats=1, receiver="task5", h=None, fading=None, Time_Delay=None,
+                  Freq_Shift=None, time_desync=0, freq_desync=0, mp_desync=1, seeds=None, seed=1, frame0=0, Register=None,
+                  device=None, want_decoded=True, want_ones=False, want_frames=False, max_frames_per_chunk=0, payload_packed=None):
+        """The caller's bits through the generator and a receiver and back as one stream, in one device-resident call
+        (ofdm_payload_transport): what every driver of the reference does first (file_reader.m -> the chain -> DeScrambler ->
+        BER_func -> display_pic.m; T3/Main_model_Task_3.m:26-32, :160-185).  payload_bits / payload_packed: as in tx_frames_fused.
+        With F = ceil(n_bits / frame_bits), for every SNR of `SNRs` and every repeat r the frames i = 0 .. F - 1 of
+        tx_frames_fused(payload, h or fading, SNR, seeds[p], Register, Time_Delay, Freq_Shift) on Philox stream frame0 + r F + i,
+        decoded as the matching sweep decodes them -- receiver="task5": rx_chain_task5 as in ber_sweep (the plan's route, its
+        MMSE / mmse-ls / OMP-route modes; no Time_Delay / Freq_Shift, time_desync = freq_desync = 0, mp_desync = 1);
+        receiver="task4": rx_chain_task4(time_desync, freq_desync, mp_desync) as in ber_sweep_task4.  The refusals of those sweeps
+        apply, under the name transport; with Register the plan must descramble with the same register.
+        Returns dict(n_bits, frames=F, errors=[n_points, repeats] wrong bits among the payload's n_bits (the zero padding of the
+        last frame is sent but not counted), BER = errors / n_bits (BER_func(input_bits, dsc_bits)), loopback = errors == 0 (the
+        reference's "Проверка пройдена")
+        (+ decoded=[n_points, repeats, ceil(n_bits / 8)] uint8, the received stream joined across frames and cut at n_bits, the
+        spare bits of the last byte 0, and decoded_bits=[n_points, repeats, n_bits] 0 / 1, with want_decoded)
+        (+ frame_errors=[n_points, repeats, F], per frame over its share of n_bits, with want_frames)
+        (+ ones=[n_points, n_bits], the sum over the repeats of decoded bit i -- ones / repeats is the mean received picture, and
+        with the payload the per-bit error counts follow -- with want_ones)); torch tensors on `device` (no host synchronisation)
+        when it is given, numpy arrays otherwise.  No output depends on max_frames_per_chunk (> 0: the frames of a chunk of the
+        plan-owned workspace; a chunk is whole frames and may cut a repeat)."""
+        try:
+            rcv = {"task5": 5, "task4": 4, 5: 5, 4: 4}[receiver]
+        except (KeyError, TypeError):
+            raise OfdmError('transport: receiver must be "task5" or "task4"') from None
+        keep, n, chan, imp, pr, pts = self._study_args("transport", SNRs, seeds, seed, h, fading, Register, Time_Delay, Freq_Shift)
+        pbuf, pp, n_bits = self._payload(device, payload_bits, payload_packed, "transport")
+        R = int(repeats)
+        F = -(-n_bits // self.frame_bits) if self.frame_bits > 0 else 0
+        nb8, Ra = (n_bits + 7) // 8, max(R, 0)                     # (a bad count is the library's refusal)
+        (dec, err, fe, ones), ptrs, flags = self._outputs(
+            device, ((n, Ra, nb8), np.uint8) if want_decoded else None, ((n, Ra), np.uint64),
+            ((n, Ra, F), np.uint32) if want_frames else None, ((n, n_bits), np.uint32) if want_ones else None)
+        L.check(self.lib.ofdm_payload_transport(self.handle, rcv, pp, n_bits, R, *chan, *imp, int(time_desync), int(freq_desync),
+                                                int(mp_desync), *pts, int(frame0), pr, int(max_frames_per_chunk), *ptrs, flags),
+                "transport")
+        if device is None:
+            err = err.astype(np.int64)
+            ber = err / np.float64(max(n_bits, 1))
+        else:
+            ber = err.double() / torch.full((1,), float(max(n_bits, 1)), dtype=torch.float64, device=err.device)
+        out = dict(n_bits=n_bits, frames=F, errors=err, BER=ber, loopback=err == 0)
+        if want_decoded:
+            out["decoded"] = dec
+            if device is None:
+                out["decoded_bits"] = np.unpackbits(dec, axis=2)[:, :, :n_bits]
+            else:
+                sh = torch.arange(7, -1, -1, dtype=torch.int16, device=dec.device)
+                out["decoded_bits"] = ((dec.to(torch.int16).unsqueeze(-1) >> sh) & 1).to(torch.uint8).reshape(n, Ra, -1)[:, :, :n_bits]
+        if want_frames:
+            out["frame_errors"] = fe
+        if want_ones:
+            out["ones"] = ones
+        return out
 
     def estimator_study(self, SNRs, frames_per_point, h=None, fading=None, mmse="ls", seeds=None, seed=1, frame0=0, device=None,
                         want_frames=False, max_frames_per_chunk=0):

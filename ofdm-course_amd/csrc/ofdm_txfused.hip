@@ -41,11 +41,16 @@
 // fill a TxfCall and a TxfGenOut and forward to one body (txf_frames): given impairments it launches the draw kernel and
 // tx_channel_imp_kernel, else tx_channel_fused_kernel; given a TxfFade, tx_fade_draw_kernel and tx_channel_fade_kernel
 // (tx_channel_imp_fade_kernel given impairments too).  The sweeps use txf_workspace and txf_generate (txf_generate.hpp).
+//
+// ofdm_tx_frames_payload is ofdm_tx_frames_fused_ex / _fading_ex with the caller's bits in place of the payload draw: the bit stage
+// of a chunk is payload_frames_kernel (ofdm_payload.hip) instead of tx_bits_kernel, the symbol stage reads the bytes it wrote (or
+// the Scrambler's), every other stage and every other draw is the same.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
 #include "fft_core.hpp"
+#include "payload_plan.hpp"
 #include "tx_philox.hpp"
 #include "txf_generate.hpp"
 
@@ -401,14 +406,15 @@ int txf_workspace(ofdm_rx_plan* pl, int64_t ch, const TxfUse& u, TxfBuffers& b) 
 
 int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf,
                  const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref, const TxfImp* imp,
-                 const TxfFade* fade) {
+                 const TxfFade* fade, const TxfPayload* src) {
   const int64_t frame_bits = (int64_t)pl->nd * pl->n_symb * pl->bps;
-  OFDM_TRY(tx_bits_device(pl, ref, scr_reg15 ? b.b0 : nullptr, k0, k1, stream0, nf));
+  if (src) OFDM_TRY(payload_frames_device(pl, *src, nf, b.b0, ref));   // the caller's bits: the only stage that differs
+  else OFDM_TRY(tx_bits_device(pl, ref, scr_reg15 ? b.b0 : nullptr, k0, k1, stream0, nf));
   if (scr_reg15) {                                              // Scrambler.m per frame, register reset (T5:58-69)
     OFDM_TRY(ofdm_Scrambler_frames(scr_reg15, b.b0, frame_bits, nf, b.b1, OFDM_DEVICE | (pl->f64 ? OFDM_F64 : 0)));
     if (scref) OFDM_TRY(tx_pack_bits_device(pl, b.b1, scref, nf));
   }
-  OFDM_TRY(txf_symbols(pl, b.tx, b.partial, scr_reg15 ? b.b1 : nullptr, k0, k1, stream0, nf));
+  OFDM_TRY(txf_symbols(pl, b.tx, b.partial, scr_reg15 ? b.b1 : src ? b.b0 : nullptr, k0, k1, stream0, nf));
   if (imp)
     OFDM_TRY(tx_draw_device(pl, imp->sto, imp->cfo, imp->sto_mode, imp->sto_value, imp->cfo_mode, imp->cfo_value, k0, k1,
                             stream0, nf));
@@ -433,10 +439,19 @@ struct TxfGenOut {
   double* taps;
 };
 
-// the body of the four generator entries: the checks of txf_generator_prelude, then c.n_frames frames from c.frame0 on in
-// chunks of the plan-owned workspace.  imp: the entry's impairments (null: none, no draw kernel, the plain channel pass).
+// the caller's payload of ofdm_tx_frames_payload, where `flags` says: frame f of the call carries the stream bits
+// (first_frame + f) frame_bits .. (payload_plan.hpp)
+struct TxfGivenBits {
+  const uint8_t* payload;
+  int64_t n_bits, first_frame;
+  bool both_channels;                                // h and a tap-delay line are given: refused
+};
+
+// the body of the five generator entries: the checks of txf_generator_prelude (given: behind the payload's own,
+// payload_generator_prelude), then c.n_frames frames from c.frame0 on in chunks of the plan-owned workspace.  imp: the entry's
+// impairments (null: none, no draw kernel, the plain channel pass).  given: the bits in place of the payload draw.
 static int txf_frames(ofdm_rx_plan* pl, TxfCall c, double snr_db, uint64_t seed, const TxfImp* imp, const TxfGenOut& out,
-                      int flags) {
+                      int flags, const TxfGivenBits* given = nullptr) {
   OFDM_TRY(ensure_init());
   const TxfShape s = pl ? txf_shape(pl) : TxfShape{};
   c.plan = pl ? &s : nullptr;
@@ -446,7 +461,10 @@ static int txf_frames(ofdm_rx_plan* pl, TxfCall c, double snr_db, uint64_t seed,
   TxfChannel ch;
   TxfFade cf;
   TxfWhy why;
-  OFDM_TRY(txf_refused(txf_generator_prelude(c, ch, cf.gains, why), why));
+  if (given)
+    OFDM_TRY(txf_refused(payload_generator_prelude(c, given->payload != nullptr, given->n_bits, given->first_frame,
+                                                   given->both_channels, ch, cf.gains, why), why));
+  else OFDM_TRY(txf_refused(txf_generator_prelude(c, ch, cf.gains, why), why));
   const int64_t n_frames = c.n_frames;
   if (n_frames == 0) return OFDM_OK;
   OFDM_TRY(tx_dict_device(pl));
@@ -466,6 +484,13 @@ static int txf_frames(ofdm_rx_plan* pl, TxfCall c, double snr_db, uint64_t seed,
   u.scr = c.scr_reg15 != nullptr;
   u.imp = imp != nullptr;
   u.fade_taps = n_taps;
+  u.payload = given != nullptr;
+  TxfPayload src;
+  if (given) {
+    OFDM_TRY(payload_stage(st, given->payload, given->n_bits, &src.words));
+    src.n_bits = given->n_bits;
+    src.first_frame = given->first_frame;
+  }
   const int64_t CH = txf_chunk(s, u, n_frames, 0);
   TxfBuffers b;
   OFDM_TRY(txf_workspace(pl, CH, u, b));
@@ -479,11 +504,12 @@ static int txf_frames(ofdm_rx_plan* pl, TxfCall c, double snr_db, uint64_t seed,
     ci.sto = dsto ? (int64_t*)dsto + c0 : b.sto;
     ci.cfo = dcfo ? (double*)dcfo + c0 : b.cfo;
     cf.taps_out = dtaps ? (c64*)dtaps + c0 * n_taps : nullptr;
+    src.frame = c0;
     OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(c.frame0 + c0), nf, c.scr_reg15, b,
                           (unsigned char*)drx + cs * (size_t)frame_samples * c0,
                           dref ? (uint32_t*)((uint8_t*)dref + fb * c0) : nullptr,
                           dscref ? (uint32_t*)((uint8_t*)dscref + fb * c0) : nullptr, imp ? &ci : nullptr,
-                          c.fading ? &cf : nullptr));
+                          c.fading ? &cf : nullptr, given ? &src : nullptr));
   }
   return st.finish();
 }
@@ -527,3 +553,22 @@ extern "C" int ofdm_tx_frames_fading_ex(ofdm_rx_plan* pl, const int32_t* tap_del
                     snr_db, seed, &imp, TxfGenOut{rx_out, ref_bits_out, sc_ref_bits_out, sto_out, cfo_out, taps_out}, flags);
 }
 
+
+// ofdm_tx_frames_fused_ex / ofdm_tx_frames_fading_ex in one entry (h, or the tap-delay line; both STO / CFO modes 0 and no
+// sto_out / cfo_out: the plain channel pass of ofdm_tx_frames_fused / _fading) with the payload draw replaced by the caller's bits
+extern "C" int ofdm_tx_frames_payload(ofdm_rx_plan* pl, const uint8_t* payload, int64_t n_bits, int64_t first_frame, const void* h,
+                                      int h_len, const int32_t* tap_delay, const double* tap_power, int n_taps, double snr_db,
+                                      uint64_t seed, int64_t frame0, int64_t n_frames, const uint8_t* scr_reg15, int sto_mode,
+                                      int64_t sto_value, int cfo_mode, double cfo_value, void* rx_out, uint8_t* ref_bits_out,
+                                      uint8_t* sc_ref_bits_out, double* taps_out, int64_t* sto_out, double* cfo_out, int flags) {
+  const bool fading = tap_delay || tap_power || n_taps != 0;
+  const TxfGivenBits given{payload, n_bits, first_frame, fading && h && h_len != 0};
+  const TxfImp imp(sto_mode, sto_value, cfo_mode, cfo_value);
+  const bool imp_on = sto_mode != 0 || cfo_mode != 0 || sto_out || cfo_out;
+  TxfCall c("tx_frames_payload", frame0, n_frames, scr_reg15);
+  c.with_imp(sto_mode, cfo_mode);
+  if (fading) c.with_fading(tap_delay, tap_power, n_taps);
+  else c.with_h(h, h_len);
+  return txf_frames(pl, c, snr_db, seed, imp_on ? &imp : nullptr,
+                    TxfGenOut{rx_out, ref_bits_out, sc_ref_bits_out, sto_out, cfo_out, fading ? taps_out : nullptr}, flags, &given);
+}

@@ -45,6 +45,20 @@ struct TxfBuffers {
   void* hest = nullptr;
 };
 
+// the bit source of a chunk where it is not the Philox draw: the caller's packed stream (ofdm_payload.hip), staged as words with a
+// zero word behind it; the chunk's first frame is frame `frame` of the call (payload_position, payload_plan.hpp)
+struct TxfPayload {
+  const uint32_t* words = nullptr;
+  int64_t n_bits = 0, first_frame = 0, period = INT64_MAX;
+  int64_t frame = 0;                                 // set per chunk by the loop that generates it
+};
+
+// payload_frames_kernel: the chunk's bits, one byte each (b0: what ofdm_Scrambler_frames and txf_symbols read), and its packed
+// reference words (ref, optional)
+int payload_frames_device(const ofdm_rx_plan* pl, const TxfPayload& src, int64_t nf, uint8_t* b0, uint32_t* ref);
+// the caller's packed stream of n_bits (where the call's flags say) as words in device memory with a zero word behind it
+int payload_stage(Stage& st, const uint8_t* payload, int64_t n_bits, const uint32_t** words);
+
 // what the checks of txf_plan.hpp read from a plan, and a refusal of theirs as the entry's return code and last-error text
 TxfShape txf_shape(const ofdm_rx_plan* pl);
 int txf_refused(int id, const TxfWhy& w);
@@ -61,9 +75,11 @@ int txf_symbols(const ofdm_rx_plan* pl, void* tx, double* partial, const uint8_t
 // imp (optional): the Task-4 impairments, the channel pass of tx_channel_imp_kernel
 // fade (optional): a channel per frame -- the draws into fade->amp (and fade->taps_out), the channel pass of
 // tx_channel_fade_kernel; with imp too, both draws and the channel pass of tx_channel_imp_fade_kernel
+// src (optional): the frames' bits from the caller's stream in place of the payload draw (b.b0 is then needed even without the
+// Scrambler); every other draw of frame f stays that of Philox stream stream0 + f
 int txf_generate(ofdm_rx_plan* pl, const TxfChannel& ch, double snr_lin, uint32_t k0, uint32_t k1, uint32_t stream0, int64_t nf,
                  const uint8_t* scr_reg15, const TxfBuffers& b, void* rx, uint32_t* ref, uint32_t* scref,
-                 const TxfImp* imp = nullptr, const TxfFade* fade = nullptr);
+                 const TxfImp* imp = nullptr, const TxfFade* fade = nullptr, const TxfPayload* src = nullptr);
 
 // ofdm_ber_sweep.hip, for the channel study beside the Task-4 sweep: the channel-estimate error sum_k |H_f(k) - hest[f][k]|^2 of
 // nf frames (t5_frame_nmse_kernel; amp_stride: dl.n for a channel per frame, 0 for one static channel), the delays of a call's

@@ -125,7 +125,7 @@ inline int txf_fading(const int32_t* tap_delay, const double* tap_power, int n_t
 // ---- the plan-owned workspace (pl->ws_txf): ONE table of its regions.  A region a call does not use has 0 bytes per frame.
 enum { TXF_R_TX,            // the chunk's TX samples
        TXF_R_PARTIAL,       // sum |x|^2 per symbol, double
-       TXF_R_B0, TXF_R_B1,  // Scrambler on: payload bits and scrambled bits, one byte each
+       TXF_R_B0, TXF_R_B1,  // Scrambler on: payload bits and scrambled bits, one byte each (B0 also for a caller's payload)
        TXF_R_RX, TXF_R_REF, // sweep: the chunk's RX frames and their packed reference bits
        TXF_R_STO, TXF_R_CFO,// impairments on: the chunk's draws (int64 / double)
        TXF_R_AMP,           // fading: the chunk's tap amplitudes [ch][fade_taps], complex double
@@ -138,6 +138,7 @@ struct TxfUse {             // what a call needs of the workspace
   bool imp = false;         // the Task-4 impairment draws
   int fade_taps = 0;        // > 0: a per-frame channel of that many taps
   bool hest = false;        // the receiver's channel estimates (sweep)
+  bool payload = false;     // the caller's payload (payload_plan.hpp): its bits, one byte each, even without the Scrambler
 };
 
 struct TxfRegions {
@@ -151,7 +152,8 @@ inline TxfRegions txf_regions(const TxfShape& s, const TxfUse& u) {
   TxfRegions r{};
   r.per_frame[TXF_R_TX] = cs * fs;
   r.per_frame[TXF_R_PARTIAL] = 8 * (size_t)s.n_symb;
-  r.per_frame[TXF_R_B0] = r.per_frame[TXF_R_B1] = u.scr ? frame_bits : 0;
+  r.per_frame[TXF_R_B0] = u.scr || u.payload ? frame_bits : 0;
+  r.per_frame[TXF_R_B1] = u.scr ? frame_bits : 0;
   r.per_frame[TXF_R_RX] = u.sweep ? cs * fs : 0;
   r.per_frame[TXF_R_REF] = u.sweep ? (size_t)s.frame_words * 4 : 0;
   r.per_frame[TXF_R_STO] = r.per_frame[TXF_R_CFO] = u.imp ? 8 : 0;

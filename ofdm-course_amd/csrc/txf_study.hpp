@@ -1,5 +1,5 @@
 // The scaffold of a sweep or a study on the fused frame generator, HIP side: the point x chunk loop with the generation inside
-// (txf_sweep_points), the generator arguments every study entry takes (TxfStudyArgs), and the two ways a study stages an output: an
+// (txf_sweep_points; its bit source the Philox draw or, for the transport, the caller's stream), the generator arguments every study entry takes (TxfStudyArgs), and the two ways a study stages an output: an
 // accumulator table (txf_table) and a per-frame array (TxfFrameOut).  What a call decides -- its checks, its channel, its chunk --
 // is txf_plan.hpp's (txf_study_prelude, txf_study_use) and the study's own plan header's.
 #pragma once
@@ -18,6 +18,7 @@ struct TxfPoints {
   int64_t n_points, frames_per_point, frame0;
   bool ref = true;             // the chunk's packed payload bits go to b.ref (false: nothing compares them, they are not written)
   uint32_t* scref = nullptr;   // the chunk's packed scrambled bits (the error study's channel side)
+  const TxfPayload* payload = nullptr;   // the frames' bits from the caller's stream (the transport); null: the Philox draw
 };
 
 // every point of a sweep, chunk by chunk of at most CH frames: the chunk generated into the workspace, then body(b, nf, p, o) with
@@ -37,6 +38,8 @@ int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfPoints& pt
   TxfFade cf;
   if (fade) cf = *fade;
   cf.amp = b.amp;
+  TxfPayload cp;
+  if (pt.payload) cp = *pt.payload;
   for (int64_t p = 0; p < pt.n_points; ++p) {
     const double snr_lin = std::pow(10.0, pt.snr_db[p] / 10.0);
     const uint32_t k0 = (uint32_t)pt.seeds[p], k1 = (uint32_t)(pt.seeds[p] >> 32);
@@ -44,8 +47,9 @@ int txf_sweep_points(ofdm_rx_plan* pl, const TxfChannel& ch, const TxfPoints& pt
       const int64_t nf = std::min<int64_t>(CH, pt.frames_per_point - c0);
       const int64_t o = p * pt.frames_per_point + c0;
       if (imp && imp->sto) { ci.sto = imp->sto + o; ci.cfo = imp->cfo + o; }
+      cp.frame = c0;
       OFDM_TRY(txf_generate(pl, ch, snr_lin, k0, k1, (uint32_t)(pt.frame0 + c0), nf, scr_reg15, b, b.rx, pt.ref ? b.ref : nullptr,
-                            pt.scref, imp ? &ci : nullptr, fade ? &cf : nullptr));
+                            pt.scref, imp ? &ci : nullptr, fade ? &cf : nullptr, pt.payload ? &cp : nullptr));
       OFDM_TRY(body(b, nf, p, o));
     }
   }
